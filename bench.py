@@ -21,13 +21,15 @@ value distribution, so that no step repeats the previous step's inputs.
 Timed region.  Several proofs are in flight per GPU (that is how the latency-bound tails of one proof hide under the bulk
 kernels of another), so a region of K proofs that starts and ends with an empty GPU contains a ramp-up and a drain that
 weigh more the smaller K is (K = 20 with 12 in flight is 1.7 pipeline fills).  The headline is therefore measured in
-steady state: after W warm-up proofs the stream of proofs keeps running and B consecutive blocks of EXACTLY K
-completions each are timed (B chosen so that B·K >= 1500 whatever K is).  `value` = B·K proofs ÷ the time from the last
-warm-up completion to the last timed completion - proofs ÷ elapsed over the WHOLE steady window, no block dropped
-(max elapsed over ranks) - and `ms_per_step` is that time ÷ (B·K).  The median block (round 3's headline, which is biased
-high by up to 3 % on a bursty stream: long blocks are the ones a median drops) is kept as `timing.median_block`, and the
-classical bracket (barrier + synchronise, K proofs, synchronise + barrier; max over ranks) is measured in the same run
-and reported as `timing.bracketed`.
+steady state: after W warm-up proofs the stream of proofs keeps running and EXACTLY K consecutive completions are timed.
+`value` = K proofs ÷ the time from the last warm-up completion to the K-th timed completion (max elapsed over ranks), and
+`ms_per_step` is that time ÷ K.  For the block statistics the K completions are split into B consecutive blocks
+(--blocks, default min(K, 5)); the median block (round 3's headline, which is biased high by up to 3 % on a bursty
+stream: long blocks are the ones a median drops) is kept as `timing.median_block`, and the classical bracket (barrier +
+synchronise, K proofs, synchronise + barrier; max over ranks) is measured in the same run and reported as
+`timing.bracketed`.  The k-th proof of the headline stream proves assignment k mod --assignments with an (r, s) drawn
+from a seed made of k and the rank, so the same arguments give the same inputs step for step in every run;
+--dump-outputs DIR writes the proof of the last timed step as DIR/proof_{a,b,c}.npy.
 
 Multi-GPU: `value` is always the replica throughput — proofs are independent objects, each rank proves its
 own stream with a full copy of the key, no data-path collective (config 5); `value_per_rank` lists every rank's own rate.
@@ -157,8 +159,15 @@ def parse():
     ap.add_argument("--no-clock-probe", action="store_true",
                     help="do not sample the shader clock during the timed proofs (profiling runs: under rocprofv3 --pmc kernels "
                          "are serialised and the probe's sleeping wave would hold the others up)")
-    ap.add_argument("--blocks", type=int, default=0, help="timed blocks of --steps proofs (0 = enough for 1500 proofs, at least 3)")
-    return ap.parse_args()
+    ap.add_argument("--blocks", type=int, default=0,
+                    help="consecutive blocks the --steps timed proofs are split into for the block statistics (0 = min(steps, 5))")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the proof the last timed step returned as DIR/proof_a.npy, proof_b.npy, proof_c.npy (its 64 / 128 / 64 "
+                         "ark-serialize uncompressed bytes as float64 values 0..255), on rank 0")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def visible_gpus_without_hip() -> int:
@@ -417,16 +426,33 @@ def cold_start_record(cc, a, pk, cm, w_np, l, m, M, fresh_rs, prover, ws_dev, lo
         shutil.rmtree(tmp, ignore_errors=True)
 
 
-def block_times(done, warmup, steps, blocks, t_start):
-    """durations of `blocks` consecutive blocks of `steps` completions after the first `warmup` completions"""
+def block_times(done, warmup, n_timed, blocks, t_start):
+    """seconds per proof of each of the `blocks` consecutive blocks that the `n_timed` completions after the first `warmup`
+    completions are split into (block sizes differ by at most one)"""
     edge = lambda i: done[i - 1] if i > 0 else t_start
-    return [edge(warmup + (b + 1) * steps) - edge(warmup + b * steps) for b in range(blocks)]
+    e = [warmup + b * n_timed // blocks for b in range(blocks + 1)]
+    return [(edge(e[b + 1]) - edge(e[b])) / (e[b + 1] - e[b]) for b in range(blocks)]
 
 
 def n_blocks(a):
-    if a.blocks > 0:
-        return a.blocks
-    return max(3, math.ceil(1500 / max(1, a.steps)))  # the steady window is >= 1500 proofs whatever --steps is
+    """blocks the headline's window of exactly --steps proofs is split into for the block statistics"""
+    return max(1, min(a.blocks if a.blocks > 0 else 5, a.steps))
+
+
+def step_rs(k, rank, modulus):
+    """(r, s) of the k-th proof of the headline stream: drawn from a seed made of k and the rank, whichever caller thread
+    takes proof k, so that a step proves the same inputs in every run with the same arguments"""
+    g = random.Random(((1234 + rank) << 32) | k)
+    return g.randrange(modulus), g.randrange(modulus)
+
+
+def dump_proof(out_dir, data):
+    """a proof's 256 bytes (a | b | c, ark-serialize uncompressed) as DIR/proof_{a,b,c}.npy, float64 byte values"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    b = np.frombuffer(bytes(data), dtype=np.uint8).astype(np.float64)
+    for name, part in (("proof_a", b[:64]), ("proof_b", b[64:192]), ("proof_c", b[192:])):
+        np.save(os.path.join(out_dir, name + ".npy"), part)
 
 
 def main():
@@ -497,6 +523,8 @@ def main():
         with rs_lock:
             return rs_rng.randrange(R), rs_rng.randrange(R)
 
+    keyed_rs = lambda k: step_rs(k, rank, R)
+
     def make_workload(bits, seed_off, dims=None):
         l_, m_, M_ = dims or (l, m, M)
         cm_, w_ = wl.synthetic_circuit(0xC5E5CE47 + seed_off, l_, m_, M_, bits, 3, profile=a.profile)
@@ -510,11 +538,10 @@ def main():
         steady_stream(prove_k, inflight, inflight)
         torch.cuda.synchronize()
 
-    def measure(prove_k, steps, warmup, blocks, sync_ranks, clock=None, threads=None):
-        """-> (seconds of the steady window of blocks x steps proofs [max over ranks], record, every rank's own proofs/s).
-        prove_k(k): the k-th proof of the stream."""
+    def measure(prove_k, n_timed, warmup, blocks, sync_ranks, clock=None, threads=None):
+        """-> (seconds of the steady window of n_timed proofs [max over ranks], record, every rank's own proofs/s); the window
+        is split into `blocks` consecutive blocks for the block statistics.  prove_k(k): the k-th proof of the stream."""
         threads = threads or inflight
-        n_timed = blocks * steps
         total = warmup + n_timed + threads                   # the tail keeps the end of the window in steady state
         if sync_ranks:
             barrier_sync(world)
@@ -529,12 +556,13 @@ def main():
         cpu_busy = (time.process_time() - cpu0) / max(1e-9, time.perf_counter() - t_start)
         torch.cuda.synchronize()
         window = done[warmup + n_timed - 1] - (done[warmup - 1] if warmup > 0 else t_start)
-        bt = sorted(block_times(done, warmup, steps, blocks, t_start))
+        bt = sorted(block_times(done, warmup, n_timed, blocks, t_start))      # seconds per proof of each block
         med = bt[len(bt) // 2]
+        per_block = n_timed / blocks
         rec = {"window_proofs": n_timed, "window_s": round(window, 4), "blocks": blocks,
-               "median_block": {"ms_per_step": round(med / steps * 1e3, 3), "value_this_rank": round(steps / med, 3),
+               "median_block": {"ms_per_step": round(med * 1e3, 3), "value_this_rank": round(1.0 / med, 3),
                                 "spread_pct": round((bt[-1] - bt[0]) / med * 100.0, 2),
-                                "block_ms_min_median_max": [round(bt[0] * 1e3, 2), round(med * 1e3, 2), round(bt[-1] * 1e3, 2)]},
+                                "block_ms_min_median_max": [round(x * per_block * 1e3, 2) for x in (bt[0], med, bt[-1])]},
                "host_cpus_busy": round(cpu_busy, 2),     # process CPU seconds per second of the stream: what the callers cost the host
                # what ONE caller waits for its proof inside this stream (call to return of cg_prove*, the proofs of the timed window)
                "latency_ms": percentiles_ms([d for t_, d in lat if (done[warmup - 1] if warmup > 0 else t_start) < t_ <= done[warmup + n_timed - 1]])}
@@ -590,15 +618,16 @@ def main():
                 pinned.append(hb)
         return pinned
 
-    def stream_of(origin, sample=None):
+    def stream_of(origin, sample=None, keep=None):
         """prove_k(k) for assignments arriving from `origin`: 'host' = pageable host memory (numpy arrays) through cg_prove,
-        'pinned' = page-locked host memory through cg_prove, 'device' = already in HBM through cg_prove_dev"""
+        'pinned' = page-locked host memory through cg_prove, 'device' = already in HBM through cg_prove_dev.  With `keep`
+        (the headline stream) (r, s) is keyed_rs(k), and the proof of step keep["k"] is kept as keep["proof"]."""
         if origin == "pinned":
             pinned_buffers()
 
         def prove_k(k):
             j = k % len(ws_np)
-            r_, s_ = fresh_rs()
+            r_, s_ = keyed_rs(k) if keep is not None else fresh_rs()
             if origin == "host":
                 p = prover.prove_host_ptr(ws_np[j].ctypes.data, r_, s_)
             elif origin == "pinned":
@@ -607,21 +636,28 @@ def main():
                 p = prover.prove_dev(ws_dev[j].data_ptr(), r_, s_)
             if sample is not None and j == 0:
                 sample["proof"] = (k, r_, s_, p.data)
+            if keep is not None and k == keep.get("k"):
+                keep["proof"] = p.data
         return prove_k
 
     # two more caller threads than proof slots when the witness arrives from the host: a context holds that many more upload
     # buffers, so the next assignments arrive while every working set is busy
     callers_of = lambda origin: inflight if origin == "device" else inflight + 2
-    prove_headline_k = stream_of(a.witness, timed_sample)
+    last_step = {}          # the proof of the last timed step (--dump-outputs)
+    prove_headline_k = stream_of(a.witness, timed_sample, last_step)
     callers = callers_of(a.witness)
 
     blocks = n_blocks(a)
-    n_timed = blocks * a.steps
+    n_timed = a.steps
     prime(prove_headline_k)
     clock = ClockSampler(cc, local_rank) if rank == 0 and not a.no_clock_probe else None
-    dt, timing, per_rank = measure(prove_headline_k, a.steps, a.warmup, blocks, True, clock, threads=callers)
+    last_step["k"] = a.warmup + n_timed - 1             # proof number of the last timed step in the measured stream
+    dt, timing, per_rank = measure(prove_headline_k, n_timed, a.warmup, blocks, True, clock, threads=callers)
+    last_step.pop("k")
     value = n_timed * world / dt
     checked_proof = timed_sample.get("proof")           # taken before any later leg overwrites it
+    if a.dump_outputs and rank == 0:
+        dump_proof(a.dump_outputs, last_step["proof"])
     dt_br = bracketed(prove_headline_k, a.steps, True, threads=callers)
     info = prover.info()
     log("steady state %.2f proofs/s (%d proofs in %.2f s; median block %.2f, spread %.1f %%); bracketed %.2f; shader clock %s GHz" %
@@ -759,8 +795,9 @@ def main():
         "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (BN254 Fq/Fr, 254-bit modular integers)",
         "data": "synthetic",
         "value_per_rank": [round(x, 3) for x in per_rank],
-        "timing": dict(timing, method="steady state: `blocks` x `steps` consecutive proof completions with the pipeline kept primed; "
-                                      "value = proofs / elapsed over that whole window (max elapsed over ranks)",
+        "timing": dict(timing, method="steady state: `steps` consecutive proof completions with the pipeline kept primed, split into "
+                                      "`blocks` blocks for the block statistics; value = proofs / elapsed over that whole window "
+                                      "(max elapsed over ranks)",
                        bracketed={"ms_per_step": round(dt_br / a.steps * 1e3, 3), "value": round(a.steps * world / dt_br, 3),
                                   "method": "barrier + synchronise, `steps` proofs, synchronise + barrier (max over ranks)"}),
         "config": {"workload": "%s shape: D=2^%d, m=%d, M=%d, l=%d, nnz=%d (%s mix); bit_fraction=%.2f; pk from seeded trapdoor (GPU setup)" %
@@ -859,7 +896,7 @@ def main():
                       "'%s' one.  From host memory every proof uploads its 32·M-byte assignment first (the reference's caller has "
                       "the witness on the host, creds/src/lib.rs:274-283); uploads overlap the other proofs in flight (proof_slots + 2 "
                       "caller threads)" % a.witness}
-        hblocks = max(3, blocks // 2)
+        hblocks = max(3, math.ceil(1500 / max(1, a.steps)) // 2)     # blocks of --steps proofs: >= 750 whatever --steps is
         hn = hblocks * a.steps
         try:
             for origin in ("host", "pinned", "device"):
@@ -868,7 +905,7 @@ def main():
                 pk_ = stream_of(origin)
                 thr = callers_of(origin)
                 steady_stream(pk_, inflight, thr)
-                d_o, rec_o, _ = measure(pk_, a.steps, min(a.warmup, inflight), hblocks, True, threads=thr)
+                d_o, rec_o, _ = measure(pk_, hn, min(a.warmup, inflight), hblocks, True, threads=thr)
                 rates[origin] = hn * world / d_o
                 rec = dict(rec_o, proofs_per_s=round(rates[origin], 3), ms_per_step=round(d_o / hn * 1e3, 4), over_value=round(rates[origin] / value, 4))
                 if origin == "device":
@@ -1347,7 +1384,7 @@ def main():
             def prove2_k(k, p2=p2, ws2=ws2):
                 p2.prove_host_ptr(ws2[k % len(ws2)].ctypes.data, *fresh_rs())
             prime(prove2_k)
-            d2, rec2, _ = measure(prove2_k, 100, inflight, 3, False, threads=inflight + 2)
+            d2, rec2, _ = measure(prove2_k, 300, inflight, 3, False, threads=inflight + 2)
             w2d = torch.from_numpy(ws2[0]).to(dev)
             tm2, ph2 = phase_record(p2, w2d, reps=2)
             r_, s_ = fresh_rs()
@@ -1393,7 +1430,7 @@ def main():
             def prove_sweep_k(k, ps=ps, wsd=wsd):
                 ps.prove_dev(wsd[k % len(wsd)].data_ptr(), *fresh_rs())
             prime(prove_sweep_k)
-            d_s, rec_s, _ = measure(prove_sweep_k, ksteps, inflight, 3, False)
+            d_s, rec_s, _ = measure(prove_sweep_k, 3 * ksteps, inflight, 3, False)
             tms, phs = phase_record(ps, wsd[0], reps=1)
             sweep.append({"bit_fraction": bf, "wires": wl.wire_stats(w_s), "nnz": cm_s.a.nnz + cm_s.b.nnz + cm_s.c.nnz,
                           "proofs_per_s": round(3 * ksteps / d_s, 3), "g1_msm_scalar_adds_per_s": round(tms["msm_g1_pairs"] * 3 * ksteps / d_s, 1),

@@ -41,22 +41,45 @@ def test_gpus_2_without_a_launcher_starts_its_own_ranks_or_says_why():
 
 
 def test_block_count_and_block_times():
+    """the timed window is exactly --steps proofs (the driver sizes later runs by ms_per_step x steps); --blocks only splits
+    that window for the block statistics"""
     class A:
         blocks = 0
         steps = 20
-    assert bench.n_blocks(A) == 75                      # 75 x 20 = 1500: the steady window does not depend on --steps
-    A.steps = 400
+    assert bench.n_blocks(A) == 5
+    A.steps = 3
+    assert bench.n_blocks(A) == 3                       # never more blocks than timed proofs
+    A.steps, A.blocks = 400, 4
     assert bench.n_blocks(A) == 4
-    A.steps = 5000
-    assert bench.n_blocks(A) == 3
-    A.blocks = 4
-    assert bench.n_blocks(A) == 4
-    # completions one per millisecond from t = 1 ms: every block of 10 lasts 10 ms whatever the warm-up
+    A.steps = 2
+    assert bench.n_blocks(A) == 2
+    # completions one per millisecond from t = 1 ms: 1 ms per proof in every block of a 50-proof window, whatever the warm-up
     done = [0.001 * (i + 1) for i in range(100)]
-    bt = bench.block_times(done, 7, 10, 5, 0.0)
-    assert all(abs(x - 0.010) < 1e-12 for x in bt) and len(bt) == 5
+    bt = bench.block_times(done, 7, 50, 5, 0.0)
+    assert all(abs(x - 0.001) < 1e-12 for x in bt) and len(bt) == 5
     # without warm-up the first block starts at t_start
-    assert abs(bench.block_times(done, 0, 10, 1, 0.0)[0] - 0.010) < 1e-12
+    assert abs(bench.block_times(done, 0, 10, 1, 0.0)[0] - 0.001) < 1e-12
+    # blocks that do not divide the window (sizes 2, 3, 3): every completion of the window in exactly one block
+    sq = [0.001 * (i + 1) ** 2 for i in range(20)]
+    bt = bench.block_times(sq, 4, 8, 3, 0.0)
+    assert len(bt) == 3 and abs(bt[0] * 2 + bt[1] * 3 + bt[2] * 3 - (sq[11] - sq[3])) < 1e-12
+    assert abs(bt[0] - (sq[5] - sq[3]) / 2) < 1e-12
+
+
+def test_steps_and_warmup_are_checked():
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *bad], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and r.stdout.strip() == ""
+
+
+def test_dump_proof_writes_the_three_points_as_float_arrays(tmp_path):
+    import numpy as np
+    data = bytes(range(256))
+    bench.dump_proof(str(tmp_path / "out"), data)
+    got = {n: np.load(str(tmp_path / "out" / (n + ".npy"))) for n in ("proof_a", "proof_b", "proof_c")}
+    assert [got[n].shape for n in ("proof_a", "proof_b", "proof_c")] == [(64,), (128,), (64,)]
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert bytes(np.concatenate([got["proof_a"], got["proof_b"], got["proof_c"]]).astype(np.uint8)) == data
 
 
 def test_gpus_are_counted_without_touching_hip(monkeypatch):
