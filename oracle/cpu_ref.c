@@ -596,6 +596,19 @@ int ref_witness_map(const csr_t abc[3], uint64_t l, uint64_t m, uint64_t M, cons
     free(h);
     return 0;
 }
+/* <M_i, w> for every row i < rows (evaluate_constraint, r1cs_to_qap.rs:16-45): the row values a test instance is made
+ * satisfiable with (tests/circom_rows.py); canonical in and out */
+int ref_spmv(const csr_t* mat, uint64_t rows, uint64_t M, const uint8_t* w_bytes, uint8_t* out, int nthreads) {
+    fe* w = (fe*)malloc(sizeof(fe) * (M ? M : 1));
+    fe* v = (fe*)malloc(sizeof(fe) * (rows ? rows : 1));
+    _Pragma("omp parallel for num_threads(nthreads)")
+    for (uint64_t i = 0; i < M; ++i) fe_from_canonical(&FR, &w[i], w_bytes + 32 * i);
+    spmv(mat, rows, w, v, nthreads);
+    _Pragma("omp parallel for num_threads(nthreads)")
+    for (uint64_t i = 0; i < rows; ++i) fe_to_canonical(&FR, out + 32 * i, &v[i]);
+    free(w); free(v);
+    return 0;
+}
 
 /* ---- the QAP at one point: what the KEY CHECK of the full-size tests needs (oracle/keycheck.py) -----------------
  * LibsnarkReduction::instance_map_with_evaluation (r1cs_to_qap.rs:103-147) at t: u_j = L_j(t) over the size-D subgroup

@@ -43,6 +43,7 @@ def lib():
         L.ref_witness_map.argtypes = [C.POINTER(_Csr), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int]
         L.ref_prove.argtypes = [C.POINTER(_Pk), C.POINTER(_Csr), C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RefTimings)]
+        L.ref_spmv.argtypes = [C.POINTER(_Csr), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int]
         L.ref_qap_at.argtypes = [C.POINTER(_Csr), C.c_uint64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6
         L.ref_fr_inner.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.ref_fr_combine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 4
@@ -139,6 +140,16 @@ def witness_map(mats, l, m, M, witness, nthreads=1) -> np.ndarray:
     rc = lib().ref_witness_map(arr, l, m, M, w.ctypes.data, h.ctypes.data, nthreads)
     assert rc == 0
     return h
+
+
+def spmv(mat, rows, M, witness, nthreads=1) -> np.ndarray:
+    """<M_i, w> for every row i < rows (evaluate_constraint, r1cs_to_qap.rs:16-45): rows x 32 canonical bytes"""
+    arr, _k = _csr3((mat, mat, mat))
+    w = _u8(witness)
+    out = np.zeros(max(1, rows) * 32, np.uint8)
+    rc = lib().ref_spmv(arr, rows, M, w.ctypes.data, out.ctypes.data, nthreads)
+    assert rc == 0
+    return out[:rows * 32]
 
 
 def _fr(x: int) -> np.ndarray:

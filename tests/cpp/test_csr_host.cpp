@@ -138,6 +138,25 @@ static Mat random_matrix(uint64_t rows, uint64_t cols, double mean_terms, int n_
     return m;
 }
 
+// rows of the given lengths (row i: lens[i] terms), every coefficient the literal one, random columns: cheap at 8^8 terms
+static Mat unit_matrix(const std::vector<uint32_t>& lens, uint64_t cols) {
+    Mat m;
+    uint64_t nnz = 0;
+    for (uint32_t n : lens) nnz += n;
+    m.row_ptr.push_back(0);
+    m.col.resize(nnz);
+    m.coeff.assign(32 * (nnz ? nnz : 1), 0);
+    for (uint64_t t = 0; t < nnz; ++t) { m.col[t] = (uint32_t)(rnd() % cols); m.coeff[32 * t] = 1; }
+    for (uint32_t n : lens) m.row_ptr.push_back(m.row_ptr.back() + n);
+    return m;
+}
+
+static size_t levels_of(const Mat& m, uint64_t rows, uint64_t cols) {
+    HostCsr h;
+    csr_prepare_host(m.view(), rows, cols, true, true, h);
+    return h.levels.size();
+}
+
 static int bench(const char* path) {
     FILE* f = fopen(path, "rb");
     if (!f) { perror(path); return 1; }
@@ -196,6 +215,36 @@ int main(int argc, char** argv) {
         threw = false;
         try { csr_prepare_host(bad.view(), 100, 50, true, true, h); } catch (const HipError& e) { threw = e.code == CG_ERR_INVALID_ARGUMENT; }
         CHECK(threw, "non-monotone row_ptr accepted");
+    }
+    // the deep end of the sliced layout: a row of 8^(k-1) + 1 terms needs k levels (k = 6, 7, 8), 8^8 terms is the longest
+    // row 8 levels hold, one term more is refused.  Literal ones only (no dictionary work), short rows around them.
+    {
+        const uint32_t p5 = 1u << 15, p6 = 1u << 18, p7 = 1u << 21, p8 = 1u << 24;
+        const uint64_t cols = 3000;
+        const std::vector<uint32_t> deep[] = {{3, p5 + 1, 0, 9, 1}, {p6 + 1, 64, 65, 2}, {5, p7 + 1, 513, p5}};
+        const size_t want_levels[] = {6, 7, 8};
+        for (int k = 0; k < 3; ++k) {
+            Mat m = unit_matrix(deep[k], cols);
+            check_matrix(m, deep[k].size(), cols, true);
+            CHECK(levels_of(m, deep[k].size(), cols) == want_levels[k], "row of %u terms: wrong level count", deep[k][k == 1 ? 0 : 1]);
+        }
+        Mat m = unit_matrix({2, p8, 7}, cols);
+        check_matrix(m, 3, cols, true);
+        CHECK(levels_of(m, 3, cols) == 8, "row of 8^8 terms: wrong level count");
+        // the same row with one more term (inserted at its end; the row after it moves up by one)
+        m.col.insert(m.col.begin() + m.row_ptr[2], 1u);
+        m.coeff.insert(m.coeff.begin() + 32 * m.row_ptr[2], 32, 0);
+        m.coeff[32 * m.row_ptr[2]] = 1;
+        m.row_ptr[2] += 1; m.row_ptr[3] += 1;
+        CHECK(m.row_ptr[2] - m.row_ptr[1] == (uint64_t)p8 + 1, "test matrix shape");
+        HostCsr h;
+        bool threw = false;
+        try { csr_prepare_host(m.view(), 3, cols, true, true, h); } catch (const HipError& e) { threw = e.code == CG_ERR_INVALID_ARGUMENT; }
+        CHECK(threw, "row of 8^8 + 1 terms accepted by the sliced layout");
+        // without the sliced layout (the setup's transposed matrices) the same row is fine
+        HostCsr flat;
+        csr_prepare_host(m.view(), 3, cols, false, true, flat);
+        CHECK(flat.long_rows.size() == 1 && flat.long_rows[0] == 1, "long rows of the unsliced matrix");
     }
     printf("ALL OK\n");
     return 0;
