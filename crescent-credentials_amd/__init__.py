@@ -17,6 +17,11 @@ from .api import (  # noqa: F401
     IOLocations,
     ProverParams,
     create_client_state,
+    PreparedVerifyingKey,
+    ProofRejected,
+    CG_VERIFY_REJECT,
+    CG_VERIFY_ACCEPT,
+    CG_VERIFY_MALFORMED,
     ConstraintMatrices,
     Groth16,
     LibsnarkReduction,

@@ -27,6 +27,7 @@ CG_FLAG_H_COEFFICIENT_BASIS = 1
 CG_FLAG_LATENCY_MODE, CG_FLAG_THROUGHPUT_MODE, CG_FLAG_SPIN_WAIT, CG_FLAG_CONTIGUOUS_H_SHARDS, CG_FLAG_H_SCALARS_EXTERNAL = 2, 4, 8, 16, 32
 CG_FLAG_STAGED_LOAD = 64
 CG_FLAG_NO_LONE_SLOT = 128
+CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
 
 
 class CrescentGpuError(RuntimeError):
@@ -181,6 +182,11 @@ _SIGNATURES = {
     "cg_client_state_parse": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "cg_client_state_get": (C.c_int, [C.c_void_p, C.POINTER(_CgClientStateView)]),
     "cg_client_state_free": (None, [C.c_void_p]),
+    "cg_pvk_load": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_int32]),
+    "cg_pvk_num_inputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cg_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cg_pvk_free": (None, [C.c_void_p]),
+    "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -975,9 +981,90 @@ class Groth16:
         """prover.rs:160-173 (r = s = 0)."""
         return cls.create_proof_with_reduction(circuit, pk, 0, 0)
 
+    @staticmethod
+    def prepare_verifying_key(vk_bytes) -> bytes:
+        """verifier.rs:13-20 on the host: serialized VerifyingKey -> serialized PreparedVerifyingKey"""
+        b = _u8(vk_bytes)
+        n = C.c_uint64()
+        _check(lib().cg_prepare_verifying_key(_ptr(b) if b.size else None, b.size, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), np.uint8)
+        _check(lib().cg_prepare_verifying_key(_ptr(b) if b.size else None, b.size, _ptr(out), out.size, C.byref(n)))
+        return out.tobytes()
+
+    @staticmethod
+    def verify_batch(pvk: "PreparedVerifyingKey", inputs, proofs) -> np.ndarray:
+        """verifier.rs:25-65 for n proofs under one key on the GPU.  inputs: n x num_inputs canonical Fr (one flat byte
+        array, or one sequence of ints per proof); proofs: n x 256 B (one flat array, or a list of bytes / Proof).
+        Returns n verdict bytes (CG_VERIFY_REJECT / ACCEPT / MALFORMED)."""
+        if isinstance(proofs, (list, tuple)):
+            proofs = b"".join(p.data if isinstance(p, Proof) else bytes(p) for p in proofs)
+        pb = _u8(proofs)
+        if pb.size % 256:
+            raise ValueError("proofs must be n x 256 bytes")
+        n = pb.size // 256
+        if isinstance(inputs, (list, tuple)):
+            ib = np.concatenate([_inputs_array(x) for x in inputs]) if inputs else np.zeros(0, np.uint8)
+        else:
+            ib = _u8(inputs)
+        if n and ib.size % (32 * n):
+            raise ValueError("inputs must be n x num_inputs x 32 bytes")
+        n_inputs = ib.size // (32 * n) if n else pvk.num_inputs
+        out = np.zeros(max(n, 1), np.uint8)
+        _check(lib().cg_verify_batch(pvk._h, _ptr(ib) if ib.size else None, n_inputs, _ptr(pb) if pb.size else None, n, _ptr(out)))
+        return out[:n]
+
+    @classmethod
+    def verify_with_processed_vk(cls, pvk: "PreparedVerifyingKey", public_inputs, proof) -> bool:
+        """`Groth16::verify_with_processed_vk` (verifier.rs:25-65, called at creds/src/lib.rs:288-289).  A proof or an
+        input that fails checked deserialisation is rejected (False)."""
+        data = proof.data if isinstance(proof, Proof) else bytes(proof)
+        return int(cls.verify_batch(pvk, [_inputs_array(public_inputs)], data)[0]) == CG_VERIFY_ACCEPT
+
     @classmethod
     def clear_cache(cls):
         cls._cache.clear()
+
+
+class PreparedVerifyingKey:
+    """forks/groth16/src/data_structures.rs:62-71, parsed from its serialized bytes (`deserialize_uncompressed_unchecked`,
+    creds/src/utils.rs:186) and resident on a GPU (cg_pvk_load): alpha_g1_beta_g2, the prepared gamma / delta lines and
+    fixed-base tables of gamma_abc_g1.  Use as a context manager or close()."""
+
+    def __init__(self, pvk_bytes, device: int = -1):
+        b = _u8(pvk_bytes)
+        self._h = C.c_void_p()
+        _check(lib().cg_pvk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, device))
+
+    @property
+    def num_inputs(self) -> int:
+        """gamma_abc_g1.len() - 1"""
+        n = C.c_uint64()
+        _check(lib().cg_pvk_num_inputs(self._h, C.byref(n)))
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().cg_pvk_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _inputs_array(inputs) -> np.ndarray:
+    """public inputs of one proof: canonical 32-byte scalars (bytes / uint8 array) or ints"""
+    if isinstance(inputs, (np.ndarray, bytes, bytearray, memoryview)):
+        return _u8(inputs)
+    return scalars_to_array(list(inputs)) if len(inputs) else np.zeros(0, np.uint8)
 
 
 class CircomCircuit:
@@ -1337,12 +1424,17 @@ class IOLocations:
         return list(self.public_io_locations.keys())
 
 
+class ProofRejected(CrescentGpuError):
+    """create_client_state(verify=True): the fresh proof does not verify (the reference's `assert!`, creds/src/lib.rs:290)"""
+
+
 def create_client_state(r1cs_bytes, prover_params_bytes, witness, rng, prover_aux: Optional[str] = None,
-                        credtype: str = "jwt", prover: Optional["Prover"] = None) -> "ClientState":
+                        credtype: str = "jwt", prover: Optional["Prover"] = None, verify: bool = False) -> "ClientState":
     """creds/src/lib.rs:255-301 without the witness generator: parse main_c.r1cs and prover_params.bin, prove with
     (r, s) drawn from `rng`, and assemble the ClientState the `show` step starts from.  `witness` is the full wire
-    assignment the WASM calculator would have produced (wire 0 = 1).  The reference also verifies the proof against
-    groth16_pvk.bin before returning (:286-290); that check is the caller's (the tests do it with the oracle)."""
+    assignment the WASM calculator would have produced (wire 0 = 1).  With verify=True the proof is checked against the
+    groth16_pvk of prover_params.bin on the GPU before the state is built, as the reference does (:286-290), and a
+    rejected proof raises ProofRejected."""
     r1cs = R1CSFile(r1cs_bytes)
     pp = ProverParams.from_bytes(prover_params_bytes)
     circuit = CircomCircuit(r1cs, witness)
@@ -1350,6 +1442,10 @@ def create_client_state(r1cs_bytes, prover_params_bytes, witness, rng, prover_au
         proof = prover.prove(circuit.full_assignment(), rng.randrange(FR_MODULUS), rng.randrange(FR_MODULUS))
     else:
         proof = Groth16.prove(pp.groth16_params, circuit, rng)
+    if verify:
+        with PreparedVerifyingKey(pp.groth16_pvk) as pvk:
+            if not Groth16.verify_with_processed_vk(pvk, circuit.get_public_inputs(), proof):
+                raise ProofRejected(CG_VERIFY_REJECT, "the proof does not verify against the prepared verifying key")
     cs = ClientState.new(circuit.get_public_inputs(), prover_aux, proof, pp.vk_bytes, pp.groth16_pvk, pp.config_str)
     cs.credtype = credtype
     return cs

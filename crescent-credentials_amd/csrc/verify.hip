@@ -1,0 +1,458 @@
+// Groth16 verification on the GPU: `Groth16::verify_with_processed_vk` (forks/groth16/src/verifier.rs:25-65) for a batch
+// of proofs under one PreparedVerifyingKey, and `prepare_verifying_key` (verifier.rs:13-20) on the host, both over
+// pairing.hpp.  What the reference's caller runs after every prove (creds/src/lib.rs:286-290).
+//
+// A cg_pvk holds one parsed key on a device: alpha_g1_beta_g2, the 91 line coefficients of gamma_g2_neg_pc and of
+// delta_g2_neg_pc, gamma_abc_g1[0] and, for every other gamma_abc_g1 entry, a fixed-base table of 32 windows x 256
+// multiples (8-bit windows: x_i·G_i is 32 mixed additions).  cg_verify_batch runs four kernels per chunk of proofs on the
+// handle's own non-blocking stream:
+//   k_vfy_inputs  one lane per (proof, input): x_i·gamma_abc[i+1] from the table                      -> XYZZ partials
+//   k_vfy_check   one lane per proof: ark's checked deserialisation of A, B, C (coordinates < q, flags, curve, [r]B = O)
+//                 and of the inputs (< r); gamma_abc[0] + Σ partials -> prepared inputs (affine)
+//   k_vfy_miller  one lane per proof: the multi-Miller loop over (A, B on the fly), (prepared inputs, gamma), (C, delta)
+//   k_vfy_final   one lane per proof: final exponentiation, == alpha_g1_beta_g2 -> one verdict byte
+#include <memory>
+
+#include "common.hpp"
+#include "pairing.hpp"
+
+namespace cg {
+int translate_current_exception();
+}
+using namespace cg;
+
+namespace {
+
+constexpr int VWIN_BITS = 8;
+constexpr int VWIN = 1 << VWIN_BITS;       // entries per window (entry 0 = O)
+constexpr int NWIN = 256 / VWIN_BITS;      // windows per 256-bit scalar
+constexpr uint64_t VCHUNK = 1u << 15;      // proofs per launch set
+constexpr int VBLOCK = 64;
+constexpr int NC = PairingConsts::N_COEFFS;
+
+// one proof after k_vfy_check, Montgomery affine (identity = zeros)
+struct alignas(16) ParsedProof {
+    G1Affine a;
+    G2Affine b;
+    G1Affine c;
+    G1Affine pi;     // prepared inputs
+};
+enum : uint8_t { ST_OK = 0, ST_MALFORMED = 2 };
+
+// ---- strict ark-serialize reader (deserialize_uncompressed_unchecked): canonical coordinates, valid flags --------------
+struct KeyRd {
+    const uint8_t* p;
+    uint64_t len, off;
+    void need(uint64_t n) const {
+        if (off + n > len || off + n < off) throw HipError(CG_ERR_PARSE, "unexpected end of serialized key");
+    }
+    uint64_t u64() {
+        need(8);
+        uint64_t v;
+        memcpy(&v, p + off, 8);
+        off += 8;
+        return v;
+    }
+    // one field element; `flag_bits` = 0xC0 strips the SWFlags of the coordinate that carries them
+    Fq fq(uint8_t flag_bits = 0) {
+        need(32);
+        uint8_t b[32];
+        memcpy(b, p + off, 32);
+        b[31] &= (uint8_t)~flag_bits;
+        off += 32;
+        Fq a = fp_from_bytes<Fq>(b);
+        if (!fp_is_canonical(a)) throw HipError(CG_ERR_PARSE, "field element not below the base field modulus");
+        return to_mont(a);
+    }
+    Fq2 fq2(uint8_t flag_bits = 0) {
+        Fq c0 = fq();
+        Fq c1 = fq(flag_bits);
+        return {c0, c1};
+    }
+    bool flags_infinity(uint64_t last_byte_at) const {
+        const uint8_t f = p[last_byte_at] & 0xC0;
+        if (f == 0xC0) throw HipError(CG_ERR_PARSE, "invalid point flags");
+        return f == 0x40;
+    }
+    G1Affine g1() {
+        need(64);
+        const bool inf = flags_infinity(off + 63);
+        G1Affine r;
+        r.x = fq();
+        r.y = fq(0xC0);
+        return inf ? G1Affine::inf() : r;
+    }
+    G2Affine g2() {
+        need(128);
+        const bool inf = flags_infinity(off + 127);
+        G2Affine r;
+        r.x = fq2();
+        r.y = fq2(0xC0);
+        return inf ? G2Affine::inf() : r;
+    }
+    uint64_t count(uint64_t item_bytes) {
+        uint64_t n = u64();
+        if (n > (len - off) / item_bytes) throw HipError(CG_ERR_PARSE, "vector length exceeds the remaining data");
+        return n;
+    }
+};
+
+struct HostVk {
+    G1Affine alpha_g1, delta_g1;
+    G2Affine beta_g2, gamma_g2, delta_g2;
+    std::vector<G1Affine> gamma_abc;
+};
+static void read_vk(KeyRd& r, HostVk& vk) {       // data_structures.rs:31-44 (the fork's delta_g1 included)
+    vk.alpha_g1 = r.g1();
+    vk.beta_g2 = r.g2();
+    vk.gamma_g2 = r.g2();
+    vk.delta_g1 = r.g1();
+    vk.delta_g2 = r.g2();
+    const uint64_t n = r.count(64);
+    vk.gamma_abc.resize(n);
+    for (uint64_t i = 0; i < n; ++i) vk.gamma_abc[i] = r.g1();
+}
+// ark-ec bn::G2Prepared: ell_coeffs: Vec<(Fq2, Fq2, Fq2)>, infinity: bool
+static bool read_g2_prepared(KeyRd& r, std::vector<EllCoeff>& c) {
+    const uint64_t n = r.count(192);
+    c.resize(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        c[i].c0 = r.fq2();
+        c[i].c1 = r.fq2();
+        c[i].c2 = r.fq2();
+    }
+    r.need(1);
+    const uint8_t inf = r.p[r.off++];
+    if (inf > 1) throw HipError(CG_ERR_PARSE, "invalid bool in G2Prepared");
+    if (!inf && n != (uint64_t)NC) throw HipError(CG_ERR_PARSE, "G2Prepared does not hold 91 line coefficients");
+    return inf == 0;      // live
+}
+
+struct HostPvk {
+    HostVk vk;
+    Fq12 alpha_beta;
+    std::vector<EllCoeff> gamma_c, delta_c;
+    bool gamma_live = false, delta_live = false;
+};
+static void parse_pvk(const uint8_t* data, uint64_t len, HostPvk& k) {   // data_structures.rs:62-71
+    KeyRd r{data, len, 0};
+    read_vk(r, k.vk);
+    Fq2* c[6] = {&k.alpha_beta.c0.c0, &k.alpha_beta.c0.c1, &k.alpha_beta.c0.c2,
+                 &k.alpha_beta.c1.c0, &k.alpha_beta.c1.c1, &k.alpha_beta.c1.c2};
+    for (int i = 0; i < 6; ++i) *c[i] = r.fq2();
+    k.gamma_live = read_g2_prepared(r, k.gamma_c);
+    k.delta_live = read_g2_prepared(r, k.delta_c);
+    if (r.off != len) throw HipError(CG_ERR_PARSE, "trailing bytes after PreparedVerifyingKey");
+}
+
+// fixed-base tables of gamma_abc[1..]: tab[(i·NWIN + w)·VWIN + d] = d·2^(8w)·gamma_abc[i+1], affine (one batch inversion)
+static void build_tables(const std::vector<G1Affine>& gabc, std::vector<G1Affine>& tab) {
+    const uint64_t ell = gabc.size() - 1;
+    const uint64_t total = ell * NWIN * VWIN;
+    std::vector<G1XYZZ> pts(total);
+    for (uint64_t i = 0; i < ell; ++i) {
+        G1XYZZ step = G1XYZZ::from_affine(gabc[i + 1]);
+        for (int w = 0; w < NWIN; ++w) {
+            G1XYZZ* row = &pts[(i * NWIN + w) * VWIN];
+            row[0] = G1XYZZ::inf();
+            for (int d = 1; d < VWIN; ++d) {
+                row[d] = row[d - 1];
+                add(row[d], step);
+            }
+            G1XYZZ next = row[VWIN - 1];
+            add(next, step);
+            step = next;
+        }
+    }
+    // batch affine: t_j = zz_j·zzz_j, one inversion of their product
+    std::vector<Fq> pref(total);
+    Fq acc = Fq::one();
+    for (uint64_t j = 0; j < total; ++j) {
+        pref[j] = acc;
+        if (!pts[j].is_inf()) acc = mul(acc, mul(pts[j].zz, pts[j].zzz));
+    }
+    Fq ia = inv(acc);
+    tab.resize(total);
+    for (uint64_t j = total; j-- > 0;) {
+        if (pts[j].is_inf()) { tab[j] = G1Affine::inf(); continue; }
+        const Fq t = mul(pts[j].zz, pts[j].zzz);
+        const Fq it = mul(ia, pref[j]);          // 1 / t_j
+        ia = mul(ia, t);
+        tab[j] = {mul(pts[j].x, mul(it, pts[j].zzz)), mul(pts[j].y, mul(it, pts[j].zz))};
+    }
+}
+
+// ---- device side ----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool limbs_below(const uint32_t a[8], const uint32_t n[8]) {
+    for (int i = 7; i >= 0; --i) {
+        if (a[i] < n[i]) return true;
+        if (a[i] > n[i]) return false;
+    }
+    return false;
+}
+// one coordinate from 8 words; strip = the SWFlags bits of the word that carries them
+__device__ __forceinline__ Fq dev_fq(const uint32_t* w, bool& ok, uint32_t strip = 0) {
+    uint32_t l[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) l[i] = w[i];
+    l[7] &= ~strip;
+    ok = ok && limbs_below(l, FqP::N);
+    Fq a;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a.l[i] = l[i];
+    return to_mont(a);
+}
+// checked deserialisation of one uncompressed G1 point (16 words): flags valid, coordinates < q, on the curve unless O
+__device__ __forceinline__ G1Affine dev_g1(const uint32_t* w, bool& ok) {
+    const uint32_t f = w[15] >> 30;
+    ok = ok && f != 3u;
+    G1Affine p;
+    p.x = dev_fq(w, ok);
+    p.y = dev_fq(w + 8, ok, 0xC0000000u);
+    if (f == 1u) return G1Affine::inf();
+    ok = ok && g1_on_curve(p);
+    return p;
+}
+__device__ __forceinline__ G2Affine dev_g2(const uint32_t* w, bool& ok) {
+    const uint32_t f = w[31] >> 30;
+    ok = ok && f != 3u;
+    G2Affine p;
+    p.x.c0 = dev_fq(w, ok);
+    p.x.c1 = dev_fq(w + 8, ok);
+    p.y.c0 = dev_fq(w + 16, ok);
+    p.y.c1 = dev_fq(w + 24, ok, 0xC0000000u);
+    if (f == 1u) return G2Affine::inf();
+    ok = ok && g2_on_twist(p);
+    if (ok) ok = g2_in_subgroup(p);
+    return p;
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_vfy_inputs(const uint32_t* __restrict__ inputs, uint64_t n, uint32_t ell,
+                                                      const G1Affine* __restrict__ tab, G1XYZZ* __restrict__ part) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * ell) return;
+    const uint32_t i = (uint32_t)(t % ell);
+    const uint32_t* x = inputs + 8 * t;
+    const G1Affine* tb = tab + (uint64_t)i * NWIN * VWIN;
+    G1XYZZ acc = G1XYZZ::inf();
+    for (int w = 0; w < NWIN; ++w) {
+        const uint32_t d = (x[w >> 2] >> (8 * (w & 3))) & 0xFFu;
+        if (d) madd(acc, tb[w * VWIN + d]);
+    }
+    part[t] = acc;
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_vfy_check(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ inputs,
+                                                     uint64_t n, uint32_t ell, const G1XYZZ* __restrict__ part, G1Affine g0,
+                                                     ParsedProof* __restrict__ out, uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t* w = proofs + 64 * p;
+    bool ok = true;
+    ParsedProof pp;
+    pp.a = dev_g1(w, ok);
+    pp.b = dev_g2(w + 16, ok);
+    pp.c = dev_g1(w + 48, ok);
+    G1XYZZ acc = G1XYZZ::from_affine(g0);
+    for (uint32_t i = 0; i < ell; ++i) {
+        ok = ok && limbs_below(inputs + 8 * (p * ell + i), FrP::N);
+        add(acc, part[p * ell + i]);
+    }
+    pp.pi = to_affine(acc);
+    out[p] = pp;
+    status[p] = ok ? ST_OK : ST_MALFORMED;
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_vfy_miller(const ParsedProof* __restrict__ in, const uint8_t* __restrict__ status,
+                                                      uint64_t n, const EllCoeff* gamma_c, const EllCoeff* delta_c,
+                                                      int gamma_live, int delta_live, Fq12* __restrict__ f) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || status[p] != ST_OK) return;
+    const ParsedProof pp = in[p];
+    MillerPairs mp;
+    mp.p[0] = pp.a; mp.q[0] = pp.b; mp.tab[0] = nullptr; mp.live[0] = !pp.a.is_inf() && !pp.b.is_inf();
+    mp.p[1] = pp.pi; mp.q[1] = G2Affine::inf(); mp.tab[1] = gamma_c; mp.live[1] = !pp.pi.is_inf() && gamma_live;
+    mp.p[2] = pp.c; mp.q[2] = G2Affine::inf(); mp.tab[2] = delta_c; mp.live[2] = !pp.c.is_inf() && delta_live;
+    f[p] = multi_miller_loop<1>(mp);
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_vfy_final(const Fq12* __restrict__ f, const uint8_t* __restrict__ status, uint64_t n,
+                                                     Fq12 alpha_beta, uint8_t* __restrict__ verdict) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (status[p] != ST_OK) {
+        verdict[p] = CG_VERIFY_MALFORMED;
+        return;
+    }
+    Fq12 r;
+    const bool some = final_exponentiation(f[p], r);
+    verdict[p] = some && r == alpha_beta ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
+}
+
+}  // namespace
+
+struct cg_pvk {
+    int device = 0;
+    uint64_t n_inputs = 0;
+    hipStream_t st = nullptr;
+    std::mutex mu;
+    G1Affine g0;
+    Fq12 alpha_beta;
+    int gamma_live = 0, delta_live = 0;
+    DevBuf<G1Affine> tab;
+    DevBuf<EllCoeff> gamma_c, delta_c;
+    // per-call buffers, grown to the largest chunk seen
+    uint64_t cap = 0;
+    DevBuf<uint8_t> d_inputs, d_proofs, d_status, d_verdict;
+    DevBuf<G1XYZZ> d_part;
+    DevBuf<ParsedProof> d_parsed;
+    DevBuf<Fq12> d_f;
+    ~cg_pvk() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+};
+
+extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len, int32_t device) {
+    if (!out || !pvk_bytes) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    try {
+        HostPvk hk;
+        parse_pvk(pvk_bytes, len, hk);           // host only: a parse error is reported before any HIP call
+        if (hk.vk.gamma_abc.empty()) return fail(CG_ERR_MALFORMED_KEY, "gamma_abc_g1 is empty");
+        std::vector<G1Affine> tab;
+        build_tables(hk.vk.gamma_abc, tab);
+        int dev = device;
+        if (dev < 0) CG_HIP(hipGetDevice(&dev));
+        CG_HIP(hipSetDevice(dev));
+        std::unique_ptr<cg_pvk> k(new cg_pvk());
+        k->device = dev;
+        k->n_inputs = hk.vk.gamma_abc.size() - 1;
+        k->g0 = hk.vk.gamma_abc[0];
+        k->alpha_beta = hk.alpha_beta;
+        k->gamma_live = hk.gamma_live;
+        k->delta_live = hk.delta_live;
+        CG_HIP(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
+        k->tab.alloc(tab.size() ? tab.size() : 1);
+        h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
+        k->gamma_c.alloc(NC);
+        k->delta_c.alloc(NC);
+        if (hk.gamma_live) h2d_sync(k->gamma_c.p, hk.gamma_c.data(), NC * sizeof(EllCoeff), k->st);
+        if (hk.delta_live) h2d_sync(k->delta_c.p, hk.delta_c.data(), NC * sizeof(EllCoeff), k->st);
+        *out = k.release();
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+extern "C" int cg_pvk_num_inputs(const cg_pvk* k, uint64_t* n) {
+    if (!k || !n) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    *n = k->n_inputs;
+    return CG_OK;
+}
+
+extern "C" int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inputs, const uint8_t* proofs, uint64_t n,
+                               uint8_t* verdicts) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_inputs != k->n_inputs)                           // SynthesisError::MalformedVerifyingKey (verifier.rs:30-32)
+        return fail(CG_ERR_MALFORMED_KEY, "%llu public inputs for a key with gamma_abc_g1.len() = %llu",
+                    (unsigned long long)n_inputs, (unsigned long long)(k->n_inputs + 1));
+    if (n == 0) return CG_OK;
+    if (!proofs || !verdicts || (n_inputs && !inputs)) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t ell = n_inputs;
+        const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
+        if (chunk > k->cap) {
+            k->d_inputs.alloc(chunk * ell * 32 + 32);
+            k->d_proofs.alloc(chunk * 256);
+            k->d_status.alloc(chunk);
+            k->d_verdict.alloc(chunk);
+            k->d_part.alloc(chunk * ell + 1);
+            k->d_parsed.alloc(chunk);
+            k->d_f.alloc(chunk);
+            k->cap = chunk;
+        }
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            if (ell) CG_HIP(hipMemcpyAsync(k->d_inputs.p, inputs + off * ell * 32, m * ell * 32, hipMemcpyHostToDevice, k->st));
+            CG_HIP(hipMemcpyAsync(k->d_proofs.p, proofs + off * 256, m * 256, hipMemcpyHostToDevice, k->st));
+            if (ell) {
+                k_vfy_inputs<<<ceil_div(m * ell, VBLOCK), VBLOCK, 0, k->st>>>((const uint32_t*)k->d_inputs.p, m, (uint32_t)ell,
+                                                                             k->tab.p, k->d_part.p);
+                CG_KERNEL_CHECK();
+            }
+            const uint32_t grid = ceil_div(m, VBLOCK);
+            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->d_proofs.p, (const uint32_t*)k->d_inputs.p, m, (uint32_t)ell,
+                                                    k->d_part.p, k->g0, k->d_parsed.p, k->d_status.p);
+            CG_KERNEL_CHECK();
+            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->d_parsed.p, k->d_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
+                                                     k->delta_live, k->d_f.p);
+            CG_KERNEL_CHECK();
+            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->d_f.p, k->d_status.p, m, k->alpha_beta, k->d_verdict.p);
+            CG_KERNEL_CHECK();
+            CG_HIP(hipMemcpyAsync(verdicts + off, k->d_verdict.p, m, hipMemcpyDeviceToHost, k->st));
+            CG_HIP(hipStreamSynchronize(k->st));
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+extern "C" void cg_pvk_free(cg_pvk* k) {
+    if (!k) return;
+    (void)hipSetDevice(k->device);
+    delete k;                    // the destructor waits for the handle's stream
+}
+
+// prepare_verifying_key (verifier.rs:13-20) on the host: one pairing and two G2Prepared, written as ark-serialize writes a
+// PreparedVerifyingKey (data_structures.rs:62-71): the VerifyingKey bytes as given, alpha_g1_beta_g2, gamma_g2_neg_pc,
+// delta_g2_neg_pc.  pvk_out = NULL asks for the size only.
+static void put_fq(std::vector<uint8_t>& o, const Fq& a) {
+    uint8_t b[32];
+    fp_to_bytes(from_mont(a), b);
+    o.insert(o.end(), b, b + 32);
+}
+static void put_fq2(std::vector<uint8_t>& o, const Fq2& a) { put_fq(o, a.c0); put_fq(o, a.c1); }
+static void put_g2_prepared(std::vector<uint8_t>& o, const G2Affine& q) {
+    uint64_t n = q.is_inf() ? 0 : NC;
+    const uint8_t* pn = (const uint8_t*)&n;
+    o.insert(o.end(), pn, pn + 8);
+    if (n) {
+        std::vector<EllCoeff> c(NC);
+        g2_prepare(q, c.data());
+        for (const EllCoeff& e : c) { put_fq2(o, e.c0); put_fq2(o, e.c1); put_fq2(o, e.c2); }
+    }
+    o.push_back(q.is_inf() ? 1 : 0);
+}
+
+extern "C" int cg_prepare_verifying_key(const uint8_t* vk_bytes, uint64_t vk_len, uint8_t* pvk_out, uint64_t cap, uint64_t* len) {
+    if (!vk_bytes || !len) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    try {
+        HostVk vk;
+        KeyRd r{vk_bytes, vk_len, 0};
+        read_vk(r, vk);
+        if (r.off != vk_len) throw HipError(CG_ERR_PARSE, "trailing bytes after VerifyingKey");
+        const uint64_t need = vk_len + 384 + 2 * 9 + (vk.gamma_g2.is_inf() ? 0 : NC * 192) + (vk.delta_g2.is_inf() ? 0 : NC * 192);
+        *len = need;
+        if (!pvk_out) return CG_OK;
+        if (cap < need) return fail(CG_ERR_INVALID_ARGUMENT, "output buffer too small (%llu bytes needed)", (unsigned long long)need);
+        // alpha_g1_beta_g2 = E::pairing(alpha_g1, beta_g2)
+        MillerPairs mp;
+        mp.p[0] = vk.alpha_g1; mp.q[0] = vk.beta_g2; mp.tab[0] = nullptr;
+        mp.live[0] = !vk.alpha_g1.is_inf() && !vk.beta_g2.is_inf();
+        for (int j = 1; j < 3; ++j) { mp.p[j] = G1Affine::inf(); mp.q[j] = G2Affine::inf(); mp.tab[j] = nullptr; mp.live[j] = false; }
+        Fq12 ab;
+        if (!final_exponentiation(multi_miller_loop<1>(mp), ab)) throw HipError(CG_ERR_MALFORMED_KEY, "degenerate pairing");
+        std::vector<uint8_t> o(vk_bytes, vk_bytes + vk_len);
+        const Fq2* c[6] = {&ab.c0.c0, &ab.c0.c1, &ab.c0.c2, &ab.c1.c0, &ab.c1.c1, &ab.c1.c2};
+        for (int i = 0; i < 6; ++i) put_fq2(o, *c[i]);
+        put_g2_prepared(o, neg(vk.gamma_g2));
+        put_g2_prepared(o, neg(vk.delta_g2));
+        if (o.size() != need) throw HipError(CG_ERR_HIP, "internal size mismatch");
+        memcpy(pvk_out, o.data(), need);
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}

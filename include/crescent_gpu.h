@@ -534,6 +534,31 @@ int cg_client_state_parse(const uint8_t* data, uint64_t len, cg_client_state** o
 int cg_client_state_get(const cg_client_state* cs, cg_client_state_view* view);
 void cg_client_state_free(cg_client_state* cs);
 
+/* Groth16 verification (SURVEY 8f-2's last step: what create_client_state runs after the prove, creds/src/lib.rs:286-290).
+ * Verdicts: one byte per proof.  CG_VERIFY_MALFORMED = the proof or its public inputs fail ark's CHECKED
+ * deserialisation (a coordinate >= q, a bad flag combination, A or C off the curve, B off the twist or outside the
+ * r-torsion, an input >= r) - for that proof only; a proof from cg_prove always passes these checks. */
+enum { CG_VERIFY_REJECT = 0, CG_VERIFY_ACCEPT = 1, CG_VERIFY_MALFORMED = 2 };
+typedef struct cg_pvk cg_pvk;
+/* Replaces: `PreparedVerifyingKey::deserialize_uncompressed_unchecked` (creds/src/utils.rs:186) + the upload to a device
+ *           (device -1 = current).  Bytes that are not exactly one PreparedVerifyingKey (data_structures.rs:62-71) are
+ *           CG_ERR_PARSE, reported before any HIP call; an empty gamma_abc_g1 is CG_ERR_MALFORMED_KEY. */
+int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len, int32_t device);
+/* gamma_abc_g1.len() - 1: the public inputs a proof under this key carries */
+int cg_pvk_num_inputs(const cg_pvk* k, uint64_t* n);
+/* Replaces: `Groth16::verify_with_processed_vk` for n proofs under one key (forks/groth16/src/verifier.rs:25-65).
+ * inputs: n x n_inputs x 32 B canonical Fr; proofs: n x 256 B (cg_prove's layout, ark-serialize uncompressed a ‖ b ‖ c);
+ * verdicts: n bytes, CG_VERIFY_*.  n_inputs + 1 != gamma_abc_g1.len() is CG_ERR_MALFORMED_KEY
+ * (SynthesisError::MalformedVerifyingKey).  Any n; calls on one handle serialise, different handles are independent. */
+int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inputs, const uint8_t* proofs, uint64_t n,
+                    uint8_t* verdicts);
+void cg_pvk_free(cg_pvk* k);
+/* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
+ * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the
+ * PreparedVerifyingKey bytes (*len of them; pvk_out = NULL only reports *len).  A buffer shorter than *len is
+ * CG_ERR_INVALID_ARGUMENT. */
+int cg_prepare_verifying_key(const uint8_t* vk_bytes, uint64_t vk_len, uint8_t* pvk_out, uint64_t cap, uint64_t* len);
+
 /* Diagnostic: the shader clock (GHz) the GPU holds over the next `window_us` microseconds, measured on the device by
  * one wave that compares the shader-cycle counter with the constant-rate counter - callable from a second thread while
  * proofs run, which is how bench.py reports the clock its peaks should be scaled by.  device -1 = current.

@@ -3,7 +3,7 @@
  * libcrescent_gpu's C ABI: no Python, no torch, nothing but <include/crescent_gpu.h>.
  *
  *   crescent_prove <main_c.r1cs> <prover_params.bin> <witness.bin> <client_state.bin>
- *                  [--rs r_hex s_hex] [--credtype jwt|mdl] [--aux prover_aux_json] [--sync-load] [--timings-json]
+ *                  [--rs r_hex s_hex] [--credtype jwt|mdl] [--aux prover_aux_json] [--sync-load] [--timings-json] [--verify]
  *
  *   main_c.r1cs       the circuit, iden3 binary format     (lib.rs:257-258; r1cs_reader.rs:54-148)
  *   prover_params.bin ProverParams{groth16_params, groth16_pvk, config_str}, ark-serialize uncompressed (lib.rs:268)
@@ -20,6 +20,10 @@
  *   --timings-json    one JSON line on stdout with the phases of this run, named after the reference's timers
  *                     ("Reading R1CS" lib.rs:257, "Reading ProverParams" :266, "Groth16 prove" :281); with a staged load it then
  *                     waits for the final arrangement and adds the background part and a second proof's time
+ *   --verify          verify the proof against the file's groth16_pvk before the ClientState is written, as the reference
+ *                     does (lib.rs:286-290: Groth16::verify_with_processed_vk, then assert!): a rejected proof ends the
+ *                     program with status 1 and no client_state.bin.  Under --timings-json the line then carries
+ *                     verify_ms (key load + verification)
  *
  * The two files are mapped, not read (the parsers take them straight from the page cache), and parsed on two threads while
  * this one starts the GPU runtime: the three are independent, and each is a few hundred milliseconds at the rs256 size.
@@ -161,7 +165,7 @@ int main(int argc, char** argv) {
     const char* credtype = "jwt";
     const char* aux = NULL;
     uint8_t r[32], s[32];
-    int have_rs = 0, bad = argc < 5, sync_load = 0, timings_json = 0;
+    int have_rs = 0, bad = argc < 5, sync_load = 0, timings_json = 0, verify = 0;
     for (int i = 5; i < argc && !bad; ++i) {
         if (!strcmp(argv[i], "--rs") && i + 2 < argc) {
             if (!hex_scalar(argv[i + 1], r) || !hex_scalar(argv[i + 2], s)) { fprintf(stderr, "--rs: need hex values below the scalar modulus\n"); return 2; }
@@ -170,11 +174,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--aux") && i + 1 < argc) aux = argv[++i];
         else if (!strcmp(argv[i], "--sync-load")) sync_load = 1;
         else if (!strcmp(argv[i], "--timings-json")) timings_json = 1;
+        else if (!strcmp(argv[i], "--verify")) verify = 1;
         else bad = 1;
     }
     if (bad) {
         fprintf(stderr, "usage: %s main_c.r1cs prover_params.bin witness.bin client_state.bin [--rs r_hex s_hex] [--credtype jwt|mdl] [--aux json] "
-                        "[--sync-load] [--timings-json]\n", argv[0]);
+                        "[--sync-load] [--timings-json] [--verify]\n", argv[0]);
         return 2;
     }
     if (!have_rs && (!random_scalar(r) || !random_scalar(s))) {
@@ -247,6 +252,25 @@ int main(int argc, char** argv) {
             (unsigned long long)hdr.n_constraints, (unsigned long long)hdr.num_variables, (unsigned long long)hdr.num_inputs, t1 - t0,
             t2 - t1, tm.witness_map_ms, tm.msm_h_ms, tm.msm_l_ms, tm.msm_a_ms, tm.msm_b1_ms, tm.msm_b2_ms);
 
+    /* lib.rs:286-290: let pvk = ...groth16_pvk; verify_with_processed_vk(&pvk, &inputs, &proof); assert!(verified) */
+    char verify_json[64] = "";
+    if (verify) {
+        const double tv = now_ms();
+        cg_pvk* pvk = NULL;
+        if (cg_pvk_load(&pvk, ppv.pvk_bytes, ppv.pvk_len, -1) != CG_OK) return die("cg_pvk_load");
+        uint8_t verdict = CG_VERIFY_REJECT;
+        const int vrc = cg_verify_batch(pvk, witness + 32, hdr.num_inputs - 1, proof, 1, &verdict);
+        cg_pvk_free(pvk);
+        if (vrc != CG_OK) return die("cg_verify_batch");
+        const double verify_ms = now_ms() - tv;
+        if (verdict != CG_VERIFY_ACCEPT) {
+            fprintf(stderr, "crescent_prove: the proof does not verify against groth16_pvk (verdict %d); no client state written\n", (int)verdict);
+            return 1;
+        }
+        fprintf(stderr, "verified against groth16_pvk in %.2f ms\n", verify_ms);
+        snprintf(verify_json, sizeof verify_json, ", \"verify_ms\": %.3f", verify_ms);
+    }
+
     /* ClientState::new (lib.rs:292-299): inputs = the public wires after the constant one */
     cg_client_state_view cs;
     memset(&cs, 0, sizeof cs);
@@ -286,12 +310,12 @@ int main(int argc, char** argv) {
                "\"slots\": %.1f}, \"staged\": %d, \"first_proof_ms\": %.3f, \"first_proof_upload_ms\": %.3f, \"client_state_write_s\": %.4f, "
                "\"total_s\": %.4f, \"background\": {\"ready_rc\": %d, \"ready_after_load_call_ms\": %.1f, \"h_query_fold_ms\": %.1f, "
                "\"window_tables_ms\": %.1f, \"final_slots_ms\": %.1f, \"swap_wait_ms\": %.2f, \"windows_from_first_proof\": %d}, "
-               "\"second_proof_ms\": %.3f, \"second_proof_bytes_identical\": %s}\n",
+               "\"second_proof_ms\": %.3f, \"second_proof_bytes_identical\": %s%s}\n",
                (unsigned long long)jr.len, (unsigned long long)jp.len, jr.read_s, jr.parse_s, jp.read_s, jp.parse_s, gpu_init_s,
                (t_parsed - t_start) / 1e3, (t1 - t0) / 1e3, lt.matrices_ms, lt.domain_ms, lt.key_copy_ms, lt.staged ? 0.0 : lt.fold_ms,
                lt.staged ? 0.0 : lt.window_tables_ms, lt.slots_ms, (int)lt.staged, t2 - t1, tm.upload_ms, (t_done - t2) / 1e3, (t_done - t_start) / 1e3,
                ready_rc, lt2.ready_after_ms, lt.staged ? lt2.fold_ms : 0.0, lt.staged ? lt2.window_tables_ms : 0.0, lt2.final_slots_ms,
-               lt2.swap_wait_ms, (int)lt2.windows_from_proof, second_ms, second_ms >= 0 ? "true" : "null");
+               lt2.swap_wait_ms, (int)lt2.windows_from_proof, second_ms, second_ms >= 0 ? "true" : "null", verify_json);
         fflush(stdout);
     }
 
