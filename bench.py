@@ -31,15 +31,22 @@ synchronise, K proofs, synchronise + barrier; max over ranks) is measured in the
 from a seed made of k and the rank, so the same arguments give the same inputs step for step in every run;
 --dump-outputs DIR writes the proof of the last timed step as DIR/proof_{a,b,c}.npy.
 
+Plain run and --full.  A plain run does what the headline needs and nothing more: it makes the workload and loads the key,
+primes the proof slots, warms up, times the K steps, writes --dump-outputs and prints the line (metric, value, ms_per_step,
+the block statistics and latencies of the same window, the configuration, and the G1 pair counts of one proof).  Every
+other measurement and check - the bracketed region, the phase times and rooflines, the witness's other origins, the
+in-flight curve, the cold start, the sharded proofs, the checker, the CPU baseline, the second shape and the bit-fraction
+sweep - runs only with --full, as described below; the --no-* switches and --headline-only select among them there.
+
 Multi-GPU: `value` is always the replica throughput — proofs are independent objects, each rank proves its
 own stream with a full copy of the key, no data-path collective (config 5); `value_per_rank` lists every rank's own rate.
 The CONTROL plane (barriers, max over ranks) always runs over gloo: the headline does not depend on RCCL coming up.  With
 N > 1 the same run then measures proofs range-sharded over the ranks (cg_prove_partial, a 384-byte all_gather,
 cg_assemble: config 4) - one at a time (latency) and several in flight per rank - and reports them as the `sharded`
-sub-record.  Only that leg opens an RCCL group, lazily, under the watchdog; if RCCL does not come up on every rank the
+sub-record (--full).  Only that leg opens an RCCL group, lazily, under the watchdog; if RCCL does not come up on every rank the
 failure is recorded in `sharded.error` and the leg runs over gloo, labelled `backend_fallback`.
 
-Checker (rank 0, after the timed region; the oracle is never the thing measured): one proof taken from the TIMED stream
+Checker (--full, rank 0, after the timed region; the oracle is never the thing measured): one proof taken from the TIMED stream
 is verified by the Python oracle's pairing (`proof_verifies`, the reference's own acceptance criterion:
 forks/groth16/src/test.rs:70-71, verifier.rs:44-65) and compared with the trapdoor's closed form, and the GPU-made key
 the bench proves on is checked entry by entry against the trapdoor (`key_check`, oracle/keycheck.py).
@@ -129,9 +136,14 @@ def parse():
                          "through the compiled C caller, with the CPU restatement's chain beside it)")
     ap.add_argument("--no-shapes", action="store_true", help="N = 1: skip the second-shape record (`shapes`: mdl1 / S22, SURVEY 8d 'report both')")
     ap.add_argument("--no-latency-curve", action="store_true", help="skip `inflight_curve` (rate and latency at 1 / 2 / 4 / 8 / 16 proofs in flight)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other measurement and check: the bracketed region, phase times and rooflines, the "
+                         "secondary legs (host witness, latency curve, cold start, sharded proofs, CPU baseline, second shape, sweep) and "
+                         "the checker.  Without it the run stops after the headline; the --no-* switches act on a --full run")
     ap.add_argument("--headline-only", action="store_true",
-                    help="profiling and A/B runs: the headline measurement and nothing else (implies every --no-* leg switch: sweep, CPU baseline, "
-                         "host witness, checker, cold start, shapes, latency curve, micro-benchmark, sharded leg)")
+                    help="with --full: the headline, the bracketed region, the phase times and the rooflines that need no run of their "
+                         "own, and nothing else (implies every --no-* leg switch: sweep, CPU baseline, host witness, checker, cold start, "
+                         "shapes, latency curve, micro-benchmark, sharded leg).  Without --full it changes nothing")
     ap.add_argument("--no-ubench", action="store_true", help="do not run tools/ubench/valu_rates (the in-run VALU issue rates of `roofline_valu`)")
     ap.add_argument("--stall-rank", type=int, default=-1,
                     help="testing aid: this rank stops before the sharded leg, as a rank that failed alone would (exercises --leg-timeout)")
@@ -525,6 +537,20 @@ def main():
 
     keyed_rs = lambda k: step_rs(k, rank, R)
 
+    def emit(out_):
+        """rank 0 prints the line on the real stdout; then a multi-rank run's process group comes down"""
+        sys.stdout.flush()
+        os.dup2(stdout_fd, 1)
+        if rank == 0:
+            print(json.dumps(out_), flush=True)
+        if world > 1:
+            os.dup2(2, 1)
+            # the line is out: a process group that does not come down must not keep the ranks (and the driver) waiting
+            t_exit = threading.Timer(30, lambda: os._exit(0))
+            t_exit.daemon = True
+            t_exit.start()
+            dist.destroy_process_group()
+
     def make_workload(bits, seed_off, dims=None):
         l_, m_, M_ = dims or (l, m, M)
         cm_, w_ = wl.synthetic_circuit(0xC5E5CE47 + seed_off, l_, m_, M_, bits, 3, profile=a.profile)
@@ -658,8 +684,65 @@ def main():
     checked_proof = timed_sample.get("proof")           # taken before any later leg overwrites it
     if a.dump_outputs and rank == 0:
         dump_proof(a.dump_outputs, last_step["proof"])
-    dt_br = bracketed(prove_headline_k, a.steps, True, threads=callers)
     info = prover.info()
+    out = {
+        "metric": "Groth16 proofs/sec (rs256-sd-shaped circuit, BN254), G1 MSM scalar-adds/sec reported alongside",
+        "value": round(value, 3), "unit": "proofs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(dt / n_timed * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (BN254 Fq/Fr, 254-bit modular integers)",
+        "data": "synthetic",
+        "value_per_rank": [round(x, 3) for x in per_rank],
+        "timing": dict(timing, method="steady state: `steps` consecutive proof completions with the pipeline kept primed, split into "
+                                      "`blocks` blocks for the block statistics; value = proofs / elapsed over that whole window "
+                                      "(max elapsed over ranks)"),
+        "config": {"workload": "%s shape: D=2^%d, m=%d, M=%d, l=%d, nnz=%d (%s mix); bit_fraction=%.2f; pk from seeded trapdoor (GPU setup)" %
+                   (a.shape, prover.domain_size.bit_length() - 1, m, M, l, nnz, a.profile, a.bits),
+                   "wires": wires, "mode": "throughput (one full key replica per GPU)",
+                   "baseline_configs": "value = configs[2] (rs256-sd, the circuit BASELINE's metric is quoted on) on one GPU; configs[1] "
+                                       "(rs256) and configs[4] (rs256-db, one replica per GPU: --gpus N) are this S21 shape with l = 20 / 28 "
+                                       "instead of 26 - a few of 1.5 M wires move between the l query and gamma_abc, which no kernel's "
+                                       "time can tell apart, so their rate IS `value` (all three proved at full size by tests/"
+                                       "test_gpu_fullsize.py); configs[3] (mdl1 / S22 sharded over the ranks) is `sharded`, its one-GPU "
+                                       "rate `shapes.mdl1`; configs[0] is the CPU path: `cpu_baseline` (those three: --full)",
+                   "h_query_basis": "coefficient" if a.h_coefficient_basis else "coset evaluation (transformed at load)",
+                   "proofs_per_rank": n_timed, "proofs_in_flight_per_gpu": inflight,
+                   "inputs": {"host": "witness in HOST memory (pageable) -> proof through cg_prove, the metric as SURVEY 8d writes it: every "
+                                      "proof uploads its %d-byte assignment first; %d assignments taken in rotation; (r,s) fresh per proof",
+                              "pinned": "witness in page-locked HOST memory (cg_host_alloc) -> proof through cg_prove: every proof uploads "
+                                        "its %d-byte assignment first; %d assignments taken in rotation; (r,s) fresh per proof",
+                              "device": "NOT the metric as written: %d-byte assignments already resident in HBM (cg_prove_dev, --witness "
+                                        "device); %d taken in rotation; (r,s) fresh per proof"}[a.witness] % (int(ws_np[0].size), len(ws_np)),
+                   "witness_origin": a.witness, "caller_threads": callers,
+                   "context": {"resident_GB": round(info["total_bytes"] / 1e9, 2), "tables_GB": round(info["table_bytes"] / 1e9, 2),
+                               "per_slot_GB": round(info["slot_bytes"] / 1e9, 3),
+                               "lone_slot_GB": round(info["lone_slot_bytes"] / 1e9, 3),     # the extra slot a proof arriving alone runs on
+                               "per_slot_GB_by_kind": {k[5:-6]: round(info[k] / 1e9, 3) for k in
+                                                       ("slot_entry_bytes", "slot_piece_bytes", "slot_bucket_bytes", "slot_transform_bytes",
+                                                        "slot_upload_bytes")},
+                               "matrices_GB": round(info["matrix_bytes"] / 1e9, 3),
+                               "window_bits": info["window_bits"], "tuned": bool(info["tuned"]),
+                               "retune_skipped_for_memory": info["retune_skipped_for_memory"]}},
+        "latency_ms": timing.get("latency_ms"),
+    }
+
+    def g1_record(tm_):
+        return {"msm_g1_pairs_per_proof": tm_["msm_g1_pairs"], "msm_g2_pairs_per_proof": tm_["msm_g2_pairs"],
+                "entries_g1": tm_["entries_g1"], "entries_g2": tm_["entries_g2"],
+                "g1_msm_scalar_adds_per_s": round(tm_["msm_g1_pairs"] * value, 1)}     # pairs consumed per second of whole-job time
+
+    if not a.full:
+        # a plain run ends here.  One untimed proof with the library's counters gives the G1 pairs per proof that the metric's
+        # scalar-adds/s is made of (they depend on the assignment, not on the time)
+        out.update(g1_record(prover.prove_dev(ws_dev[0].data_ptr(), *fresh_rs(), timings=True)[1]))
+        log("steady state %.2f proofs/s (%d proofs in %.2f s; median block %.2f, spread %.1f %%); shader clock %s GHz" %
+            (value, n_timed, dt, timing["median_block"]["value_this_rank"] * world, timing["median_block"]["spread_pct"],
+             clock.median() if clock else None))
+        emit(out)
+        return
+
+    dt_br = bracketed(prove_headline_k, a.steps, True, threads=callers)
+    out["timing"]["bracketed"] = {"ms_per_step": round(dt_br / a.steps * 1e3, 3), "value": round(a.steps * world / dt_br, 3),
+                                  "method": "barrier + synchronise, `steps` proofs, synchronise + barrier (max over ranks)"}
     log("steady state %.2f proofs/s (%d proofs in %.2f s; median block %.2f, spread %.1f %%); bracketed %.2f; shader clock %s GHz" %
         (value, n_timed, dt, timing["median_block"]["value_this_rank"] * world, timing["median_block"]["spread_pct"],
          a.steps * world / dt_br, clock.median() if clock else None))
@@ -788,56 +871,13 @@ def main():
         except Exception as e:
             roof_ntt = {"error": repr(e)}
 
-    out = {
-        "metric": "Groth16 proofs/sec (rs256-sd-shaped circuit, BN254), G1 MSM scalar-adds/sec reported alongside",
-        "value": round(value, 3), "unit": "proofs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(dt / n_timed * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u32 limbs (BN254 Fq/Fr, 254-bit modular integers)",
-        "data": "synthetic",
-        "value_per_rank": [round(x, 3) for x in per_rank],
-        "timing": dict(timing, method="steady state: `steps` consecutive proof completions with the pipeline kept primed, split into "
-                                      "`blocks` blocks for the block statistics; value = proofs / elapsed over that whole window "
-                                      "(max elapsed over ranks)",
-                       bracketed={"ms_per_step": round(dt_br / a.steps * 1e3, 3), "value": round(a.steps * world / dt_br, 3),
-                                  "method": "barrier + synchronise, `steps` proofs, synchronise + barrier (max over ranks)"}),
-        "config": {"workload": "%s shape: D=2^%d, m=%d, M=%d, l=%d, nnz=%d (%s mix); bit_fraction=%.2f; pk from seeded trapdoor (GPU setup)" %
-                   (a.shape, prover.domain_size.bit_length() - 1, m, M, l, nnz, a.profile, a.bits),
-                   "wires": wires, "mode": "throughput (one full key replica per GPU)",
-                   "baseline_configs": "value = configs[2] (rs256-sd, the circuit BASELINE's metric is quoted on) on one GPU; configs[1] "
-                                       "(rs256) and configs[4] (rs256-db, one replica per GPU: --gpus N) are this S21 shape with l = 20 / 28 "
-                                       "instead of 26 - a few of 1.5 M wires move between the l query and gamma_abc, which no kernel's "
-                                       "time can tell apart, so their rate IS `value` (all three proved at full size by tests/"
-                                       "test_gpu_fullsize.py); configs[3] (mdl1 / S22 sharded over the ranks) is `sharded`, its one-GPU "
-                                       "rate `shapes.mdl1`; configs[0] is the CPU path: `cpu_baseline`",
-                   "h_query_basis": "coefficient" if a.h_coefficient_basis else "coset evaluation (transformed at load)",
-                   "proofs_per_rank": n_timed, "proofs_in_flight_per_gpu": inflight,
-                   "inputs": {"host": "witness in HOST memory (pageable) -> proof through cg_prove, the metric as SURVEY 8d writes it: every "
-                                      "proof uploads its %d-byte assignment first; %d assignments taken in rotation; (r,s) fresh per proof",
-                              "pinned": "witness in page-locked HOST memory (cg_host_alloc) -> proof through cg_prove: every proof uploads "
-                                        "its %d-byte assignment first; %d assignments taken in rotation; (r,s) fresh per proof",
-                              "device": "NOT the metric as written: %d-byte assignments already resident in HBM (cg_prove_dev, --witness "
-                                        "device); %d taken in rotation; (r,s) fresh per proof"}[a.witness] % (int(ws_np[0].size), len(ws_np)),
-                   "witness_origin": a.witness, "caller_threads": callers,
-                   "context": {"resident_GB": round(info["total_bytes"] / 1e9, 2), "tables_GB": round(info["table_bytes"] / 1e9, 2),
-                               "per_slot_GB": round(info["slot_bytes"] / 1e9, 3),
-                               "lone_slot_GB": round(info["lone_slot_bytes"] / 1e9, 3),     # the extra slot a proof arriving alone runs on
-                               "per_slot_GB_by_kind": {k[5:-6]: round(info[k] / 1e9, 3) for k in
-                                                       ("slot_entry_bytes", "slot_piece_bytes", "slot_bucket_bytes", "slot_transform_bytes",
-                                                        "slot_upload_bytes")},
-                               "matrices_GB": round(info["matrix_bytes"] / 1e9, 3),
-                               "window_bits": info["window_bits"], "tuned": bool(info["tuned"]),
-                               "retune_skipped_for_memory": info["retune_skipped_for_memory"]}},
-        "roofline": roof, "roofline_valu": roof_valu, "roofline_ntt": roof_ntt, "phase_ms": phases,
-        "latency_ms": timing.get("latency_ms"),
-        "phase_ms_note": "one proof ALONE on this throughput context, whose proofs run their kernels back to back on one stream each (the "
-                         "overlap comes from the other proofs in flight); a latency context (proof_slots = 1) spreads a proof over five "
-                         "streams: 6.3 ms (profiles/r03_l_shard_latency.txt)",
-        "msm_g1_pairs_per_proof": g1_pairs, "msm_g2_pairs_per_proof": g2_pairs,
-        "entries_g1": tm["entries_g1"], "entries_g2": tm["entries_g2"],
-        "g1_msm_scalar_adds_per_s": round(g1_pairs * value, 1),      # pairs consumed per second of whole-job time
-    }
+    out.update({"roofline": roof, "roofline_valu": roof_valu, "roofline_ntt": roof_ntt, "phase_ms": phases,
+                "phase_ms_note": "one proof ALONE on this throughput context, whose proofs run their kernels back to back on one stream "
+                                 "each (the overlap comes from the other proofs in flight); a latency context (proof_slots = 1) spreads a "
+                                 "proof over five streams: 6.3 ms (profiles/r03_l_shard_latency.txt)"})
+    out.update(g1_record(tm))
 
-    legs_s = {}                 # wall seconds of every leg after the headline (the default run has to finish within minutes)
+    legs_s = {}                 # wall seconds of every leg after the headline (a --full run has to finish within minutes)
     out["legs_s"] = legs_s
     t_leg = [time.perf_counter()]
 
@@ -1447,17 +1487,7 @@ def main():
 
     if watchdog:
         watchdog.cancel()
-    sys.stdout.flush()
-    os.dup2(stdout_fd, 1)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        os.dup2(2, 1)
-        # the line is out: a process group that does not come down must not keep the ranks (and the driver) waiting
-        t_exit = threading.Timer(30, lambda: os._exit(0))
-        t_exit.daemon = True
-        t_exit.start()
-        dist.destroy_process_group()
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -207,3 +207,12 @@ def test_every_tool_parses():
     with open(os.path.join(tools, "patches", "r06_load_stress_experiments.patch")) as fh:
         head = fh.read(2000)
     assert "NOT applied" in head and "fingerprint" in head
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """a plain run is the headline alone; everything else is asked for with --full"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "20"])
+    a = bench.parse()
+    assert a.full is True and a.steps == 20

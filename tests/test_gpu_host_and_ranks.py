@@ -460,7 +460,7 @@ def test_bench_gpus_2_starts_its_own_ranks(tmp_path):
     """the driver's command, verbatim: no launcher around it.  One GPU here, so the ranks share it (gloo plumbing run);
     the line must carry n_gpus = 2 and a `sharded` record whose proofs equal the unsharded ones."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "12", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "12", "--warmup", "2",
            "--inflight", "4", "--blocks", "3", "--shape", "medium", "--no-host-witness", "--sharded-steps", "6"]
     run = _run_ranks(cmd, env, 1500, "gpus2")
     lines = [x for x in run.stdout.splitlines() if x.strip()]
@@ -510,7 +510,7 @@ def test_bench_gpus_8_as_eight_processes_on_the_one_gpu():
     and the sharded leg over eight strided h shards (j = rank mod 8), one all_gather per proof, bytes identical to the
     unsharded context - one proof at a time and with proofs in flight."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--allow-shared-gpu", "--steps", "8",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--backend", "gloo", "--allow-shared-gpu", "--steps", "8",
            "--warmup", "2", "--inflight", "2", "--blocks", "3", "--shape", "medium", "--no-host-witness", "--sharded-steps", "6",
            "--sharded-inflight", "2", "--sharded-stream", "16", "--no-check", "--leg-timeout", "900"]
     run = _run_ranks(cmd, env, 2400, "gpus8")
@@ -538,7 +538,7 @@ def test_bench_gpus_2_without_a_shape_shards_config_4s_own_circuit():
     is quoted on) and the SHARDED proofs are made on mdl1 at S22 - BASELINE.json configs[3], "mdl1 ... MSM sharded across 8 x
     MI355X" - in both arrangements, with the bytes of an unsharded mdl1 context."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "8", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "8", "--warmup", "2",
            "--inflight", "4", "--blocks", "3", "--no-host-witness", "--no-check", "--sharded-steps", "4", "--sharded-inflight", "2",
            "--sharded-stream", "8", "--leg-timeout", "900"]
     run = _run_ranks(cmd, env, 2400, "gpus2_mdl1")
@@ -560,7 +560,7 @@ def test_bench_survives_an_rccl_group_that_does_not_come_up():
     ranks on one device (or, at worst, says nothing until --rccl-deadline), which the sharded leg records as `error` and
     answers by running over gloo, labelled `backend_fallback` - rc 0, one line, no hang."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "nccl", "--allow-shared-gpu", "--steps", "12",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "nccl", "--allow-shared-gpu", "--steps", "12",
            "--warmup", "2", "--inflight", "4", "--blocks", "3", "--shape", "medium", "--no-host-witness", "--sharded-steps", "6",
            "--sharded-stream", "24", "--rccl-deadline", "60", "--leg-timeout", "400"]
     t0 = time.time()

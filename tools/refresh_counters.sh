@@ -6,8 +6,8 @@ O=${1:-gpurun_out/refresh}; mkdir -p $O
 (time python -m pytest tests -m gpu -q) > $O/gputests.log 2>&1; tail -2 $O/gputests.log
 tools/profile_pmc.sh $O/pmc "rs256-sd/gates/bits=0.90" > /dev/null 2>&1
 cp $O/pmc/pmc_counters.json profiles/pmc_counters.json
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 200 $O/bench_default.err
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 200 $O/bench_default.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err
 python - <<PY
 import json
 for f in ("bench_default", "bench_driver_args"):
