@@ -27,6 +27,8 @@ CG_FLAG_H_COEFFICIENT_BASIS = 1
 CG_FLAG_LATENCY_MODE, CG_FLAG_THROUGHPUT_MODE, CG_FLAG_SPIN_WAIT, CG_FLAG_CONTIGUOUS_H_SHARDS, CG_FLAG_H_SCALARS_EXTERNAL = 2, 4, 8, 16, 32
 CG_FLAG_STAGED_LOAD = 64
 CG_FLAG_NO_LONE_SLOT = 128
+CG_FLAG_CHECK_WITNESS = 256
+CG_ERR_UNSATISFIED = -8
 CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
 
 
@@ -34,6 +36,17 @@ class CrescentGpuError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__("libcrescent_gpu error %d: %s" % (code, msg))
         self.code = code
+
+
+class UnsatisfiedWitness(CrescentGpuError):
+    """The witness fails a constraint (CG_ERR_UNSATISFIED): the reference's `cs.is_satisfied()` failing in the circom builder
+    (builder.rs:82-94) or in the prover's debug assertion (prover.rs:197).  `report` is the WitnessReport when the check
+    itself was called (check_witness, Groth16.prove(check_witness=True)); a proving call on a flagged context
+    (Prover(check_witness=True)) names the constraint in its message only."""
+
+    def __init__(self, msg: str, report: Optional["WitnessReport"] = None):
+        super().__init__(CG_ERR_UNSATISFIED, msg)
+        self.report = report
 
 
 def library_path() -> str:
@@ -92,6 +105,42 @@ class CgLoadTimings(C.Structure):
                [("reserved", C.c_int32 * 3)]
 
 
+class _CgWitnessReport(C.Structure):
+    _fields_ = [("n_unsatisfied", C.c_uint64), ("first_unsatisfied", C.c_uint64), ("a", C.c_uint8 * 32), ("b", C.c_uint8 * 32),
+                ("c", C.c_uint8 * 32), ("check_ms", C.c_float), ("reserved", C.c_int32 * 7)]
+
+
+@dataclass
+class WitnessReport:
+    """cg_witness_report: how many constraints the assignment fails, the first of them (what `which_is_unsatisfied` names)
+    and the three inner products of that row as integers"""
+    n_unsatisfied: int
+    first_unsatisfied: Optional[int]
+    a: Optional[int]
+    b: Optional[int]
+    c: Optional[int]
+    check_ms: float
+
+    @property
+    def satisfied(self) -> bool:
+        return self.n_unsatisfied == 0
+
+
+def _check_witness_call(fn, handle, assignment, on_device: bool, num_variables: int) -> WitnessReport:
+    rep = _CgWitnessReport()
+    if on_device:
+        rc = fn(handle, C.c_void_p(assignment), 1, C.byref(rep))
+    else:
+        w = _u8(assignment, num_variables * 32)
+        rc = fn(handle, _ptr(w), 0, C.byref(rep))
+    if rc != CG_ERR_UNSATISFIED:
+        _check(rc)
+    bad = rep.n_unsatisfied != 0
+    val = lambda f: int.from_bytes(bytes(f), "little") if bad else None
+    return WitnessReport(int(rep.n_unsatisfied), int(rep.first_unsatisfied) if bad else None, val(rep.a), val(rep.b), val(rep.c),
+                         float(rep.check_ms))
+
+
 class _CgProverParamsView(C.Structure):
     _fields_ = [("pk", _CgProvingKey), ("gamma_g2", C.c_void_p), ("gamma_abc_g1", C.c_void_p), ("gamma_abc_len", C.c_uint64),
                 ("vk_bytes", C.c_void_p), ("vk_len", C.c_uint64), ("pvk_bytes", C.c_void_p), ("pvk_len", C.c_uint64),
@@ -145,6 +194,8 @@ _SIGNATURES = {
     "cg_ctx_wait_ready": (C.c_int, [C.c_void_p, C.c_int32]),
     "cg_probe_shader_clock": (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(C.c_double)]),
     "cg_witness_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_check_witness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_CgWitnessReport)]),
+    "cg_qap_check_witness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_CgWitnessReport)]),
     "cg_domain_size": (C.c_uint64, [C.c_void_p]),
     "cg_qap_load": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(_CgCsr), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32]),
     "cg_qap_witness_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
@@ -223,6 +274,8 @@ def lib() -> C.CDLL:
 
 
 def _check(rc: int) -> None:
+    if rc == CG_ERR_UNSATISFIED:
+        raise UnsatisfiedWitness(lib().cg_last_error().decode("utf-8", "replace"))
     if rc != 0:
         raise CrescentGpuError(rc, lib().cg_last_error().decode("utf-8", "replace"))
 
@@ -443,8 +496,10 @@ class Prover:
                  shard_rank: int = 0, shard_count: int = 1, proof_slots: int = 1, h_coefficient_basis: bool = False,
                  mode: Optional[str] = None, spin_wait: bool = False, contiguous_h_shards: bool = False,
                  h_scalars_external: bool = False, flags: int = 0, staged_load: bool = False, shard_span: Optional[Tuple[int, int]] = None,
-                 lone_slot: bool = True):
-        """lone_slot=False: CG_FLAG_NO_LONE_SLOT (a throughput context then holds no extra slot for proofs that arrive alone).
+                 lone_slot: bool = True, check_witness: bool = False):
+        """check_witness=True: CG_FLAG_CHECK_WITNESS - every proving / witness-map call on the context first checks that the
+        witness satisfies the R1CS and raises UnsatisfiedWitness instead of returning a proof that cannot verify.
+        lone_slot=False: CG_FLAG_NO_LONE_SLOT (a throughput context then holds no extra slot for proofs that arrive alone).
         h_coefficient_basis=True keeps the h query as loaded (seven transforms per proof, CG_FLAG_H_COEFFICIENT_BASIS).
         shard_span: (lo, hi) in 1/10000 of every query - this shard's part instead of the shard_rank-th of shard_count equal parts
         (cg_options.shard_span: unequal shares for the ranks that also run the witness map).
@@ -458,7 +513,8 @@ class Prover:
         flags |= (CG_FLAG_H_COEFFICIENT_BASIS if h_coefficient_basis else 0) | (CG_FLAG_LATENCY_MODE if mode == "latency" else 0) | \
                  (CG_FLAG_THROUGHPUT_MODE if mode == "throughput" else 0) | (CG_FLAG_SPIN_WAIT if spin_wait else 0) | \
                  (CG_FLAG_CONTIGUOUS_H_SHARDS if contiguous_h_shards else 0) | (CG_FLAG_H_SCALARS_EXTERNAL if h_scalars_external else 0) | \
-                 (CG_FLAG_STAGED_LOAD if staged_load else 0) | (0 if lone_slot else CG_FLAG_NO_LONE_SLOT)
+                 (CG_FLAG_STAGED_LOAD if staged_load else 0) | (0 if lone_slot else CG_FLAG_NO_LONE_SLOT) | \
+                 (CG_FLAG_CHECK_WITNESS if check_witness else 0)
         L = lib()
         self.num_inputs = matrices.num_instance_variables
         self.num_constraints = matrices.num_constraints
@@ -525,6 +581,12 @@ class Prover:
             return False
         _check(rc)
         return True
+
+    def check_witness(self, assignment, on_device: bool = False) -> WitnessReport:
+        """cg_check_witness: does the assignment (host scalars, or a device address with on_device) satisfy the R1CS, and
+        which constraint fails first (`cs.is_satisfied()` / `which_is_unsatisfied()`, builder.rs:82-94).  Returns the
+        report either way; a non-canonical element raises CrescentGpuError as prove() does."""
+        return _check_witness_call(lib().cg_check_witness, self._h, assignment, on_device, self.num_variables)
 
     def prove_host_ptr(self, ptr: int, r: int, s: int, timings: bool = False):
         """cg_prove on a raw host address (num_variables x 32 B canonical): pageable or page-locked (HostBuffer)"""
@@ -735,6 +797,10 @@ class QapContext:
         h = np.zeros(self.domain_size * 32, dtype=np.uint8)
         _check(lib().cg_qap_witness_map(self._h, _ptr(w), 0, _ptr(h), 0))
         return h
+
+    def check_witness(self, assignment, on_device: bool = False) -> WitnessReport:
+        """cg_qap_check_witness: Prover.check_witness without a key (where the reference's check sits: the circom builder)"""
+        return _check_witness_call(lib().cg_qap_check_witness, self._h, assignment, on_device, self.num_variables)
 
     def witness_map_dev(self, d_assignment: int, d_h: int) -> None:
         """assignment (num_variables x 32 B) and h (domain_size x 32 B) both in this GPU's memory"""
@@ -947,18 +1013,25 @@ class Groth16:
 
     @classmethod
     def create_proof_with_reduction_and_matrices(cls, pk: ProvingKey, r: int, s: int, matrices: ConstraintMatrices,
-                                                 num_inputs: int, num_constraints: int, full_assignment) -> Proof:
-        """prover.rs:26-51."""
+                                                 num_inputs: int, num_constraints: int, full_assignment,
+                                                 check_witness: bool = False) -> Proof:
+        """prover.rs:26-51.  check_witness: the `debug_assert!(cs.is_satisfied())` of prover.rs:197 - the witness is checked
+        on the resident circuit first and UnsatisfiedWitness (with the report) raised instead of proving."""
         if num_inputs != matrices.num_instance_variables or num_constraints != matrices.num_constraints:
             raise ValueError("num_inputs/num_constraints disagree with the matrices")
         prover = cls._prover_for(pk, matrices)
         try:
+            if check_witness:
+                rep = prover.check_witness(full_assignment)
+                if not rep.satisfied:
+                    raise UnsatisfiedWitness("constraint %d of %d is not satisfied (%d in all)"
+                                             % (rep.first_unsatisfied, matrices.num_constraints, rep.n_unsatisfied), rep)
             return prover.prove(full_assignment, r, s)
         finally:
             prover._unlease()
 
     @classmethod
-    def create_proof_with_reduction(cls, circuit: "CircomCircuit", pk: ProvingKey, r: int, s: int) -> Proof:
+    def create_proof_with_reduction(cls, circuit: "CircomCircuit", pk: ProvingKey, r: int, s: int, check_witness: bool = False) -> Proof:
         """prover.rs:177-221.  The reference synthesises the constraint system from the circuit on every call
         (circuit.rs:29-86) and extracts the matrices (r1cs_to_qap.rs:58-80); here the matrices ARE the circuit's
         R1CS (column = wire id, circuit.rs:61-67) and stay resident, so only the witness travels."""
@@ -966,15 +1039,15 @@ class Groth16:
             raise CrescentGpuError(-1, "AssignmentMissing: the circuit has no witness (SynthesisError::AssignmentMissing, circuit.rs:38-45)")
         cm = circuit.r1cs.matrices
         return cls.create_proof_with_reduction_and_matrices(pk, r, s, cm, cm.num_instance_variables, cm.num_constraints,
-                                                            circuit.full_assignment())
+                                                            circuit.full_assignment(), check_witness=check_witness)
 
     @classmethod
-    def prove(cls, pk: ProvingKey, circuit: "CircomCircuit", rng) -> Proof:
+    def prove(cls, pk: ProvingKey, circuit: "CircomCircuit", rng, check_witness: bool = False) -> Proof:
         """`SNARK::prove` (lib.rs:76-82) -> create_random_proof_with_reduction (prover.rs:142-154): r and s are
         sampled from `rng` (any object with randrange, e.g. random.Random / random.SystemRandom), r first."""
         r = rng.randrange(FR_MODULUS)
         s = rng.randrange(FR_MODULUS)
-        return cls.create_proof_with_reduction(circuit, pk, r, s)
+        return cls.create_proof_with_reduction(circuit, pk, r, s, check_witness=check_witness)
 
     @classmethod
     def create_proof_no_zk(cls, circuit: "CircomCircuit", pk: ProvingKey) -> Proof:
@@ -1085,6 +1158,27 @@ class CircomCircuit:
 
     def full_assignment(self) -> np.ndarray:
         return self.witness
+
+    def check_witness(self) -> WitnessReport:
+        """the witness against the circuit's R1CS on the GPU, over the resident matrices LibsnarkReduction keeps"""
+        if self.witness is None:
+            raise CrescentGpuError(-1, "AssignmentMissing: the circuit has no witness (SynthesisError::AssignmentMissing, circuit.rs:38-45)")
+        cm = self.r1cs.matrices
+        LibsnarkReduction._cache.max_cached = LibsnarkReduction.MAX_CACHED
+        ctx = LibsnarkReduction._cache.lease(_matrices_key(cm), lambda: QapContext(cm))
+        try:
+            return ctx.check_witness(self.witness)
+        finally:
+            ctx._unlease()
+
+    def is_satisfied(self) -> bool:
+        """`cs.is_satisfied()` as the circom builder asks it (builder.rs:82-94)"""
+        return self.check_witness().satisfied
+
+    def which_is_unsatisfied(self) -> Optional[int]:
+        """`cs.which_is_unsatisfied()`: the index of the first constraint the witness fails, None when it fails none
+        (the reference names the constraint by a string; circom constraints have no names, so the index is the name)"""
+        return self.check_witness().first_unsatisfied
 
     def get_public_inputs(self):
         """circuit.rs:18-26: wires 1 .. num_inputs-1 as integers (None without a witness)"""
@@ -1429,19 +1523,26 @@ class ProofRejected(CrescentGpuError):
 
 
 def create_client_state(r1cs_bytes, prover_params_bytes, witness, rng, prover_aux: Optional[str] = None,
-                        credtype: str = "jwt", prover: Optional["Prover"] = None, verify: bool = False) -> "ClientState":
+                        credtype: str = "jwt", prover: Optional["Prover"] = None, verify: bool = False,
+                        check_witness: bool = False) -> "ClientState":
     """creds/src/lib.rs:255-301 without the witness generator: parse main_c.r1cs and prover_params.bin, prove with
     (r, s) drawn from `rng`, and assemble the ClientState the `show` step starts from.  `witness` is the full wire
     assignment the WASM calculator would have produced (wire 0 = 1).  With verify=True the proof is checked against the
     groth16_pvk of prover_params.bin on the GPU before the state is built, as the reference does (:286-290), and a
-    rejected proof raises ProofRejected."""
+    rejected proof raises ProofRejected.  With check_witness=True the witness is checked against the R1CS on the GPU before it
+    is proved (the circom builder's check, builder.rs:82-94) and UnsatisfiedWitness names the first failing constraint."""
     r1cs = R1CSFile(r1cs_bytes)
     pp = ProverParams.from_bytes(prover_params_bytes)
     circuit = CircomCircuit(r1cs, witness)
     if prover is not None:
+        if check_witness:
+            rep = prover.check_witness(circuit.full_assignment())
+            if not rep.satisfied:
+                raise UnsatisfiedWitness("constraint %d of %d is not satisfied (%d in all)"
+                                         % (rep.first_unsatisfied, prover.num_constraints, rep.n_unsatisfied), rep)
         proof = prover.prove(circuit.full_assignment(), rng.randrange(FR_MODULUS), rng.randrange(FR_MODULUS))
     else:
-        proof = Groth16.prove(pp.groth16_params, circuit, rng)
+        proof = Groth16.prove(pp.groth16_params, circuit, rng, check_witness=check_witness)
     if verify:
         with PreparedVerifyingKey(pp.groth16_pvk) as pvk:
             if not Groth16.verify_with_processed_vk(pvk, circuit.get_public_inputs(), proof):

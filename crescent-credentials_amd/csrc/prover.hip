@@ -313,6 +313,7 @@ struct cg_ctx {
     bool latency = false;
     bool spin_wait = false;      // CG_FLAG_SPIN_WAIT
     bool external_q = false;     // CG_FLAG_H_SCALARS_EXTERNAL: no witness-map resources; the h scalars arrive with every proof
+    bool check_witness = false;  // CG_FLAG_CHECK_WITNESS: every witness map also checks a·b = c row by row (wmap29.hpp SatCheck29)
     // device bytes that stay resident (cg_ctx_get_info): window tables + validity flags | matrices and domain tables | one slot
     // (slot_bytes is the sum of slot_part: entry lists, segment pieces, bucket arrays and reduction buffers, the witness
     // map's vectors + the h MSM's scalars, one upload buffer - account_slot)
@@ -752,10 +753,19 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
     if (opt && opt->shard_span != 0 && (shard_count <= 1 || span_lo >= span_hi || span_hi > 10000))
         return fail(CG_ERR_INVALID_ARGUMENT, "shard_span needs a sharded context and 0 <= lo < hi <= 10000");
     constexpr int32_t KNOWN_FLAGS = CG_FLAG_H_COEFFICIENT_BASIS | CG_FLAG_LATENCY_MODE | CG_FLAG_THROUGHPUT_MODE | CG_FLAG_SPIN_WAIT |
-                                    CG_FLAG_CONTIGUOUS_H_SHARDS | CG_FLAG_H_SCALARS_EXTERNAL | CG_FLAG_STAGED_LOAD | CG_FLAG_NO_LONE_SLOT;
+                                    CG_FLAG_CONTIGUOUS_H_SHARDS | CG_FLAG_H_SCALARS_EXTERNAL | CG_FLAG_STAGED_LOAD | CG_FLAG_NO_LONE_SLOT |
+                                    CG_FLAG_CHECK_WITNESS;
     if (opt && (opt->flags & ~KNOWN_FLAGS)) return fail(CG_ERR_INVALID_ARGUMENT, "unknown bits in flags");
     if (opt && (opt->flags & CG_FLAG_H_SCALARS_EXTERNAL) && ((opt->flags & CG_FLAG_H_COEFFICIENT_BASIS) || shard_count <= 1))
         return fail(CG_ERR_INVALID_ARGUMENT, "flags: CG_FLAG_H_SCALARS_EXTERNAL needs a sharded context over the folded key");
+    if (opt && (opt->flags & CG_FLAG_H_SCALARS_EXTERNAL) && (opt->flags & CG_FLAG_CHECK_WITNESS))
+        return fail(CG_ERR_INVALID_ARGUMENT, "flags: CG_FLAG_CHECK_WITNESS needs the matrices, which a CG_FLAG_H_SCALARS_EXTERNAL context does not hold");
+    // the flag is a promise to read the matrices on every proof: a load that asks for it without them is told so by the flag's
+    // name, before the key is looked at (without the flag the same views are refused further down, after the key's pointers)
+    if (opt && (opt->flags & CG_FLAG_CHECK_WITNESS))
+        for (int k = 0; k < 3; ++k)
+            if (const char* why = csr_view_problem(abc[k]))
+                return fail(CG_ERR_INVALID_ARGUMENT, "flags: CG_FLAG_CHECK_WITNESS checks witnesses against the matrices, and matrix %d has a %s", k, why);
     if (opt && (opt->flags & CG_FLAG_LATENCY_MODE) && (opt->flags & CG_FLAG_THROUGHPUT_MODE))
         return fail(CG_ERR_INVALID_ARGUMENT, "flags: CG_FLAG_LATENCY_MODE and CG_FLAG_THROUGHPUT_MODE are exclusive");
     // every pointer the structs carry is checked before anything is read through it (a half-filled struct from the
@@ -786,6 +796,7 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
         c->n_slots_final = n_slots;
         c->folded = !(opt && (opt->flags & CG_FLAG_H_COEFFICIENT_BASIS));
         c->external_q = opt && (opt->flags & CG_FLAG_H_SCALARS_EXTERNAL);
+        c->check_witness = opt && (opt->flags & CG_FLAG_CHECK_WITNESS);
         // a staged load proves in the reference's arrangement first (see CG_FLAG_STAGED_LOAD); sharded contexts and contexts
         // that keep that arrangement for good load synchronously
         const bool staged = opt && (opt->flags & CG_FLAG_STAGED_LOAD) && c->folded && shard_count == 1;
@@ -1028,7 +1039,15 @@ extern "C" void cg_circuit_free(cg_ctx* ctx) {
 // ---------------------------------------------------------------------------------------------
 static void run_witness_map(cg_ctx* c, ProofSlot* S, const Fr* w_canon_dev, hipStream_t st, bool coset_values) {
     wm29_run(c->wdom, c->A, c->B, c->C, c->dA, c->dB, c->dC, S->wm, w_canon_dev, c->M, c->m, c->l, S->h_canon.p, st, coset_values,
-             coset_values && c->h_strided ? &c->wstr : nullptr);
+             coset_values && c->h_strided ? &c->wstr : nullptr, 0, c->check_witness);
+}
+
+// CG_FLAG_CHECK_WITNESS: the verdict of the check a witness map queued, read where h_bad_input is read - after the call's
+// own synchronisation of the slot's stream 0.  -> CG_OK or CG_ERR_UNSATISFIED
+static int unsatisfied(const cg_ctx* c, const ProofSlot* S) {
+    const unsigned long long n = S->wm.sat.h_rec.p[0], first = S->wm.sat.h_rec.p[1];
+    if (!n) return CG_OK;
+    return fail(CG_ERR_UNSATISFIED, "constraint %llu of %llu is not satisfied (%llu in all)", first, (unsigned long long)c->m, n);
 }
 
 // x >= r for any of n scalars -> *bad = 1 (the witness map's own input check, for proofs that skip the witness map)
@@ -1220,6 +1239,8 @@ static int prove_partial_impl(cg_ctx* c, ProofSlot* S, const Fr* w_dev, bool ski
     if (S->wm.h_bad_input.p[0])
         return fail(CG_ERR_INVALID_ARGUMENT, q_dev ? "full_assignment or the h-scalar slice holds a value >= the scalar field modulus"
                                                    : "full_assignment holds a value >= the scalar field modulus");
+    if (c->check_witness && !q_dev)
+        if (int e = unsatisfied(c, S)) return e;
     P.h = to_affine(S->eh.value());
     P.l = to_affine(S->el.value());
     P.a = to_affine(S->ea.value());
@@ -1559,7 +1580,8 @@ struct cg_partial {
 // shards, to host or device memory; waits for them.  -> CG_OK or CG_ERR_INVALID_ARGUMENT (a non-canonical assignment element)
 static int coset_values_to(cg_ctx* ctx, ProofSlot* S, const Fr* w_dev, int half, void* q_out, int q_on_device) {
     hipStream_t s0 = S->st[0];
-    wm29_run(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, S->wm, w_dev, ctx->M, ctx->m, ctx->l, S->h_canon.p, s0, true, nullptr, half);
+    wm29_run(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, S->wm, w_dev, ctx->M, ctx->m, ctx->l, S->h_canon.p, s0, true, nullptr, half,
+             ctx->check_witness && !half);
     const Fr* src = S->h_canon.p;
     if (ctx->h_strided) {        // shard-major: shard p's scalars q_{p + k·count} become the contiguous slice p
         Fr* tmp = reinterpret_cast<Fr*>(half == 1 ? S->wm.vb.p : S->wm.va.p);      // a vector the half just computed does not use
@@ -1571,6 +1593,8 @@ static int coset_values_to(cg_ctx* ctx, ProofSlot* S, const Fr* w_dev, int half,
     CG_HIP(hipMemcpyAsync(q_out, src, ctx->D * 32, q_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s0));
     CG_HIP(hipStreamSynchronize(s0));
     if (S->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+    if (ctx->check_witness && !half)
+        if (int e = unsatisfied(ctx, S)) return e;
     return CG_OK;
 }
 
@@ -1838,7 +1862,49 @@ extern "C" int cg_witness_map(cg_ctx* ctx, const uint8_t* full_assignment, uint8
         CG_HIP(hipMemcpyAsync(h_out, S->h_canon.p, ctx->D * 32, hipMemcpyDeviceToHost, s0));
         CG_HIP(hipStreamSynchronize(s0));
         if (S->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+        if (ctx->check_witness)
+            if (int e = unsatisfied(ctx, S)) return e;
         return CG_OK;
+    } catch (...) {
+        return translate_exception();
+    }
+}
+
+// Replaces: cs.is_satisfied() / which_is_unsatisfied() (forks/circom-compat/src/circom/builder.rs:82-94, forks/groth16/src/prover.rs:197).
+// A proof slot is the working set, so the call sits beside proofs in flight like any other and cg_circuit_free drains it.
+extern "C" int cg_check_witness(cg_ctx* ctx, const void* full_assignment, int assignment_on_device, cg_witness_report* report) {
+    if (!ctx || !full_assignment) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (ctx->external_q) return fail(CG_ERR_INVALID_ARGUMENT, "context loaded with CG_FLAG_H_SCALARS_EXTERNAL holds no matrices to check a witness against");
+    CallGuard inside(ctx);
+    try {
+        CG_HIP(hipSetDevice(ctx->device));
+        std::shared_lock<TuneGate> tl(ctx->tune_mu);
+        if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
+        UploadGuard up;
+        const Fr* w_dev = (const Fr*)full_assignment;
+        if (!assignment_on_device) {
+            up.take(ctx);
+            (void)upload_assignment(ctx, up.u, full_assignment, false);
+            w_dev = up.u->w.p;
+        }
+        SlotGuard g(ctx);
+        ProofSlot* S = g.s;
+        hipStream_t s0 = S->st[0];
+        CG_HIP(hipEventRecord(S->ev_t[0], s0));
+        wm29_check(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, S->wm, w_dev, ctx->M, ctx->m, ctx->l, s0);
+        CG_HIP(hipEventRecord(S->ev_t[1], s0));
+        CG_HIP(hipEventSynchronize(S->ev_t[1]));
+        if (S->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+        if (report) {
+            memset(report, 0, sizeof(*report));
+            report->n_unsatisfied = S->wm.sat.h_rec.p[0];
+            report->first_unsatisfied = S->wm.sat.h_rec.p[1];
+            memcpy(report->a, S->wm.sat.h_row.p, 32);
+            memcpy(report->b, S->wm.sat.h_row.p + 8, 32);
+            memcpy(report->c, S->wm.sat.h_row.p + 16, 32);
+            report->check_ms = ev_ms(S->ev_t[0], S->ev_t[1]);
+        }
+        return unsatisfied(ctx, S);
     } catch (...) {
         return translate_exception();
     }

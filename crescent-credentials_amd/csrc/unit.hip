@@ -234,8 +234,12 @@ struct cg_qap_ctx {
     Wm29Buffers wm;
     DevBuf<Fr> w_canon, h_canon;
     hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};     // cg_qap_check_witness: check_ms
     std::mutex mu;
-    ~cg_qap_ctx() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+    ~cg_qap_ctx() {
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    }
 };
 
 namespace cg {
@@ -267,6 +271,7 @@ extern "C" int cg_qap_load(cg_qap_ctx** out, const cg_csr abc[3], uint64_t num_i
         c->l = num_inputs; c->m = num_constraints; c->M = num_variables;
         c->logD = logD; c->D = 1ull << logD;
         CG_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+        for (auto& e : c->ev) CG_HIP(hipEventCreate(&e));
         c->A.upload(abc[0], c->m, c->M, c->st);
         c->B.upload(abc[1], c->m, c->M, c->st);
         c->C.upload(abc[2], c->m, c->M, c->st);
@@ -306,6 +311,39 @@ extern "C" int cg_qap_witness_map(cg_qap_ctx* ctx, const void* full_assignment, 
         if (!h_on_device) CG_HIP(hipMemcpyAsync(h_out, ctx->h_canon.p, ctx->D * 32, hipMemcpyDeviceToHost, ctx->st));
         CG_HIP(hipStreamSynchronize(ctx->st));
         if (ctx->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+// cg_check_witness on the key-less handle (prover.hip): the same kernels over this handle's working set
+extern "C" int cg_qap_check_witness(cg_qap_ctx* ctx, const void* full_assignment, int assignment_on_device, cg_witness_report* report) {
+    if (!ctx || !full_assignment) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    try {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        CG_HIP(hipSetDevice(ctx->device));
+        const Fr* w = (const Fr*)full_assignment;
+        if (!assignment_on_device) {
+            CG_HIP(hipMemcpyAsync(ctx->w_canon.p, full_assignment, ctx->M * 32, hipMemcpyHostToDevice, ctx->st));
+            w = ctx->w_canon.p;
+        }
+        CG_HIP(hipEventRecord(ctx->ev[0], ctx->st));
+        wm29_check(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, ctx->wm, w, ctx->M, ctx->m, ctx->l, ctx->st);
+        CG_HIP(hipEventRecord(ctx->ev[1], ctx->st));
+        CG_HIP(hipStreamSynchronize(ctx->st));
+        if (ctx->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+        const unsigned long long n = ctx->wm.sat.h_rec.p[0], first = ctx->wm.sat.h_rec.p[1];
+        if (report) {
+            memset(report, 0, sizeof(*report));
+            report->n_unsatisfied = n;
+            report->first_unsatisfied = first;
+            memcpy(report->a, ctx->wm.sat.h_row.p, 32);
+            memcpy(report->b, ctx->wm.sat.h_row.p + 8, 32);
+            memcpy(report->c, ctx->wm.sat.h_row.p + 16, 32);
+            (void)hipEventElapsedTime(&report->check_ms, ctx->ev[0], ctx->ev[1]);
+        }
+        if (n) return fail(CG_ERR_UNSATISFIED, "constraint %llu of %llu is not satisfied (%llu in all)", first, (unsigned long long)ctx->m, n);
         return CG_OK;
     } catch (...) {
         return translate_current_exception();

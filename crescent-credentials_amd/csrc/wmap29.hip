@@ -9,6 +9,7 @@
 // scalings, the 1/n factors, the pointwise step and the exit from Montgomery form all fused into the
 // loads and stores of those passes.
 #include "wmap29.hpp"
+#include "satcheck.hpp"
 
 namespace cg {
 
@@ -518,9 +519,65 @@ static void dit29(const Wm29Domain& d, const uint32_t* tw, const uint32_t* in_a,
     }
 }
 
-void wm29_run(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const DevCsr& C, const Csr29& dA, const Csr29& dB,
-              const Csr29& dC, Wm29Buffers& buf, const Fr* w_canon, uint64_t M, uint64_t m, uint64_t l, Fr* h_out,
-              hipStream_t st, bool coset_values, const Wm29Strided* strided, int half) {
+// ---- witness check: a_i·b_i = c_i for every row i < m ---------------------------------------------------------------------
+__global__ void k_sat_init29(unsigned long long* __restrict__ rec) {
+    if (threadIdx.x == 0) { rec[0] = 0ull; rec[1] = ~0ull; }
+}
+// One thread per STORED element j < D (the vectors are read once, 64 lanes x 32 B contiguous); the row it holds is i = rev(j),
+// and only i < m is a constraint: rows m .. m+l-1 of va carry the instance wires (k_w_to29), everything above is zero padding.
+// The wave votes (a 64-bit ballot); a wave without a failing row - every wave of a satisfied witness - leaves here and performs
+// no atomic.  Otherwise the count is the ballot's population, the smallest row a minimum over the lanes (the lanes' rows are
+// bit-reversed, so not in lane order), and ONE lane issues the pair of atomics on the record in device memory.
+__global__ void __launch_bounds__(256) k_sat_check29(const uint32_t* __restrict__ va, const uint32_t* __restrict__ vb,
+                                                     const uint32_t* __restrict__ vc, uint64_t D, uint64_t m, int logn,
+                                                     unsigned long long* __restrict__ rec) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = j < D ? brev((uint32_t)j, logn) : 0xffffffffu;
+    bool bad = false;
+    if (j < D && (uint64_t)i < m) {
+        const uint4* pa = reinterpret_cast<const uint4*>(va + j * 8);
+        const uint4* pb = reinterpret_cast<const uint4*>(vb + j * 8);
+        const uint4* pc = reinterpret_cast<const uint4*>(vc + j * 8);
+        const uint4 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1], c0 = pc[0], c1 = pc[1];
+        const uint32_t a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        const uint32_t b[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+        const uint32_t c[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+        bad = !sat_row_ok(a, b, c);
+    }
+    const unsigned long long failing = __ballot(bad);
+    if (failing == 0ull) return;                                   // wave-uniform
+    uint32_t first = bad ? i : 0xffffffffu;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) first = min(first, (uint32_t)__shfl_xor((int)first, off, 64));
+    if ((threadIdx.x & 63u) == 0u) {
+        atomicAdd(&rec[0], (unsigned long long)__popcll(failing));
+        atomicMin(&rec[1], (unsigned long long)first);
+    }
+}
+// the report's three values: a_i, b_i, c_i of the first failing row, canonical.  Runs BEHIND the check on the same stream
+// and reads its record; one thread.
+__global__ void k_sat_row29(const uint32_t* __restrict__ va, const uint32_t* __restrict__ vb, const uint32_t* __restrict__ vc,
+                            const unsigned long long* __restrict__ rec, uint64_t m, int logn, uint32_t* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (rec[0] == 0ull || rec[1] >= m) {
+        for (int k = 0; k < 24; ++k) out[k] = 0u;
+        return;
+    }
+    const uint64_t j = brev((uint32_t)rec[1], logn);
+    const uint32_t* v[3] = {va, vb, vc};
+    for (int k = 0; k < 3; ++k) {
+        uint32_t in[8], o[8];
+        for (int t = 0; t < 8; ++t) in[t] = v[k][j * 8 + t];
+        sat_row_value(in, o);
+        for (int t = 0; t < 8; ++t) out[k * 8 + t] = o[t];
+    }
+}
+
+// w -> R' form (and the instance wires behind A's rows), then <M_i, w> for the first `nvec` matrices (only matrix half - 1
+// when `half` is set) into va / vb / vc at bit-reversed rows
+static void wm29_products(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const DevCsr& C, const Csr29& dA, const Csr29& dB,
+                          const Csr29& dC, Wm29Buffers& buf, const Fr* w_canon, uint64_t M, uint64_t m, uint64_t l, hipStream_t st, int nvec,
+                          int half) {
     const uint64_t D = dom.n;
     const int logn = dom.logn;
     // the flag is HOST memory the kernel writes only when it meets a non-canonical element: no memset, no copy back
@@ -531,7 +588,6 @@ void wm29_run(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const Dev
     CG_KERNEL_CHECK();
     const DevCsr* mats[3] = {&A, &B, &C};
     const Csr29* dicts[3] = {&dA, &dB, &dC};
-    const int nvec = coset_values ? 2 : 3;       // c's share of the quotient lives in the folded l query
     for (int k = 0; k < nvec; ++k) {
         if (half && k != half - 1) continue;       // one side of the quotient only (wmap29.hpp): the other matrix is somebody else's
         if (k) fill_zero(v[k], D * 32, st);
@@ -548,6 +604,33 @@ void wm29_run(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const Dev
             src = scratch;
         }
     }
+}
+// the check over va / vb / vc and the copy of its record, on st
+static void wm29_queue_check(const Wm29Domain& dom, Wm29Buffers& buf, uint64_t m, hipStream_t st) {
+    k_sat_init29<<<1, 64, 0, st>>>(buf.sat.rec.p);
+    k_sat_check29<<<ceil_div(dom.n, 256), 256, 0, st>>>(buf.va.p, buf.vb.p, buf.vc.p, dom.n, m, dom.logn, buf.sat.rec.p);
+    CG_KERNEL_CHECK();
+    CG_HIP(hipMemcpyAsync(buf.sat.h_rec.p, buf.sat.rec.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+}
+
+void wm29_check(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const DevCsr& C, const Csr29& dA, const Csr29& dB, const Csr29& dC,
+                Wm29Buffers& buf, const Fr* w_canon, uint64_t M, uint64_t m, uint64_t l, hipStream_t st) {
+    wm29_products(dom, A, B, C, dA, dB, dC, buf, w_canon, M, m, l, st, 3, 0);
+    wm29_queue_check(dom, buf, m, st);
+    k_sat_row29<<<1, 64, 0, st>>>(buf.va.p, buf.vb.p, buf.vc.p, buf.sat.rec.p, m, dom.logn, buf.sat.row.p);
+    CG_KERNEL_CHECK();
+    CG_HIP(hipMemcpyAsync(buf.sat.h_row.p, buf.sat.row.p, 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+}
+
+void wm29_run(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const DevCsr& C, const Csr29& dA, const Csr29& dB,
+              const Csr29& dC, Wm29Buffers& buf, const Fr* w_canon, uint64_t M, uint64_t m, uint64_t l, Fr* h_out,
+              hipStream_t st, bool coset_values, const Wm29Strided* strided, int half, bool check_witness) {
+    uint32_t* v[3] = {buf.va.p, buf.vb.p, buf.vc.p};
+    if (check_witness && half) throw HipError(CG_ERR_INVALID_ARGUMENT, "one half of the witness map cannot check the witness");
+    // c's share of the quotient lives in the folded l query: the map itself needs C·w only in the coefficient arrangement
+    const int nvec = (coset_values && !check_witness) ? 2 : 3;
+    wm29_products(dom, A, B, C, dA, dB, dC, buf, w_canon, M, m, l, st, nvec, half);
+    if (check_witness) wm29_queue_check(dom, buf, m, st);
     if (coset_values && strided) {
         // a shard's own coset points only (Wm29Strided): two transforms of size D, two of size d
         const Wm29Strided& S = *strided;

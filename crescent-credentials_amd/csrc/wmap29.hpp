@@ -45,18 +45,31 @@ struct Csr29 {     // the matrices' coefficient dictionary in R' form (index arr
     void build(const DevCsr& m, hipStream_t st);
 };
 
+// Witness check (cg_check_witness, CG_FLAG_CHECK_WITNESS): the verdict of k_sat_check29 over one working set's va / vb / vc.
+// The record is DEVICE memory - the kernel's atomics stay on the device - initialised on the proof's stream in front of the
+// kernel and copied to the page-locked mirror behind it; the host reads the mirror after the stream synchronisation it makes anyway.
+struct SatCheck29 {
+    DevBuf<unsigned long long> rec;        // [0] rows with a·b != c, [1] the smallest such row (~0 while there is none)
+    PinnedBuf<unsigned long long> h_rec;
+    DevBuf<uint32_t> row;                  // a_i ‖ b_i ‖ c_i of row rec[1], canonical plain integers, 3 x 8 words (cg_check_witness only)
+    PinnedBuf<uint32_t> h_row;
+    void alloc() { rec.alloc(2); h_rec.alloc(2); row.alloc(24); h_row.alloc(24); }
+};
+
 struct Wm29Buffers {     // per proof slot
     DevBuf<uint32_t> w29;            // witness in R' form, M x 8 words
     DevBuf<uint32_t> va, vb, vc, vt; // D x 8 words each (vt: ping-pong partner of the bit-reversing stores)
     DevBuf<uint32_t> sp_a, sp_b;     // partial sums of the sliced sparse product, levels alternating (sp_cap x 8 words)
     uint32_t sp_cap = 0;
     PinnedBuf<uint32_t> h_bad_input; // host memory; a kernel sets it to 1 when a witness element is not a canonical field element
+    SatCheck29 sat;                  // (56 + 96 bytes: left out of device_bytes)
     // sparse_scratch: the largest DevCsr::sell_scratch of the matrices this working set will serve
     void alloc(uint64_t M, uint64_t D, uint32_t sparse_scratch) {
         w29.alloc(M * 8); va.alloc(D * 8); vb.alloc(D * 8); vc.alloc(D * 8); vt.alloc(D * 8);
         sp_cap = sparse_scratch;
         sp_a.alloc((size_t)(sparse_scratch ? sparse_scratch : 1) * 8); sp_b.alloc((size_t)(sparse_scratch ? sparse_scratch : 1) * 8);
         h_bad_input.alloc(1);
+        sat.alloc();
     }
     uint64_t device_bytes() const { return w29.bytes() + va.bytes() + vb.bytes() + vc.bytes() + vt.bytes() + sp_a.bytes() + sp_b.bytes(); }
 };
@@ -84,7 +97,14 @@ struct Ntt29Unit {
 // q_j of the shard's points j = rank + k·2^logs, k < d, in the order of k.
 void wm29_run(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const DevCsr& C, const Csr29& dA, const Csr29& dB,
               const Csr29& dC, Wm29Buffers& buf, const Fr* w_canon, uint64_t M, uint64_t m, uint64_t l, Fr* h_out,
-              hipStream_t st, bool coset_values, const Wm29Strided* strided = nullptr, int half = 0);
+              hipStream_t st, bool coset_values, const Wm29Strided* strided = nullptr, int half = 0, bool check_witness = false);
+// check_witness (never with `half`, which sees one matrix only): all three sparse products are formed - with coset_values C·w
+// is the one the map itself skips - and the check of every row i < m is queued between them and the first transform (the
+// transforms overwrite va / vb in place); buf.sat.h_rec holds the verdict once the caller has synchronised st.
+// The check alone (cg_check_witness): the three products, the check, and the three values of the first failing row into
+// buf.sat.h_row.  Queues on st and does not wait.
+void wm29_check(const Wm29Domain& dom, const DevCsr& A, const DevCsr& B, const DevCsr& C, const Csr29& dA, const Csr29& dB, const Csr29& dC,
+                Wm29Buffers& buf, const Fr* w_canon, uint64_t M, uint64_t m, uint64_t l, hipStream_t st);
 // half (coset_values only, no `strided`): 1 = the a side alone, vinv·a(g·ω^j); 2 = the b side alone, b(g·ω^j) - D plain
 // canonical integers each, natural order, from ONE sparse product and TWO transforms: the two sides are independent until
 // the pointwise product, so two GPUs can compute one each (cg_witness_map_coset_half).  q_j = side1_j · side2_j:

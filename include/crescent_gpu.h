@@ -45,7 +45,7 @@ typedef enum cg_status {
     CG_ERR_POLY_DEGREE_TOO_LARGE = -5, /* SynthesisError::PolynomialDegreeTooLarge, r1cs_to_qap.rs:156-157 */
     CG_ERR_MALFORMED_KEY = -6,        /* query lengths inconsistent with the circuit (SynthesisError::MalformedVerifyingKey analogue) */
     CG_ERR_PARSE = -7,                /* .r1cs / serialized key parse failure */
-    CG_ERR_UNSATISFIED = -8           /* witness does not satisfy the R1CS (debug check only) */
+    CG_ERR_UNSATISFIED = -8           /* witness does not satisfy the R1CS (cg_check_witness, CG_FLAG_CHECK_WITNESS) */
 } cg_status;
 
 enum { CG_FORM_CANONICAL = 0, CG_FORM_MONTGOMERY = 1 };
@@ -158,7 +158,19 @@ enum {
      * rate is untouched.  Costs a latency slot's memory each (cg_ctx_info.lone_slot_bytes is their sum; a device without room
      * for them does without) and no stream: they run on streams of the last one-stream slots.  A call that asks for cg_timings
      * always runs on a one-stream slot: its phases are then stand-alone durations that add up.  This flag leaves them out. */
-    CG_FLAG_NO_LONE_SLOT = 128
+    CG_FLAG_NO_LONE_SLOT = 128,
+    /* Check every witness before it is proved (off by default, as the reference's check is a debug assertion in release
+     * builds: forks/groth16/src/prover.rs:197).  Every call that runs the sparse products on this context - cg_prove,
+     * cg_prove_dev, cg_prove_partial, cg_prove_partial_q_begin + cg_partial_witness_map_coset, cg_witness_map,
+     * cg_witness_map_coset - also forms C·w (over the folded key that is the third product it otherwise skips) and queues
+     * cg_check_witness's kernel between the products and the first transform.  A witness that fails a constraint: the call
+     * returns CG_ERR_UNSATISFIED (cg_last_error names the first failing constraint and their number), writes nothing to
+     * proof_out / out_partials (the output vector of a witness-map call is then unspecified), and gives its slot back as
+     * after any other failure.  The verdict is
+     * read after the synchronisation the call makes anyway.  NOT checked: the _q forms (cg_prove_partial_q, _q_finish,
+     * _q_finish2), whose h scalars come from outside, and the _half forms, which see one matrix only.
+     * With CG_FLAG_H_SCALARS_EXTERNAL (no matrices on the context) the load is CG_ERR_INVALID_ARGUMENT. */
+    CG_FLAG_CHECK_WITNESS = 256
 };
 
 /* Per-phase wall/GPU times of one cg_prove call, mirroring the reference's `print-trace` phases
@@ -230,6 +242,28 @@ int cg_prove(cg_ctx* ctx, const uint8_t* full_assignment, const uint8_t r[32], c
  * (d_full_assignment is a device pointer, num_variables x 32 B canonical). */
 int cg_prove_dev(cg_ctx* ctx, const void* d_full_assignment, const uint8_t r[32], const uint8_t s[32],
                  uint8_t proof_out[256], cg_timings* timings);
+
+/* Does this assignment satisfy the R1CS, and if not, which constraint fails first?
+ * Replaces: `cs.is_satisfied()` / `cs.which_is_unsatisfied()` in the circom builder
+ *           (forks/circom-compat/src/circom/builder.rs:82-94) and `debug_assert!(cs.is_satisfied())`
+ *           (forks/groth16/src/prover.rs:197): <A_i,w>·<B_i,w> = <C_i,w> for every constraint i < num_constraints.
+ * The three sparse products and one pass over their results on the GPU; takes one of the context's proof slots like a
+ * proof, so it may be called from any thread next to proofs in flight.  Works on whole and sharded contexts, over both
+ * key layouts, and in both phases of a staged load.
+ * Returns CG_OK (satisfied; report->n_unsatisfied = 0), CG_ERR_UNSATISFIED (report filled; cg_last_error says
+ * "constraint <i> of <m> is not satisfied (<n> in all)"), CG_ERR_INVALID_ARGUMENT for an assignment element >= the
+ * scalar field modulus (as cg_prove) and on a CG_FLAG_H_SCALARS_EXTERNAL context (it holds no matrices).
+ * report may be NULL. */
+typedef struct cg_witness_report {
+    uint64_t n_unsatisfied;      /* constraints with <A_i,w>·<B_i,w> != <C_i,w>; 0 = satisfied */
+    uint64_t first_unsatisfied;  /* smallest such i (what which_is_unsatisfied names); undefined when n_unsatisfied == 0 */
+    uint8_t  a[32];              /* <A_i,w> of that row, 32-byte little-endian canonical */
+    uint8_t  b[32];              /* <B_i,w> */
+    uint8_t  c[32];              /* <C_i,w> */
+    float    check_ms;           /* HIP-event time of the products + the check */
+    int32_t  reserved[7];
+} cg_witness_report;
+int cg_check_witness(cg_ctx* ctx, const void* full_assignment, int assignment_on_device, cg_witness_report* report);
 
 /* Page-locked host memory for assignments.
  * Replaces: the allocation behind `full_assignment: &[E::ScalarField]` (forks/groth16/src/prover.rs:33; built as
@@ -390,6 +424,8 @@ int cg_qap_load(cg_qap_ctx** out, const cg_csr abc[3], uint64_t num_inputs, uint
                 uint64_t num_variables, int32_t device /* -1 = current */);
 int cg_qap_witness_map(cg_qap_ctx* ctx, const void* full_assignment, int assignment_on_device, void* h_out,
                        int h_on_device);
+/* cg_check_witness on the key-less handle: where the reference's own check sits (the circom builder, before any key). */
+int cg_qap_check_witness(cg_qap_ctx* ctx, const void* full_assignment, int assignment_on_device, cg_witness_report* report);
 uint64_t cg_qap_domain_size(const cg_qap_ctx* ctx);
 void cg_qap_free(cg_qap_ctx* ctx);
 

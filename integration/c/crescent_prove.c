@@ -165,7 +165,7 @@ int main(int argc, char** argv) {
     const char* credtype = "jwt";
     const char* aux = NULL;
     uint8_t r[32], s[32];
-    int have_rs = 0, bad = argc < 5, sync_load = 0, timings_json = 0, verify = 0;
+    int have_rs = 0, bad = argc < 5, sync_load = 0, timings_json = 0, verify = 0, check_witness = 0;
     for (int i = 5; i < argc && !bad; ++i) {
         if (!strcmp(argv[i], "--rs") && i + 2 < argc) {
             if (!hex_scalar(argv[i + 1], r) || !hex_scalar(argv[i + 2], s)) { fprintf(stderr, "--rs: need hex values below the scalar modulus\n"); return 2; }
@@ -175,11 +175,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--sync-load")) sync_load = 1;
         else if (!strcmp(argv[i], "--timings-json")) timings_json = 1;
         else if (!strcmp(argv[i], "--verify")) verify = 1;
+        else if (!strcmp(argv[i], "--check-witness")) check_witness = 1;
         else bad = 1;
     }
     if (bad) {
         fprintf(stderr, "usage: %s main_c.r1cs prover_params.bin witness.bin client_state.bin [--rs r_hex s_hex] [--credtype jwt|mdl] [--aux json] "
-                        "[--sync-load] [--timings-json] [--verify]\n", argv[0]);
+                        "[--sync-load] [--timings-json] [--verify] [--check-witness]\n", argv[0]);
         return 2;
     }
     if (!have_rs && (!random_scalar(r) || !random_scalar(s))) {
@@ -232,13 +233,32 @@ int main(int argc, char** argv) {
     memset(&opt, 0, sizeof opt);
     opt.device = -1;
     opt.flags = sync_load ? 0 : CG_FLAG_STAGED_LOAD;
+    /* the circom builder's `cs.is_satisfied()` (builder.rs:82-94), on the GPU in front of the proof's transforms */
+    if (check_witness) opt.flags |= CG_FLAG_CHECK_WITNESS;
     if (cg_circuit_load(&ctx, &ppv.pk, abc, hdr.num_inputs, hdr.n_constraints, hdr.num_variables, &opt) != CG_OK) return die("cg_circuit_load");
     double t1 = now_ms();
 
     /* "Groth16 prove" (lib.rs:281-283): Groth16::prove(pk, circuit, rng) */
     uint8_t proof[256];
     cg_timings tm;
-    if (cg_prove(ctx, witness, r, s, proof, &tm) != CG_OK) return die("cg_prove");
+    const int prc = cg_prove(ctx, witness, r, s, proof, &tm);
+    if (prc == CG_ERR_UNSATISFIED) {
+        /* which_is_unsatisfied (builder.rs:86-92): the row and its three inner products, from the check called on its own */
+        fprintf(stderr, "crescent_prove: cg_prove: %s; no client state written\n", cg_last_error());
+        cg_witness_report rep;
+        if (cg_check_witness(ctx, witness, 0, &rep) == CG_ERR_UNSATISFIED) {
+            fprintf(stderr, "unsatisfied constraint %llu:", (unsigned long long)rep.first_unsatisfied);
+            const uint8_t* v[3] = {rep.a, rep.b, rep.c};
+            for (int k = 0; k < 3; ++k) {
+                fprintf(stderr, " %c = 0x", "abc"[k]);
+                for (int i = 31; i >= 0; --i) fprintf(stderr, "%02x", v[k][i]);
+            }
+            fprintf(stderr, "\n");
+        }
+        cg_circuit_free(ctx);
+        return 1;
+    }
+    if (prc != CG_OK) return die("cg_prove");
     double t2 = now_ms();
     cg_ctx_info info;
     if (cg_ctx_get_info(ctx, &info) != CG_OK) return die("cg_ctx_get_info");

@@ -81,6 +81,7 @@ fn map_err(rc: i32) -> SynthesisError {
     match rc {
         sys::CG_ERR_POLY_DEGREE_TOO_LARGE => SynthesisError::PolynomialDegreeTooLarge, // r1cs_to_qap.rs:156-157
         sys::CG_ERR_MALFORMED_KEY => SynthesisError::MalformedVerifyingKey,
+        sys::CG_ERR_UNSATISFIED => SynthesisError::Unsatisfiable, // a context loaded with CG_FLAG_CHECK_WITNESS
         _ => SynthesisError::AssignmentMissing, // no twin in SynthesisError; the message is on stderr
     }
 }
@@ -414,6 +415,23 @@ impl GpuCircuit {
             return Err(map_err(rc));
         }
         Ok(t)
+    }
+
+    /// `cs.is_satisfied()` / `cs.which_is_unsatisfied()` (forks/circom-compat/src/circom/builder.rs:82-94; the debug assertion
+    /// of forks/groth16/src/prover.rs:197) on the GPU (`cg_check_witness`): `Ok(None)` = every constraint holds, `Ok(Some(report))`
+    /// = `report.first_unsatisfied` is the first of `report.n_unsatisfied` failing constraints and `a`, `b`, `c` its three inner
+    /// products.  A context loaded with `sys::CG_FLAG_CHECK_WITNESS` runs the same check inside every `create_proof`.
+    pub fn check_witness(&self, full_assignment: &[Fr]) -> Result<Option<sys::cg_witness_report>, SynthesisError> {
+        if full_assignment.len() != self.num_variables {
+            return Err(SynthesisError::AssignmentMissing);
+        }
+        let w = canonical_bytes(full_assignment);
+        let mut rep = sys::cg_witness_report::default();
+        match unsafe { sys::cg_check_witness(self.ctx, w.as_ptr() as *const _, 0, &mut rep) } {
+            0 => Ok(None),
+            sys::CG_ERR_UNSATISFIED => Ok(Some(rep)),
+            rc => Err(map_err(rc)),
+        }
     }
 
     /// What the circuit occupies on the GPU and how its MSMs are configured (`cg_ctx_get_info`).

@@ -12,8 +12,10 @@ pub const CG_FLAG_CONTIGUOUS_H_SHARDS: i32 = 16;
 pub const CG_FLAG_H_SCALARS_EXTERNAL: i32 = 32;
 pub const CG_FLAG_STAGED_LOAD: i32 = 64;
 pub const CG_FLAG_NO_LONE_SLOT: i32 = 128;
+pub const CG_FLAG_CHECK_WITNESS: i32 = 256;
 pub const CG_ERR_POLY_DEGREE_TOO_LARGE: c_int = -5;
 pub const CG_ERR_MALFORMED_KEY: c_int = -6;
+pub const CG_ERR_UNSATISFIED: c_int = -8;
 
 #[repr(C)]
 pub struct cg_proving_key {
@@ -130,6 +132,19 @@ pub struct cg_load_timings {
     pub reserved: [i32; 3],
 }
 
+/// `cg_check_witness` / `cg_qap_check_witness`: how many constraints fail, the first of them, its three inner products
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct cg_witness_report {
+    pub n_unsatisfied: u64,
+    pub first_unsatisfied: u64,
+    pub a: [u8; 32],
+    pub b: [u8; 32],
+    pub c: [u8; 32],
+    pub check_ms: f32,
+    pub reserved: [i32; 7],
+}
+
 pub enum cg_ctx {}
 pub enum cg_partial {}
 pub enum cg_msm_ctx {}
@@ -198,6 +213,13 @@ extern "C" {
         timings: *mut cg_timings,
     ) -> c_int;
     pub fn cg_witness_map(ctx: *mut cg_ctx, full_assignment: *const u8, h_out: *mut u8) -> c_int;
+    // cs.is_satisfied() / which_is_unsatisfied() (builder.rs:82-94, prover.rs:197)
+    pub fn cg_check_witness(
+        ctx: *mut cg_ctx,
+        full_assignment: *const c_void,
+        assignment_on_device: c_int,
+        report: *mut cg_witness_report,
+    ) -> c_int;
     // the same in two calls: the l, a, b1, b2 sums start at once, the h share follows the slice
     pub fn cg_prove_partial_q_begin(
         ctx: *mut cg_ctx,
@@ -248,6 +270,12 @@ extern "C" {
         assignment_on_device: c_int,
         h_out: *mut c_void,
         h_on_device: c_int,
+    ) -> c_int;
+    pub fn cg_qap_check_witness(
+        ctx: *mut cg_qap_ctx,
+        full_assignment: *const c_void,
+        assignment_on_device: c_int,
+        report: *mut cg_witness_report,
     ) -> c_int;
     pub fn cg_qap_domain_size(ctx: *const cg_qap_ctx) -> u64;
     pub fn cg_qap_free(ctx: *mut cg_qap_ctx);

@@ -317,8 +317,29 @@ def check_signed():
     assert inv["zzz"][0] + 1 >= 0 and inv["zzz"][1] + 1 < 3
 
 
+def check_sat_row():
+    """csrc/satcheck.hpp sat_row_residue: canonical(normalize(sub<7,1>(mul(A, B), C))) for packed operands below 2^256."""
+    packed = 2.0 ** 256 / (2.0 ** 261 / RN)            # 2^256 in units of N: what the 32-byte form can hold
+    assert packed < 5.3
+    A = B(packed, 1.0)                                  # unpack29: normalised
+    col_ok([(A.L, A.L)], 1)
+    p = B(A.V * A.V / RN + 1, 1.0)                      # mul(A, B) < A·B/R' + N
+    assert p.V < 1.17
+    K, T = 7, 1
+    assert A.V < K - 1 and A.L <= T                     # sub<K,T>: C normalised and below (K-1)·N
+    d = B(p.V + K, 3.0)                                 # limb-wise a + (KN boosted by 2^29) - c, before normalize
+    assert d.V - packed > 0                             # the difference itself stays positive: 7N - C > 1.7N
+    dn = B(d.V, 1.0)
+    col_ok([(dn.L, 1.0)], 1)                            # mul(d, R' mod N); limb 8 of d: 8.17N / 2^232 < 2^26
+    assert d.V * 2.0 ** 261 / RN / 2.0 ** 232 < 2.0 ** 26
+    r = B(dn.V * 1.0 / RN + 1, 1.0)
+    assert r.V < 2.0                                    # cond_sub_n's precondition: the result is the value in [0, N)
+    print("Fr   sat_row    packed < %.2f N, a·b < %.2f N, difference < %.2f N, before cond_sub_n < %.3f N  ok" % (packed, p.V, d.V, r.V))
+
+
 if __name__ == "__main__":
     check_signed()
+    check_sat_row()
     # invariant of stored accumulators (values in units of N) and the K constants of curve29.hpp
     INV = dict(x=13.0, y=8.0, z=3.0)
     KC = dict(KX=14, KY=9, K1=4, K2=6)
