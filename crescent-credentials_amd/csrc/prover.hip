@@ -376,32 +376,6 @@ struct CallGuard {
     CallGuard& operator=(const CallGuard&) = delete;
     ~CallGuard() { if (c) c->calls_inside.fetch_sub(1, std::memory_order_acq_rel); }
 };
-struct UploadGuard {
-    cg_ctx* c = nullptr;
-    Upload* u = nullptr;
-    UploadGuard() = default;
-    UploadGuard(const UploadGuard&) = delete;
-    UploadGuard& operator=(const UploadGuard&) = delete;
-    void take(cg_ctx* ctx) { c = ctx; u = ctx->acquire_upload(); }
-    ~UploadGuard() {
-        if (!u) return;
-        (void)hipStreamSynchronize(u->st);      // a failed call may leave its copy in flight
-        c->release_upload(u);
-    }
-};
-struct SlotGuard {
-    cg_ctx* c;
-    ProofSlot* s;
-    int exceptions;
-    explicit SlotGuard(cg_ctx* ctx, bool may_run_alone = false) : c(ctx), s(ctx->acquire(may_run_alone)), exceptions(std::uncaught_exceptions()) {}
-    ~SlotGuard() {
-        // a failure part-way through a proof may leave kernels queued on the slot's streams: drain them before the
-        // working set is handed to the next proof
-        if (std::uncaught_exceptions() > exceptions)
-            for (auto st : s->st) if (st) (void)hipStreamSynchronize(st);
-        c->release(s);
-    }
-};
 
 namespace cg {
 int translate_current_exception() {
@@ -1037,9 +1011,11 @@ extern "C" void cg_circuit_free(cg_ctx* ctx) {
 // witness map on stream st: w_mont must be ready; result h (canonical, natural order) in c->h_canon
 // (LibsnarkReduction::witness_map_from_matrices, r1cs_to_qap.rs:150-213)
 // ---------------------------------------------------------------------------------------------
-static void run_witness_map(cg_ctx* c, ProofSlot* S, const Fr* w_canon_dev, hipStream_t st, bool coset_values) {
+// half (coset values only): 0 = the map, 1 / 2 = one side of it (wmap29.hpp).  own_share: a strided shard transforms its own
+// coset points only; false = the values of the whole domain, whatever this context's share is
+static void run_witness_map(cg_ctx* c, ProofSlot* S, const Fr* w_canon_dev, hipStream_t st, bool coset_values, int half = 0, bool own_share = true) {
     wm29_run(c->wdom, c->A, c->B, c->C, c->dA, c->dB, c->dC, S->wm, w_canon_dev, c->M, c->m, c->l, S->h_canon.p, st, coset_values,
-             coset_values && c->h_strided ? &c->wstr : nullptr, 0, c->check_witness);
+             coset_values && own_share && c->h_strided ? &c->wstr : nullptr, half, c->check_witness && !half);
 }
 
 // CG_FLAG_CHECK_WITNESS: the verdict of the check a witness map queued, read where h_bad_input is read - after the call's
@@ -1048,6 +1024,14 @@ static int unsatisfied(const cg_ctx* c, const ProofSlot* S) {
     const unsigned long long n = S->wm.sat.h_rec.p[0], first = S->wm.sat.h_rec.p[1];
     if (!n) return CG_OK;
     return fail(CG_ERR_UNSATISFIED, "constraint %llu of %llu is not satisfied (%llu in all)", first, (unsigned long long)c->m, n);
+}
+// What the slot's input check, and the witness check if this call's witness map queued one (`checked`), found; read after
+// the call's own synchronisation.  with_slice: caller-supplied h scalars were checked with the assignment.
+static int input_verdict(const cg_ctx* c, const ProofSlot* S, bool with_slice, bool checked) {
+    if (S->wm.h_bad_input.p[0])
+        return fail(CG_ERR_INVALID_ARGUMENT, with_slice ? "full_assignment or the h-scalar slice holds a value >= the scalar field modulus"
+                                                        : "full_assignment holds a value >= the scalar field modulus");
+    return checked ? unsatisfied(c, S) : CG_OK;
 }
 
 // x >= r for any of n scalars -> *bad = 1 (the witness map's own input check, for proofs that skip the witness map)
@@ -1069,20 +1053,45 @@ __global__ void __launch_bounds__(256) k_shard_major(const Fr* __restrict__ in, 
     out[i] = in[p + k * (uint64_t)count];
 }
 
-// The scalars of this context's share of the h MSM, on stream st: out of the witness map (h_canon: coefficients of h, or the
-// coset values vinv·a·b for a folded key), or - q_dev given - the caller's, with the input check the witness map would
-// have made (canonical assignment) and the same check of the slice.
-static const Fr* witness_map_or_check(cg_ctx* c, ProofSlot* S, const Fr* w_dev, const Fr* q_dev, hipStream_t st) {
-    if (!q_dev) {
-        run_witness_map(c, S, w_dev, st, c->folded);
-        return S->h_canon.p + c->rh.lo;
-    }
-    S->wm.h_bad_input.p[0] = 0;
+// This shard's h scalars as a caller supplies them (cg_prove_partial_q, cg_prove_partial_q_finish) - or, with `b`, the two
+// sides' slices whose products they are (_finish2) - in device memory, or in host memory (both, then)
+struct SuppliedH {
+    const void* q = nullptr;
+    const void* b = nullptr;
+    bool on_device = false;
+};
+// Queues on the slot's stream 0 what makes them the h MSM's operand: the copy of a host slice to this shard's place in the
+// slot's h vector, the input check the witness map would have made (canonical assignment) and the same check of what
+// arrived instead of it.  -> where eh.digits reads them
+static const Fr* supplied_h_scalars(cg_ctx* c, ProofSlot* S, const Fr* w_dev, const SuppliedH& h) {
+    hipStream_t s0 = S->st[0];
     const uint64_t nq = c->rh.hi - c->rh.lo;
-    k_flag_non_canonical<<<ceil_div(c->M, 256), 256, 0, st>>>(w_dev, c->M, S->wm.h_bad_input.dev());
-    if (nq) k_flag_non_canonical<<<ceil_div(nq, 256), 256, 0, st>>>(q_dev, nq, S->wm.h_bad_input.dev());
+    Fr* const own_q = c->external_q ? S->h_canon.p : S->h_canon.p + c->rh.lo;
+    auto landed = [&](const void* slice, Fr* dst) {
+        if (h.on_device || !nq) return (const Fr*)slice;
+        CG_HIP(hipMemcpyAsync(dst, slice, nq * 32, hipMemcpyHostToDevice, s0));
+        return (const Fr*)dst;
+    };
+    const Fr* q_dev = landed(h.q, own_q);
+    S->wm.h_bad_input.p[0] = 0;
+    k_flag_non_canonical<<<ceil_div(c->M, 256), 256, 0, s0>>>(w_dev, c->M, S->wm.h_bad_input.dev());
+    if (h.b && nq) {
+        if (!h.on_device && S->q2.n < nq) S->q2.alloc(nq);
+        fr_mul_plain29(q_dev, landed(h.b, S->q2.p), own_q, nq, S->wm.h_bad_input.dev(), s0);    // q_j = (vinv·a_j)·b_j; checks both operands
+        q_dev = own_q;
+    } else if (nq) {
+        k_flag_non_canonical<<<ceil_div(nq, 256), 256, 0, s0>>>(q_dev, nq, S->wm.h_bad_input.dev());
+    }
     CG_KERNEL_CHECK();
     return q_dev;
+}
+
+// The scalars of this context's share of the h MSM, on the slot's stream 0: out of the witness map (h_canon: coefficients
+// of h, or the coset values vinv·a·b for a folded key), or the caller's
+static const Fr* witness_map_or_check(cg_ctx* c, ProofSlot* S, const Fr* w_dev, const SuppliedH* supplied) {
+    if (supplied) return supplied_h_scalars(c, S, w_dev, *supplied);
+    run_witness_map(c, S, w_dev, S->st[0], c->folded);
+    return S->h_canon.p + c->rh.lo;
 }
 
 struct Partials {
@@ -1104,8 +1113,7 @@ static float ev_ms(hipEvent_t a, hipEvent_t b) {
 // between (hipEventQuery is a read of the completion signal): a 250 us nap costs a proof 0.3 % of its time in flight and
 // nothing of the GPU's, which the other proofs keep busy (wait_sleeping: shorter naps early on, for small circuits).  A
 // latency context (one proof at a time: the wait IS the latency) keeps the spinning synchronise.  CG_FLAG_SPIN_WAIT makes
-// every caller of a context spin.
-static bool spin_wait(const cg_ctx* c) { return c->spin_wait; }
+// every caller of a context spin (cg_ctx::spin_wait).
 // Polls `ev` until it is done: spinning for the first 200 us (a small circuit's proof is over by then), after that napping
 // an eighth of the time already waited, at most `max_nap_us` - the overshoot stays below an eighth of the wait whatever
 // the circuit's size, and a long wait costs next to no CPU.
@@ -1126,8 +1134,14 @@ static void wait_sleeping(hipEvent_t ev, unsigned max_nap_us) {
 
 // Waits for what THIS proof queued on its slot's streams - not for the streams themselves: a lone slot runs on streams that
 // belong to one-stream slots, and a proof of theirs that queued behind this one (the context filled up meanwhile) would be
-// waited for as well: +77 ms on the two proofs that open a burst, measured.  The calling thread spins in the runtime.
-static void wait_for_slot(ProofSlot* S) {
+// waited for as well: +77 ms on the two proofs that open a burst, measured.  The calling thread spins in the runtime, except
+// on a one-stream slot of a context whose callers sleep (see above).
+static void wait_for_slot(const cg_ctx* c, ProofSlot* S) {
+    if (S->one_stream && !c->spin_wait) {
+        CG_HIP(hipEventRecord(S->ev_done, S->st[0]));
+        wait_sleeping(S->ev_done, 250);            // a proof with fifteen others in flight takes ~80 ms
+        return;
+    }
     for (int i = 0; i < 5; ++i)
         if (i == 0 || S->st[i] != S->st[0]) CG_HIP(hipEventRecord(S->ev_fin[i], S->st[i]));
     for (int i = 0; i < 5; ++i)
@@ -1141,11 +1155,10 @@ static void wait_for_slot(ProofSlot* S) {
 // (profiles/r03_a_host_witness.txt).  Page-locked source (cg_host_alloc / cg_host_register): one DMA at PCIe speed;
 // pageable source: staged by the runtime through its own pinned buffers, inside the call.  Returns the copy's ms (timed).
 static float upload_assignment(cg_ctx* c, Upload* u, const void* host_assignment, bool timed) {
-    CG_HIP(hipSetDevice(c->device));
     if (timed) CG_HIP(hipEventRecord(u->ev[0], u->st));
     CG_HIP(hipMemcpyAsync(u->w.p, host_assignment, c->M * 32, hipMemcpyHostToDevice, u->st));
     if (timed) CG_HIP(hipEventRecord(u->ev[1], u->st));
-    if (spin_wait(c) || c->latency) {
+    if (c->spin_wait || c->latency) {
         CG_HIP(hipStreamSynchronize(u->st));
     } else {
         CG_HIP(hipEventRecord(u->ev_done, u->st));
@@ -1154,118 +1167,204 @@ static float upload_assignment(cg_ctx* c, Upload* u, const void* host_assignment
     return timed ? ev_ms(u->ev[0], u->ev[1]) : 0.f;
 }
 
-// w_dev: the assignment in this context's device memory (the caller's own buffer, or an Upload's)
-// q_dev (optional): this shard's h scalars, supplied by the caller (cg_prove_partial_q) - the witness map is skipped
-static int prove_partial_impl(cg_ctx* c, ProofSlot* S, const Fr* w_dev, bool skip_b1, Partials& P, cg_timings* tm,
-                              const std::function<void()>* while_gpu_runs = nullptr, const Fr* q_dev = nullptr) {
-    CG_HIP(hipSetDevice(c->device));
-    auto t0 = std::chrono::steady_clock::now();
-    const uint64_t M = c->M, l = c->l;
-    (void)M;
-    hipStream_t s0 = S->st[0];
-    // assignment-driven MSMs: operands (prover.rs:70-74, 84-89, 265-266)
-    //   l: l_query[i] x w[l + i];  a, b1, b2: query[1 + i] x w[1 + i]
-    const Fr* w_l = w_dev + (c->folded ? 0 : l) + c->rl.lo;          // folded l query: one base per wire
-    const uint64_t n_l = c->rl.hi - c->rl.lo, n_a = c->ra.hi - c->ra.lo;
-    const Fr* w_a = w_dev + 1 + c->ra.lo;
-    // b1 and b2 take the same scalars against bases that vanish together: with equal windows the grouped entry list of
-    // one IS the other's, so the G2 MSM skips its own grouping (five launches, ~0.9 % of a proof's instructions)
-    static const bool no_share = CG_TUNE_ENV("NO_SHARE_B") != nullptr;        // A/B aid (tuning builds)
-    // tuning builds: KNOCK is a mask of parts of a proof to leave out (1 l, 2 a, 4 b1, 8 b2, 16 the witness map after a slot's
-    // first proof, 32 h) - the proof is wrong, the time is what the rest costs in the pipeline (profiles/r05_w_knock_outs.md)
-    static const int knock = [] { const char* e = CG_TUNE_ENV("KNOCK"); return e ? atoi(e) : 0; }();
-    if (knock & 4) skip_b1 = true;
-    if (knock && tm) { memset(tm, 0, sizeof(*tm)); tm = nullptr; }       // an engine left out has no events to read
-    const bool b2_adopts = !skip_b1 && !no_share && c->b_same_identities && S->eb2.can_adopt(S->eb1) && n_a > 0 && !(knock & 8);
-    if (knock && S->one_stream) {
-        if (!(knock & 1)) { S->el.digits(w_l, n_l, s0); S->el.accumulate(s0); }
-        if (!(knock & 2)) { S->ea.digits(w_a, n_a, s0); S->ea.accumulate(s0); }
-        if (!skip_b1) S->eb1.digits(w_a, n_a, s0);
-        if (b2_adopts) S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, s0);
-        if (!skip_b1) S->eb1.accumulate(s0);
-        if (!(knock & 8)) { if (!b2_adopts) S->eb2.digits(w_a, n_a, s0); S->eb2.accumulate(s0); }
-        if (tm) CG_HIP(hipEventRecord(S->ev_t[0], s0));
-        const Fr* h_scalars = (knock & 16) && S->knock_h ? S->knock_h : witness_map_or_check(c, S, w_dev, q_dev, s0);
-        S->knock_h = h_scalars;
-        if (tm) CG_HIP(hipEventRecord(S->ev_t[1], s0));
-        if (!(knock & 32)) { S->eh.digits(h_scalars, c->rh.hi - c->rh.lo, s0); S->eh.accumulate(s0); }
-    } else if (S->one_stream) {
-        // everything on one stream, every MSM grouped and accumulated before the next one starts: the engines share the
-        // slot's scratch (entry lists, segment pieces), which is what a slot's memory mostly is
-        S->el.digits(w_l, n_l, s0); S->el.accumulate(s0);
-        S->ea.digits(w_a, n_a, s0); S->ea.accumulate(s0);
-        if (!skip_b1) S->eb1.digits(w_a, n_a, s0);
-        if (b2_adopts) S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, s0);    // b1's list is still in the scratch ...
-        if (!skip_b1) S->eb1.accumulate(s0);
-        if (!b2_adopts) S->eb2.digits(w_a, n_a, s0);
-        S->eb2.accumulate(s0);                                                         // ... until here
-        if (tm) CG_HIP(hipEventRecord(S->ev_t[0], s0));
-        const Fr* h_scalars = witness_map_or_check(c, S, w_dev, q_dev, s0);
-        if (tm) CG_HIP(hipEventRecord(S->ev_t[1], s0));
-        S->eh.digits(h_scalars, c->rh.hi - c->rh.lo, s0);
-        S->eh.accumulate(s0);
-    } else {
+static const char* const BROKEN_CONTEXT = "a window re-tune ran out of device memory while re-sizing the proof slots: free this context and load the circuit again";
+
+// What an entry point that works on the GPU holds while it does: its place in the count of calls inside the context, the
+// tune gate (shared), the device copy of a host assignment, a proof slot.  Made after the argument checks; a context that
+// cannot prove any more is refused here (CG_ERR_OUT_OF_MEMORY, BROKEN_CONTEXT).
+// may_run_alone: the call may take a lone slot (cg_ctx::acquire) - untimed proofs (a TIMED proof stays on a one-stream slot:
+// its phases are then stand-alone durations that add up); never the witness-map and check entries.
+// in_handle: the frame lives in a cg_partial, from cg_prove_partial_q_begin to the call that ends that proof.
+struct CallFrame {
+    CallGuard inside;                  // first: the count is let go of last, after whatever the call does past release()
+    cg_ctx* const c;
+    const Fr* w_dev = nullptr;         // the assignment in device memory: the caller's own buffer, or the upload's
+    ProofSlot* S = nullptr;
+    float upload_ms = 0.f;             // (timed)
+    CallFrame(cg_ctx* ctx, const void* assignment, bool on_device, bool may_run_alone, bool timed = false, bool handle = false)
+        : inside(ctx), c(ctx), in_handle(handle), exceptions(std::uncaught_exceptions()) {
+        try {
+            if (c->broken) throw HipError(CG_ERR_OUT_OF_MEMORY, BROKEN_CONTEXT);
+            CG_HIP(hipSetDevice(c->device));
+            // a host opens proof k + 1 before it finishes proof k: a handle's frame must not queue behind a writer that waits
+            // for the same host's other handle (TuneGate)
+            if (in_handle) c->tune_mu.lock_shared_passing_waiting_writers();
+            else c->tune_mu.lock_shared();
+            gate_held = true;
+            // a caller that passed the check above can have waited here for another thread's re-tune, and that re-tune can
+            // have failed half-way: the engines of the slots are then cut for the old window against the rebuilt table
+            if (c->broken) throw HipError(CG_ERR_OUT_OF_MEMORY, BROKEN_CONTEXT);
+            w_dev = (const Fr*)assignment;
+            if (!on_device) {          // before the slot: an upload never holds a working set
+                up = c->acquire_upload();
+                upload_ms = upload_assignment(c, up, assignment, timed);
+                w_dev = up->w.p;
+            }
+            S = c->acquire(may_run_alone);
+        } catch (...) {
+            release();
+            throw;
+        }
+    }
+    ~CallFrame() { release(); }
+    // Gives back the slot, then the upload, then the gate; the count of calls inside stays until the frame goes.  A call
+    // does this itself before its re-tune check (which takes the gate exclusively) and its host finish, which need neither.
+    void release() {
+        if (S) {
+            // a failure part-way through a proof may leave kernels queued on the slot's streams, and so do
+            // cg_prove_partial_q_abort and a failed _finish: drain them before the working set is handed to the next proof
+            if (in_handle || std::uncaught_exceptions() > exceptions)
+                for (auto st : S->st) if (st) (void)hipStreamSynchronize(st);
+            c->release(S);
+            S = nullptr;
+        }
+        if (up) {
+            (void)hipStreamSynchronize(up->st);      // a failed call may leave its copy in flight
+            c->release_upload(up);
+            up = nullptr;
+        }
+        if (gate_held) { c->tune_mu.unlock_shared(); gate_held = false; }
+    }
+private:
+    Upload* up = nullptr;
+    bool gate_held = false;
+    const bool in_handle;
+    const int exceptions;
+};
+
+// tuning builds: NO_SHARE_B keeps the G2 MSM's own grouping (A/B aid); KNOCK is a mask of parts of a proof to leave out (1 l,
+// 2 a, 4 b1, 8 b2, 16 the witness map after a slot's first proof, 32 h) - the proof is wrong, the time is what the rest costs
+// in the pipeline (profiles/r05_w_knock_outs.md).  The shipped library has neither: false and 0.
+static bool no_share_b() {
+    static const bool v = CG_TUNE_ENV("NO_SHARE_B") != nullptr;
+    return v;
+}
+static int knock_mask() {
+    static const int v = [] { const char* e = CG_TUNE_ENV("KNOCK"); return e ? atoi(e) : 0; }();
+    return v;
+}
+
+// The four assignment-driven MSMs of one proof on a slot: the ONE place that knows their operands and the order in which
+// their work is queued.  Two phases, because the host queues the h side between them (prove_partial_impl) and the order of
+// its submissions is part of what was measured:
+//   phase 1   one-stream slot: all four MSMs, grouped and accumulated one after another on stream 0.
+//             five-stream slot: streams 1-4 wait for what stream 0 holds; the digits of l, a, b1, b2 on streams 1-4.
+//   phase 2   five-stream slot: the four accumulations (each waits for its own entry count).  one-stream slot: nothing.
+// operands (prover.rs:70-74, 84-89, 265-266):  l: l_query[i] x w[l + i];  a, b1, b2: query[1 + i] x w[1 + i]
+struct Schedule {
+    ProofSlot* const S;
+    const Fr *w_l, *w_a;
+    uint64_t n_l, n_a;
+    bool run_l, run_a, run_b1, run_b2;     // all but b1 (a proof with r = 0 skips it, prover.rs:102-112) run outside KNOCK runs
+    bool b2_adopts;
+    Schedule(const cg_ctx* c, ProofSlot* slot, const Fr* w_dev, bool skip_b1) : S(slot) {
+        w_l = w_dev + (c->folded ? 0 : c->l) + c->rl.lo;          // folded l query: one base per wire
+        w_a = w_dev + 1 + c->ra.lo;
+        n_l = c->rl.hi - c->rl.lo;
+        n_a = c->ra.hi - c->ra.lo;
+        const int knock = knock_mask();
+        run_l = !(knock & 1); run_a = !(knock & 2); run_b1 = !skip_b1 && !(knock & 4); run_b2 = !(knock & 8);
+        // b1 and b2 take the same scalars against bases that vanish together: with equal windows the grouped entry list of
+        // one IS the other's, so the G2 MSM skips its own grouping (five launches, ~0.9 % of a proof's instructions)
+        b2_adopts = run_b1 && run_b2 && !no_share_b() && c->b_same_identities && S->eb2.can_adopt(S->eb1) && n_a > 0;
+    }
+    void phase1() const {
+        hipStream_t s0 = S->st[0];
+        if (S->one_stream) {
+            // every MSM grouped and accumulated before the next one starts: the engines share the slot's scratch (entry
+            // lists, segment pieces), which is what a slot's memory mostly is
+            if (run_l) { S->el.digits(w_l, n_l, s0); S->el.accumulate(s0); }
+            if (run_a) { S->ea.digits(w_a, n_a, s0); S->ea.accumulate(s0); }
+            if (run_b1) S->eb1.digits(w_a, n_a, s0);
+            if (b2_adopts) S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, s0);    // b1's list is still in the scratch ...
+            if (run_b1) S->eb1.accumulate(s0);
+            if (run_b2 && !b2_adopts) S->eb2.digits(w_a, n_a, s0);
+            if (run_b2) S->eb2.accumulate(s0);                                             // ... until here
+            return;
+        }
         CG_HIP(hipEventRecord(S->ev_w, s0));
         for (int i = 1; i < 5; ++i) CG_HIP(hipStreamWaitEvent(S->st[i], S->ev_w, 0));
-        S->el.digits(w_l, n_l, S->st[1]);
-        S->ea.digits(w_a, n_a, S->st[2]);
-        if (!skip_b1) S->eb1.digits(w_a, n_a, S->st[3]);
+        if (run_l) S->el.digits(w_l, n_l, S->st[1]);
+        if (run_a) S->ea.digits(w_a, n_a, S->st[2]);
+        if (run_b1) S->eb1.digits(w_a, n_a, S->st[3]);
         if (b2_adopts) {
             CG_HIP(hipEventRecord(S->ev_b1, S->st[3]));
             CG_HIP(hipStreamWaitEvent(S->st[4], S->ev_b1, 0));
             S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, S->st[4]);
-        } else {
+        } else if (run_b2) {
             S->eb2.digits(w_a, n_a, S->st[4]);
         }
-        // witness map, then h digits, on stream 0
-        if (tm) CG_HIP(hipEventRecord(S->ev_t[0], s0));
-        const Fr* h_scalars = witness_map_or_check(c, S, w_dev, q_dev, s0);
-        if (tm) CG_HIP(hipEventRecord(S->ev_t[1], s0));
-        S->eh.digits(h_scalars, c->rh.hi - c->rh.lo, s0);
-        // second phase (each waits for its own entry count)
-        S->el.accumulate(S->st[1]);
-        S->ea.accumulate(S->st[2]);
-        if (!skip_b1) S->eb1.accumulate(S->st[3]);
-        S->eb2.accumulate(S->st[4]);
-        S->eh.accumulate(s0);
     }
-    if (while_gpu_runs) (*while_gpu_runs)();      // host work that needs no MSM value
-    if (S->one_stream && !spin_wait(c)) {
-        CG_HIP(hipEventRecord(S->ev_done, s0));
-        wait_sleeping(S->ev_done, 250);            // a proof with fifteen others in flight takes ~80 ms
-    } else {
-        wait_for_slot(S);
+    void phase2() const {
+        if (S->one_stream) return;
+        if (run_l) S->el.accumulate(S->st[1]);
+        if (run_a) S->ea.accumulate(S->st[2]);
+        if (run_b1) S->eb1.accumulate(S->st[3]);
+        if (run_b2) S->eb2.accumulate(S->st[4]);
     }
-    if (S->wm.h_bad_input.p[0])
-        return fail(CG_ERR_INVALID_ARGUMENT, q_dev ? "full_assignment or the h-scalar slice holds a value >= the scalar field modulus"
-                                                   : "full_assignment holds a value >= the scalar field modulus");
-    if (c->check_witness && !q_dev)
-        if (int e = unsatisfied(c, S)) return e;
+};
+
+static void snapshot_tune_stats(const cg_ctx* c, const ProofSlot* S, bool skip_b1, TuneStats& ts);
+
+// Waits for what the proof queued on its slot and reads what it left there: the verdict on its input, the five sums, the
+// timings, the digit statistics for the window re-tune.  h_supplied: the h scalars were the caller's - they were checked with
+// the assignment, and no witness map ran that could have checked the witness.  in_one_call: the whole proof was queued by
+// this call, so every field of cg_timings has its events; the two-call form reports the five MSMs and the time since begin.
+static int collect(cg_ctx* c, ProofSlot* S, bool skip_b1, bool h_supplied, bool in_one_call, std::chrono::steady_clock::time_point t0,
+                   Partials& P, cg_timings* tm, TuneStats& ts) {
+    wait_for_slot(c, S);
+    if (int e = input_verdict(c, S, h_supplied, c->check_witness && !h_supplied)) return e;
     P.h = to_affine(S->eh.value());
     P.l = to_affine(S->el.value());
     P.a = to_affine(S->ea.value());
     P.b1 = skip_b1 ? G1Affine::inf() : to_affine(S->eb1.value());
     P.b2 = to_affine(S->eb2.value());
+    if (knock_mask() && tm) { memset(tm, 0, sizeof(*tm)); tm = nullptr; }       // an engine left out has no events to read
     if (tm) {
         memset(tm, 0, sizeof(*tm));
-        tm->witness_map_ms = ev_ms(S->ev_t[0], S->ev_t[1]);
         tm->msm_h_ms = S->eh.ms_total();
         tm->msm_l_ms = S->el.ms_total();
         tm->msm_a_ms = S->ea.ms_total();
         tm->msm_b1_ms = skip_b1 ? 0.f : S->eb1.ms_total();
         tm->msm_b2_ms = S->eb2.ms_total();
-        tm->accum_g1_ms = S->eh.ms_accum() + S->el.ms_accum() + S->ea.ms_accum() + (skip_b1 ? 0.f : S->eb1.ms_accum());
-        tm->accum_g2_ms = S->eb2.ms_accum();
-        tm->sort_ms = S->eh.ms_sort() + S->el.ms_sort() + S->ea.ms_sort() + (skip_b1 ? 0.f : S->eb1.ms_sort()) + S->eb2.ms_sort();
-        tm->entries_g1 = (uint64_t)S->eh.n_entries() + S->el.n_entries() + S->ea.n_entries() + (skip_b1 ? 0 : S->eb1.n_entries());
-        tm->entries_g2 = S->eb2.n_entries();
-        tm->accum_g1_launches = (S->eh.n_entries() != 0) + (S->el.n_entries() != 0) + (S->ea.n_entries() != 0) + (!skip_b1 && S->eb1.n_entries() != 0);
-        tm->accum_g2_launches = S->eb2.n_entries() != 0;
-        tm->msm_g1_pairs = S->eh.n_scalars + S->el.n_scalars + S->ea.n_scalars + (skip_b1 ? 0 : S->eb1.n_scalars);
-        tm->msm_g2_pairs = S->eb2.n_scalars;
-        tm->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (in_one_call) {
+            tm->witness_map_ms = ev_ms(S->ev_t[0], S->ev_t[1]);
+            tm->accum_g1_ms = S->eh.ms_accum() + S->el.ms_accum() + S->ea.ms_accum() + (skip_b1 ? 0.f : S->eb1.ms_accum());
+            tm->accum_g2_ms = S->eb2.ms_accum();
+            tm->sort_ms = S->eh.ms_sort() + S->el.ms_sort() + S->ea.ms_sort() + (skip_b1 ? 0.f : S->eb1.ms_sort()) + S->eb2.ms_sort();
+            tm->entries_g1 = (uint64_t)S->eh.n_entries() + S->el.n_entries() + S->ea.n_entries() + (skip_b1 ? 0 : S->eb1.n_entries());
+            tm->entries_g2 = S->eb2.n_entries();
+            tm->accum_g1_launches = (S->eh.n_entries() != 0) + (S->el.n_entries() != 0) + (S->ea.n_entries() != 0) + (!skip_b1 && S->eb1.n_entries() != 0);
+            tm->accum_g2_launches = S->eb2.n_entries() != 0;
+            tm->msm_g1_pairs = S->eh.n_scalars + S->el.n_scalars + S->ea.n_scalars + (skip_b1 ? 0 : S->eb1.n_scalars);
+            tm->msm_g2_pairs = S->eb2.n_scalars;
+        }
+        tm->total_ms = ms_since(t0);
     }
+    snapshot_tune_stats(c, S, skip_b1, ts);
     return CG_OK;
+}
+
+// One proof's five MSMs on slot S, queued, waited for and read.
+// w_dev: the assignment in this context's device memory (the caller's own buffer, or an Upload's)
+// supplied (optional): this shard's h scalars, supplied by the caller (cg_prove_partial_q) - the witness map is skipped
+static int prove_partial_impl(cg_ctx* c, ProofSlot* S, const Fr* w_dev, bool skip_b1, Partials& P, cg_timings* tm, TuneStats& ts,
+                              const std::function<void()>* while_gpu_runs = nullptr, const SuppliedH* supplied = nullptr) {
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t s0 = S->st[0];
+    const Schedule sch(c, S, w_dev, skip_b1);
+    const int knock = knock_mask();
+    sch.phase1();
+    // the h side on stream 0: the witness map (or the caller's scalars), then the h digits
+    if (tm) CG_HIP(hipEventRecord(S->ev_t[0], s0));
+    const Fr* h_scalars = (knock & 16) && S->knock_h ? S->knock_h : witness_map_or_check(c, S, w_dev, supplied);
+    if (knock & 16) S->knock_h = h_scalars;
+    if (tm) CG_HIP(hipEventRecord(S->ev_t[1], s0));
+    if (!(knock & 32)) S->eh.digits(h_scalars, c->rh.hi - c->rh.lo, s0);
+    sch.phase2();
+    if (!(knock & 32)) S->eh.accumulate(s0);
+    if (while_gpu_runs) (*while_gpu_runs)();      // host work that needs no MSM value
+    return collect(c, S, !sch.run_b1, supplied != nullptr, true, t0, P, tm, ts);
 }
 
 // The scalar multiples of delta that do not depend on the MSM values (prover.rs:76-80,94,104,116): fixed-base, and
@@ -1425,11 +1524,40 @@ static void maybe_retune(cg_ctx* c, const TuneStats& ts) {
     }
 }
 
-static const char* const BROKEN_CONTEXT = "a window re-tune ran out of device memory while re-sizing the proof slots: free this context and load the circuit again";
 static int check_rs(const uint8_t r[32], const uint8_t s[32]) {
     if (!r || !s) return fail(CG_ERR_INVALID_ARGUMENT, "null r/s");
     if (!scalar_is_canonical(r) || !scalar_is_canonical(s)) return fail(CG_ERR_INVALID_ARGUMENT, "r/s not canonical (>= field modulus)");
     return CG_OK;
+}
+
+// One proof on one slot, for every entry point that proves in one call.  s given: the proof itself, 256 bytes at `out` (the
+// multiples of delta are computed while the GPU works); s == nullptr: this shard's five sums, 384 bytes at `out`.
+static int prove_on_slot(cg_ctx* ctx, const void* assignment, bool on_device, const SuppliedH* supplied, const uint8_t r[32], const uint8_t* s,
+                         uint8_t* out, cg_timings* tm) {
+    try {
+        Partials P;
+        DeltaMultiples pre;
+        TuneStats ts;
+        const std::function<void()> overlap = [&]() { pre = delta_multiples(ctx, r, s); };
+        CallFrame f(ctx, assignment, on_device, tm == nullptr, tm != nullptr);
+        if (int e = prove_partial_impl(ctx, f.S, f.w_dev, scalar_is_zero(r), P, tm, ts, s ? &overlap : nullptr, supplied)) return e;
+        if (tm) { tm->upload_ms = f.upload_ms; tm->total_ms += f.upload_ms; }
+        f.release();
+        maybe_retune(ctx, ts);
+        if (!s) {
+            partials_to_bytes(P, out);
+            return CG_OK;
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        assemble_impl(ctx, P, r, s, out, &pre);
+        if (tm) {
+            tm->finish_ms = ms_since(t0);
+            tm->total_ms += tm->finish_ms;
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_exception();
+    }
 }
 
 static int prove_common(cg_ctx* ctx, const void* assignment, bool on_device, const uint8_t r[32], const uint8_t s[32],
@@ -1437,45 +1565,7 @@ static int prove_common(cg_ctx* ctx, const void* assignment, bool on_device, con
     if (!ctx || !assignment || !proof_out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     if (int e = check_rs(r, s)) return e;
     if (ctx->shard_count != 1) return fail(CG_ERR_INVALID_ARGUMENT, "context is a shard; use cg_prove_partial + cg_assemble");
-    if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
-    CallGuard inside(ctx);
-    try {
-        Partials P;
-        DeltaMultiples pre;
-        TuneStats ts;
-        const std::function<void()> overlap = [&]() { pre = delta_multiples(ctx, r, s); };
-        int e;
-        {
-            std::shared_lock<TuneGate> tl(ctx->tune_mu);
-            // a caller that passed the check above can have waited here for another thread's re-tune, and that re-tune can
-            // have failed half-way: the engines of the slots are then cut for the old window against the rebuilt table
-            if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
-            UploadGuard up;                       // declared before the slot: released after it
-            float upload_ms = 0.f;
-            const Fr* w_dev = (const Fr*)assignment;
-            if (!on_device) {
-                up.take(ctx);
-                upload_ms = upload_assignment(ctx, up.u, assignment, tm != nullptr);
-                w_dev = up.u->w.p;
-            }
-            // (a TIMED proof stays on a one-stream slot: its phases are then stand-alone durations that add up)
-            SlotGuard g(ctx, tm == nullptr);
-            e = prove_partial_impl(ctx, g.s, w_dev, scalar_is_zero(r), P, tm, &overlap);
-            if (!e) snapshot_tune_stats(ctx, g.s, scalar_is_zero(r), ts);
-            if (!e && tm) { tm->upload_ms = upload_ms; tm->total_ms += upload_ms; }
-        }
-        if (e) return e;
-        maybe_retune(ctx, ts);
-        auto t0 = std::chrono::steady_clock::now();
-        assemble_impl(ctx, P, r, s, proof_out, &pre);
-        if (tm) {
-            tm->finish_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            tm->total_ms += tm->finish_ms;
-        }
-        return CG_OK;
-    } catch (...) {
-        return translate_exception();
-    }
+    return prove_on_slot(ctx, assignment, on_device, nullptr, r, s, proof_out, tm);
 }
 
 extern "C" int cg_prove(cg_ctx* ctx, const uint8_t* full_assignment, const uint8_t r[32], const uint8_t s[32],
@@ -1495,46 +1585,8 @@ static int prove_partial_common(cg_ctx* ctx, const void* full_assignment, int as
         return fail(CG_ERR_INVALID_ARGUMENT, "cg_prove_partial_q needs a sharded context over the folded key");
     if (!with_q && ctx->external_q)
         return fail(CG_ERR_INVALID_ARGUMENT, "context loaded with CG_FLAG_H_SCALARS_EXTERNAL: its h scalars must be supplied (cg_prove_partial_q)");
-    if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
-    CallGuard inside(ctx);
-    try {
-        Partials P;
-        TuneStats ts;
-        int e;
-        {
-            std::shared_lock<TuneGate> tl(ctx->tune_mu);
-            if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);     // as in prove_common
-            UploadGuard up;
-            float upload_ms = 0.f;
-            const Fr* w_dev = (const Fr*)full_assignment;
-            if (!assignment_on_device) {
-                up.take(ctx);
-                upload_ms = upload_assignment(ctx, up.u, full_assignment, timings != nullptr);
-                w_dev = up.u->w.p;
-            }
-            SlotGuard g(ctx, timings == nullptr);        // (as prove_common: a shard of a proof that arrives alone, untimed)
-            const Fr* q_dev = nullptr;
-            if (with_q) {
-                q_dev = (const Fr*)q_slice;
-                const uint64_t nq = ctx->rh.hi - ctx->rh.lo;
-                if (!q_on_device && nq) {        // lands in the slot's h vector, in front of the proof's kernels on its stream
-                    CG_HIP(hipSetDevice(ctx->device));
-                    Fr* dst = ctx->external_q ? g.s->h_canon.p : g.s->h_canon.p + ctx->rh.lo;
-                    CG_HIP(hipMemcpyAsync(dst, q_slice, nq * 32, hipMemcpyHostToDevice, g.s->st[0]));
-                    q_dev = dst;
-                }
-            }
-            e = prove_partial_impl(ctx, g.s, w_dev, scalar_is_zero(r), P, timings, nullptr, q_dev);
-            if (!e) snapshot_tune_stats(ctx, g.s, scalar_is_zero(r), ts);
-            if (!e && timings) { timings->upload_ms = upload_ms; timings->total_ms += upload_ms; }
-        }
-        if (e) return e;
-        maybe_retune(ctx, ts);
-        partials_to_bytes(P, out_partials);
-        return CG_OK;
-    } catch (...) {
-        return translate_exception();
-    }
+    const SuppliedH supplied{q_slice, nullptr, q_on_device != 0};
+    return prove_on_slot(ctx, full_assignment, assignment_on_device != 0, with_q ? &supplied : nullptr, r, nullptr, out_partials, timings);
 }
 
 extern "C" int cg_prove_partial(cg_ctx* ctx, const void* full_assignment, int assignment_on_device, const uint8_t r[32],
@@ -1551,37 +1603,20 @@ extern "C" int cg_prove_partial_q(cg_ctx* ctx, const void* full_assignment, int 
 // a sharded proof in two calls (cg_prove_partial_q_begin / _finish): the assignment-driven MSMs run while the h scalars are
 // still on their way
 // ---------------------------------------------------------------------------------------------
+// The open proof: its frame is held from _begin to the call that ends it (_finish, _finish2 or _abort), which deletes the
+// handle; everything the proof holds is given back when the frame goes, whichever call that is.
 struct cg_partial {
-    cg_ctx* c = nullptr;
-    ProofSlot* S = nullptr;
-    Upload* up = nullptr;
-    const Fr* w_dev = nullptr;
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();      // cg_timings.total_ms counts from _begin
+    CallFrame f;
     bool skip_b1 = false;
-    bool gate_held = false;
-    std::chrono::steady_clock::time_point t0;
-    // everything the open proof holds is given back exactly once, whichever call ends it
-    void close() {
-        if (S) {
-            for (auto st : S->st) if (st) (void)hipStreamSynchronize(st);
-            c->release(S);
-            S = nullptr;
-        }
-        if (up) {
-            (void)hipStreamSynchronize(up->st);
-            c->release_upload(up);
-            up = nullptr;
-        }
-        if (gate_held) { c->tune_mu.unlock_shared(); gate_held = false; }
-        if (c) { c->calls_inside.fetch_sub(1, std::memory_order_acq_rel); c = nullptr; }
-    }
+    cg_partial(cg_ctx* ctx, const void* assignment, bool on_device) : f(ctx, assignment, on_device, true, false, true) {}
 };
 
 // all coset values (half = 0) or one side of them (1: vinv·a, 2: b) for `w_dev`, on the slot's stream 0, shard-major for strided
 // shards, to host or device memory; waits for them.  -> CG_OK or CG_ERR_INVALID_ARGUMENT (a non-canonical assignment element)
 static int coset_values_to(cg_ctx* ctx, ProofSlot* S, const Fr* w_dev, int half, void* q_out, int q_on_device) {
     hipStream_t s0 = S->st[0];
-    wm29_run(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, S->wm, w_dev, ctx->M, ctx->m, ctx->l, S->h_canon.p, s0, true, nullptr, half,
-             ctx->check_witness && !half);
+    run_witness_map(ctx, S, w_dev, s0, true, half, false);      // ALL coset values (the whole-domain arrangement, whatever this context's own share is)
     const Fr* src = S->h_canon.p;
     if (ctx->h_strided) {        // shard-major: shard p's scalars q_{p + k·count} become the contiguous slice p
         Fr* tmp = reinterpret_cast<Fr*>(half == 1 ? S->wm.vb.p : S->wm.va.p);      // a vector the half just computed does not use
@@ -1592,10 +1627,7 @@ static int coset_values_to(cg_ctx* ctx, ProofSlot* S, const Fr* w_dev, int half,
     }
     CG_HIP(hipMemcpyAsync(q_out, src, ctx->D * 32, q_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s0));
     CG_HIP(hipStreamSynchronize(s0));
-    if (S->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
-    if (ctx->check_witness && !half)
-        if (int e = unsatisfied(ctx, S)) return e;
-    return CG_OK;
+    return input_verdict(ctx, S, false, ctx->check_witness && !half);
 }
 
 extern "C" int cg_prove_partial_q_begin(cg_ctx* ctx, const void* full_assignment, int assignment_on_device, const uint8_t r[32], cg_partial** out) {
@@ -1603,73 +1635,26 @@ extern "C" int cg_prove_partial_q_begin(cg_ctx* ctx, const void* full_assignment
     *out = nullptr;
     if (!scalar_is_canonical(r)) return fail(CG_ERR_INVALID_ARGUMENT, "r not canonical");
     if (!ctx->folded || ctx->shard_count <= 1) return fail(CG_ERR_INVALID_ARGUMENT, "cg_prove_partial_q_begin needs a sharded context over the folded key");
-    if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
-    std::unique_ptr<cg_partial> p(new cg_partial());
-    p->c = ctx;
-    ctx->calls_inside.fetch_add(1, std::memory_order_acq_rel);
     try {
-        ctx->tune_mu.lock_shared_passing_waiting_writers();
-        p->gate_held = true;
-        if (ctx->broken) { p->close(); return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT); }
-        CG_HIP(hipSetDevice(ctx->device));
-        p->t0 = std::chrono::steady_clock::now();
-        p->w_dev = (const Fr*)full_assignment;
-        if (!assignment_on_device) {
-            p->up = ctx->acquire_upload();
-            (void)upload_assignment(ctx, p->up, full_assignment, false);
-            p->w_dev = p->up->w.p;
-        }
-        p->S = ctx->acquire(true);
-        p->skip_b1 = scalar_is_zero(r);
-        ProofSlot* S = p->S;
-        cg_ctx* c = ctx;
-        const Fr* w_l = p->w_dev + c->rl.lo;                      // folded l query: one base per wire
-        const uint64_t n_l = c->rl.hi - c->rl.lo, n_a = c->ra.hi - c->ra.lo;
-        const Fr* w_a = p->w_dev + 1 + c->ra.lo;
-        const bool b2_adopts = !p->skip_b1 && c->b_same_identities && S->eb2.can_adopt(S->eb1) && n_a > 0;
-        hipStream_t s0 = S->st[0];
-        if (S->one_stream) {
-            S->el.digits(w_l, n_l, s0); S->el.accumulate(s0);
-            S->ea.digits(w_a, n_a, s0); S->ea.accumulate(s0);
-            if (!p->skip_b1) S->eb1.digits(w_a, n_a, s0);
-            if (b2_adopts) S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, s0);
-            if (!p->skip_b1) S->eb1.accumulate(s0);
-            if (!b2_adopts) S->eb2.digits(w_a, n_a, s0);
-            S->eb2.accumulate(s0);
-        } else {
-            CG_HIP(hipEventRecord(S->ev_w, s0));
-            for (int i = 1; i < 5; ++i) CG_HIP(hipStreamWaitEvent(S->st[i], S->ev_w, 0));
-            S->el.digits(w_l, n_l, S->st[1]);
-            S->ea.digits(w_a, n_a, S->st[2]);
-            if (!p->skip_b1) S->eb1.digits(w_a, n_a, S->st[3]);
-            if (b2_adopts) {
-                CG_HIP(hipEventRecord(S->ev_b1, S->st[3]));
-                CG_HIP(hipStreamWaitEvent(S->st[4], S->ev_b1, 0));
-                S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, S->st[4]);
-            } else {
-                S->eb2.digits(w_a, n_a, S->st[4]);
-            }
-            S->el.accumulate(S->st[1]);
-            S->ea.accumulate(S->st[2]);
-            if (!p->skip_b1) S->eb1.accumulate(S->st[3]);
-            S->eb2.accumulate(S->st[4]);
-        }
+        std::unique_ptr<cg_partial> p(new cg_partial(ctx, full_assignment, assignment_on_device != 0));
+        const Schedule sch(ctx, p->f.S, p->f.w_dev, scalar_is_zero(r));
+        p->skip_b1 = !sch.run_b1;
+        sch.phase1();
+        sch.phase2();
         *out = p.release();
         return CG_OK;
     } catch (...) {
-        const int e = translate_exception();
-        p->close();
-        return e;
+        return translate_exception();
     }
 }
 
 static int partial_coset_values(cg_partial* p, int half, void* q_out, int q_on_device) {
-    if (!p || !p->c || !p->S || !q_out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument or a closed handle");
-    cg_ctx* ctx = p->c;
+    if (!p || !p->f.S || !q_out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument or a closed handle");
+    cg_ctx* ctx = p->f.c;
     if (ctx->external_q) return fail(CG_ERR_INVALID_ARGUMENT, "context loaded with CG_FLAG_H_SCALARS_EXTERNAL holds no witness-map resources");
     try {
         CG_HIP(hipSetDevice(ctx->device));
-        return coset_values_to(ctx, p->S, p->w_dev, half, q_out, q_on_device);
+        return coset_values_to(ctx, p->f.S, p->f.w_dev, half, q_out, q_on_device);
     } catch (...) {
         return translate_exception();
     }
@@ -1680,95 +1665,39 @@ extern "C" int cg_partial_witness_map_coset_half(cg_partial* p, int which, void*
     return partial_coset_values(p, which + 1, out, out_on_device);
 }
 
-// q_slice: this shard's h scalars; or, with b_slice, the a side's slice, the h scalars being the products of the two
-static int partial_finish(cg_partial* p, const void* q_slice, const void* b_slice, bool two_sides, int q_on_device, uint8_t out_partials[384],
-                          cg_timings* timings) {
+// supplied.q: this shard's h scalars; or, with supplied.b, the a side's slice, the h scalars being the products of the two
+static int partial_finish(cg_partial* p, const SuppliedH& supplied, bool two_sides, uint8_t out_partials[384], cg_timings* timings) {
     if (!p) return fail(CG_ERR_INVALID_ARGUMENT, "null handle");
-    std::unique_ptr<cg_partial> own(p);
-    if (!p->c || !p->S) return fail(CG_ERR_INVALID_ARGUMENT, "closed handle");
-    if (!q_slice || !out_partials || (two_sides && !b_slice)) { p->close(); return fail(CG_ERR_INVALID_ARGUMENT, "null argument"); }
-    cg_ctx* c = p->c;
-    ProofSlot* S = p->S;
-    int e = CG_OK;
-    Partials P;
-    TuneStats ts;
+    std::unique_ptr<cg_partial> own(p);       // goes last, on every way out: a failed finish leaves work queued, which the frame drains
+    if (!p->f.S) return fail(CG_ERR_INVALID_ARGUMENT, "closed handle");
+    if (!supplied.q || !out_partials || (two_sides && !supplied.b)) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    cg_ctx* c = p->f.c;
+    ProofSlot* S = p->f.S;
     try {
         CG_HIP(hipSetDevice(c->device));
-        hipStream_t s0 = S->st[0];
-        const uint64_t nq = c->rh.hi - c->rh.lo;
-        const Fr* q_dev = (const Fr*)q_slice;
-        Fr* const own_q = c->external_q ? S->h_canon.p : S->h_canon.p + c->rh.lo;      // this shard's place in the slot's h vector
-        if (!q_on_device && nq) {
-            CG_HIP(hipMemcpyAsync(own_q, q_slice, nq * 32, hipMemcpyHostToDevice, s0));
-            q_dev = own_q;
-        }
-        // the input checks the witness map would have made (canonical assignment), and of what arrived instead of it
-        S->wm.h_bad_input.p[0] = 0;
-        k_flag_non_canonical<<<ceil_div(c->M, 256), 256, 0, s0>>>(p->w_dev, c->M, S->wm.h_bad_input.dev());
-        if (two_sides && nq) {
-            const Fr* b_dev = (const Fr*)b_slice;
-            if (!q_on_device) {
-                if (S->q2.n < nq) S->q2.alloc(nq);
-                CG_HIP(hipMemcpyAsync(S->q2.p, b_slice, nq * 32, hipMemcpyHostToDevice, s0));
-                b_dev = S->q2.p;
-            }
-            fr_mul_plain29(q_dev, b_dev, own_q, nq, S->wm.h_bad_input.dev(), s0);    // q_j = (vinv·a_j)·b_j; checks both operands
-            q_dev = own_q;
-        } else if (nq) {
-            k_flag_non_canonical<<<ceil_div(nq, 256), 256, 0, s0>>>(q_dev, nq, S->wm.h_bad_input.dev());
-        }
-        CG_KERNEL_CHECK();
-        const Fr* h_scalars = q_dev;
-        S->eh.digits(h_scalars, nq, s0);
-        S->eh.accumulate(s0);
-        if (S->one_stream && !spin_wait(c)) {
-            CG_HIP(hipEventRecord(S->ev_done, s0));
-            wait_sleeping(S->ev_done, 250);
-        } else {
-            wait_for_slot(S);
-        }
-        if (S->wm.h_bad_input.p[0]) {
-            e = fail(CG_ERR_INVALID_ARGUMENT, "full_assignment or the h-scalar slice holds a value >= the scalar field modulus");
-        } else {
-            P.h = to_affine(S->eh.value());
-            P.l = to_affine(S->el.value());
-            P.a = to_affine(S->ea.value());
-            P.b1 = p->skip_b1 ? G1Affine::inf() : to_affine(S->eb1.value());
-            P.b2 = to_affine(S->eb2.value());
-            if (timings) {
-                memset(timings, 0, sizeof(*timings));
-                timings->msm_h_ms = S->eh.ms_total(); timings->msm_l_ms = S->el.ms_total(); timings->msm_a_ms = S->ea.ms_total();
-                timings->msm_b1_ms = p->skip_b1 ? 0.f : S->eb1.ms_total(); timings->msm_b2_ms = S->eb2.ms_total();
-                timings->total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - p->t0).count();
-            }
-            snapshot_tune_stats(c, S, p->skip_b1, ts);
-        }
-    } catch (...) {
-        e = translate_exception();
-    }
-    p->c->calls_inside.fetch_add(1, std::memory_order_acq_rel);    // this call's own tail (the re-tune check) outlives the handle's hold
-    p->close();
-    if (!e) {
+        S->eh.digits(supplied_h_scalars(c, S, p->f.w_dev, supplied), c->rh.hi - c->rh.lo, S->st[0]);
+        S->eh.accumulate(S->st[0]);
+        Partials P;
+        TuneStats ts;
+        if (int e = collect(c, S, p->skip_b1, true, false, p->t0, P, timings, ts)) return e;
+        p->f.release();      // the frame's place in the count of calls inside stays for this call's own tail
         maybe_retune(c, ts);
         partials_to_bytes(P, out_partials);
+        return CG_OK;
+    } catch (...) {
+        return translate_exception();
     }
-    c->calls_inside.fetch_sub(1, std::memory_order_acq_rel);
-    return e;
 }
 
 extern "C" int cg_prove_partial_q_finish(cg_partial* p, const void* q_slice, int q_on_device, uint8_t out_partials[384], cg_timings* timings) {
-    return partial_finish(p, q_slice, nullptr, false, q_on_device, out_partials, timings);
+    return partial_finish(p, SuppliedH{q_slice, nullptr, q_on_device != 0}, false, out_partials, timings);
 }
 extern "C" int cg_prove_partial_q_finish2(cg_partial* p, const void* a_slice, const void* b_slice, int slices_on_device, uint8_t out_partials[384],
                                           cg_timings* timings) {
-    return partial_finish(p, a_slice, b_slice, true, slices_on_device, out_partials, timings);
+    return partial_finish(p, SuppliedH{a_slice, b_slice, slices_on_device != 0}, true, out_partials, timings);
 }
 
-extern "C" void cg_prove_partial_q_abort(cg_partial* p) {
-    if (!p) return;
-    p->close();
-    delete p;
-}
+extern "C" void cg_prove_partial_q_abort(cg_partial* p) { delete p; }
 
 extern "C" int cg_h_scalars_slice(const cg_ctx* ctx, uint32_t shard, uint64_t* offset, uint64_t* count) {
     if (!ctx || !offset || !count) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
@@ -1793,21 +1722,9 @@ static int witness_map_coset_common(cg_ctx* ctx, const void* full_assignment, in
     if (!ctx || !full_assignment || !q_out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     if (!ctx->folded) return fail(CG_ERR_INVALID_ARGUMENT, "context keeps the h query in the coefficient basis: its h scalars are cg_witness_map's");
     if (ctx->external_q) return fail(CG_ERR_INVALID_ARGUMENT, "context loaded with CG_FLAG_H_SCALARS_EXTERNAL holds no witness-map resources");
-    CallGuard inside(ctx);
     try {
-        CG_HIP(hipSetDevice(ctx->device));
-        std::shared_lock<TuneGate> tl(ctx->tune_mu);
-        if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
-        UploadGuard up;
-        const Fr* w_dev = (const Fr*)full_assignment;
-        if (!assignment_on_device) {
-            up.take(ctx);
-            (void)upload_assignment(ctx, up.u, full_assignment, false);
-            w_dev = up.u->w.p;
-        }
-        SlotGuard g(ctx);
-        // ALL coset values (the whole-domain arrangement, whatever this context's own share is)
-        return coset_values_to(ctx, g.s, w_dev, half, q_out, q_on_device);
+        CallFrame f(ctx, full_assignment, assignment_on_device != 0, false);
+        return coset_values_to(ctx, f.S, f.w_dev, half, q_out, q_on_device);
     } catch (...) {
         return translate_exception();
     }
@@ -1847,24 +1764,13 @@ extern "C" int cg_assemble(cg_ctx* ctx, const uint8_t* partials, uint32_t n_shar
 extern "C" int cg_witness_map(cg_ctx* ctx, const uint8_t* full_assignment, uint8_t* h_out) {
     if (!ctx || !full_assignment || !h_out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     if (ctx->external_q) return fail(CG_ERR_INVALID_ARGUMENT, "context loaded with CG_FLAG_H_SCALARS_EXTERNAL holds no witness-map resources");
-    CallGuard inside(ctx);
     try {
-        CG_HIP(hipSetDevice(ctx->device));
-        std::shared_lock<TuneGate> tl(ctx->tune_mu);
-        if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
-        UploadGuard up;
-        up.take(ctx);
-        (void)upload_assignment(ctx, up.u, full_assignment, false);
-        SlotGuard g(ctx);
-        ProofSlot* S = g.s;
-        hipStream_t s0 = S->st[0];
-        run_witness_map(ctx, S, up.u->w.p, s0, false);   // the reference's result: coefficients
-        CG_HIP(hipMemcpyAsync(h_out, S->h_canon.p, ctx->D * 32, hipMemcpyDeviceToHost, s0));
+        CallFrame f(ctx, full_assignment, false, false);
+        hipStream_t s0 = f.S->st[0];
+        run_witness_map(ctx, f.S, f.w_dev, s0, false);   // the reference's result: coefficients
+        CG_HIP(hipMemcpyAsync(h_out, f.S->h_canon.p, ctx->D * 32, hipMemcpyDeviceToHost, s0));
         CG_HIP(hipStreamSynchronize(s0));
-        if (S->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
-        if (ctx->check_witness)
-            if (int e = unsatisfied(ctx, S)) return e;
-        return CG_OK;
+        return input_verdict(ctx, f.S, false, ctx->check_witness);
     } catch (...) {
         return translate_exception();
     }
@@ -1875,26 +1781,15 @@ extern "C" int cg_witness_map(cg_ctx* ctx, const uint8_t* full_assignment, uint8
 extern "C" int cg_check_witness(cg_ctx* ctx, const void* full_assignment, int assignment_on_device, cg_witness_report* report) {
     if (!ctx || !full_assignment) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     if (ctx->external_q) return fail(CG_ERR_INVALID_ARGUMENT, "context loaded with CG_FLAG_H_SCALARS_EXTERNAL holds no matrices to check a witness against");
-    CallGuard inside(ctx);
     try {
-        CG_HIP(hipSetDevice(ctx->device));
-        std::shared_lock<TuneGate> tl(ctx->tune_mu);
-        if (ctx->broken) return fail(CG_ERR_OUT_OF_MEMORY, "%s", BROKEN_CONTEXT);
-        UploadGuard up;
-        const Fr* w_dev = (const Fr*)full_assignment;
-        if (!assignment_on_device) {
-            up.take(ctx);
-            (void)upload_assignment(ctx, up.u, full_assignment, false);
-            w_dev = up.u->w.p;
-        }
-        SlotGuard g(ctx);
-        ProofSlot* S = g.s;
+        CallFrame f(ctx, full_assignment, assignment_on_device != 0, false);
+        ProofSlot* S = f.S;
         hipStream_t s0 = S->st[0];
         CG_HIP(hipEventRecord(S->ev_t[0], s0));
-        wm29_check(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, S->wm, w_dev, ctx->M, ctx->m, ctx->l, s0);
+        wm29_check(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, S->wm, f.w_dev, ctx->M, ctx->m, ctx->l, s0);
         CG_HIP(hipEventRecord(S->ev_t[1], s0));
         CG_HIP(hipEventSynchronize(S->ev_t[1]));
-        if (S->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+        if (int e = input_verdict(ctx, S, false, false)) return e;
         if (report) {
             memset(report, 0, sizeof(*report));
             report->n_unsatisfied = S->wm.sat.h_rec.p[0];
