@@ -30,6 +30,7 @@ CG_FLAG_NO_LONE_SLOT = 128
 CG_FLAG_CHECK_WITNESS = 256
 CG_ERR_UNSATISFIED = -8
 CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
+CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED = 0, 1, 2      # PublicIOType, creds/src/structs.rs:33-37
 
 
 class CrescentGpuError(RuntimeError):
@@ -236,6 +237,8 @@ _SIGNATURES = {
     "cg_pvk_load": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_int32]),
     "cg_pvk_num_inputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "cg_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cg_verify_show_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "cg_pvk_free": (None, [C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
@@ -1093,6 +1096,53 @@ class Groth16:
         data = proof.data if isinstance(proof, Proof) else bytes(proof)
         return int(cls.verify_batch(pvk, [_inputs_array(public_inputs)], data)[0]) == CG_VERIFY_ACCEPT
 
+    @staticmethod
+    def verify_show_batch(pvk: "PreparedVerifyingKey", io_types, shows, with_pok: bool = True):
+        """`ShowGroth16::verify` (creds/src/groth16rand.rs:232-306) for n showings under one key and one io_types layout,
+        up to the Merlin transcript.  io_types: one CG_IO_* per public input; shows: a sequence of (ShowGroth16, revealed
+        inputs in input order).  Returns (verdicts, k_bytes): n verdict bytes of the Groth16 half, and per showing the
+        n_committed + 1 recomputed Schnorr commitments k_i of `DLogPoK::verify` (creds/src/dlog.rs:137-145) as the 32
+        compressed bytes each the transcript absorbs under b"k" - an n x (n_committed + 1) x 32 uint8 array, zero for a
+        malformed showing, None with with_pok=False.  The caller runs the transcript and compares the challenge with c."""
+        io = np.ascontiguousarray(np.asarray(list(io_types), dtype=np.uint8))
+        n = len(shows)
+        n_rev, n_hid, n_com = (int((io == t).sum()) for t in (CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED))
+        n_resp = 2 * n_com + n_hid + 1
+        shapes = [2] * n_com + [n_hid + 1]
+        for sh, x in shows:
+            if [len(si) for si in sh.pok_s] != shapes or len(sh.commited_inputs) != n_com or len(_inputs_array(x)) != 32 * n_rev:
+                raise ValueError("a showing does not have the shape of io_types")
+        cat = lambda parts, width: _u8(b"".join(parts), n * width)
+        fr = lambda v: int(v).to_bytes(32, "little")          # as given: a value >= r must reach the range check
+        return Groth16.verify_show_batch_packed(
+            pvk, io, cat([_inputs_array(x).tobytes() for _, x in shows], 32 * n_rev), cat([sh.rand_proof for sh, _ in shows], 256),
+            cat([sh.com_hidden_inputs for sh, _ in shows], 64), cat([b"".join(sh.commited_inputs) for sh, _ in shows], 64 * n_com),
+            cat([fr(sh.pok_c) for sh, _ in shows], 32) if with_pok else None,
+            cat([b"".join(fr(s) for si in sh.pok_s for s in si) for sh, _ in shows], 32 * n_resp) if with_pok else None)
+
+    @staticmethod
+    def verify_show_batch_packed(pvk: "PreparedVerifyingKey", io_types, revealed, rand_proofs, com_hidden, committed, pok_c=None,
+                                 pok_s=None):
+        """cg_verify_show_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = rand_proofs / 256);
+        pok_c = None asks for the Groth16 half only.  Returns (verdicts, k_bytes or None)."""
+        io = _u8(np.asarray(io_types, dtype=np.uint8))
+        n_rev, n_hid, n_com = (int((io == t).sum()) for t in (CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED))
+        pb = _u8(rand_proofs)
+        if pb.size % 256:
+            raise ValueError("rand_proofs must be n x 256 bytes")
+        n = pb.size // 256
+        rev, comh, comm = _u8(revealed, 32 * n_rev * n), _u8(com_hidden, 64 * n), _u8(committed, 64 * n_com * n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        verdicts = np.zeros(max(n, 1), np.uint8)
+        pc = ps = k = None
+        if pok_c is not None:
+            pc, ps = _u8(pok_c, 32 * n), _u8(pok_s, 32 * (2 * n_com + n_hid + 1) * n)
+            k = np.zeros((max(n, 1), n_com + 1, 32), np.uint8)
+        _check(lib().cg_verify_show_batch(pvk._h, ptr(io), io.size, ptr(rev), ptr(pb), ptr(comh), ptr(comm),
+                                          None if pc is None else ptr(pc), None if ps is None else ptr(ps), n, _ptr(verdicts),
+                                          None if k is None else _ptr(k)))
+        return verdicts[:n], (None if k is None else k[:n])
+
     @classmethod
     def clear_cache(cls):
         cls._cache.clear()
@@ -1131,6 +1181,51 @@ class PreparedVerifyingKey:
             self.close()
         except Exception:
             pass
+
+
+@dataclass
+class ShowGroth16:
+    """creds/src/groth16rand.rs:38-45 as its serialized pieces: rand_proof 256 B (cg_prove's layout), com_hidden_inputs and
+    every commited_inputs entry 64 B ark-serialize uncompressed G1, pok_c and the responses pok_s[statement][j] ints."""
+    rand_proof: bytes
+    com_hidden_inputs: bytes
+    pok_c: int
+    pok_s: List[List[int]]
+    commited_inputs: List[bytes]
+
+    def to_ark_bytes(self) -> bytes:
+        """`serialize_uncompressed`: rand_proof | com_hidden_inputs | pok_inputs {c, s: Vec<Vec<Fr>>} | commited_inputs: Vec<G1>"""
+        u64 = lambda v: int(v).to_bytes(8, "little")
+        fr = lambda v: int(v).to_bytes(32, "little")
+        s = u64(len(self.pok_s)) + b"".join(u64(len(si)) + b"".join(fr(x) for x in si) for si in self.pok_s)
+        return (bytes(self.rand_proof) + bytes(self.com_hidden_inputs) + fr(self.pok_c) + s
+                + u64(len(self.commited_inputs)) + b"".join(bytes(p) for p in self.commited_inputs))
+
+    @staticmethod
+    def from_ark_bytes(data) -> "ShowGroth16":
+        b = bytes(data)
+        at = 0
+
+        def take(k):
+            nonlocal at
+            if k < 0 or at + k > len(b):
+                raise ValueError("unexpected end of a serialized ShowGroth16")
+            at += k
+            return b[at - k:at]
+
+        def count(item):
+            k = int.from_bytes(take(8), "little")
+            if k > (len(b) - at) // item:
+                raise ValueError("vector length exceeds the remaining data")
+            return k
+
+        proof, comh = take(256), take(64)
+        c = int.from_bytes(take(32), "little")
+        s = [[int.from_bytes(take(32), "little") for _ in range(count(32))] for _ in range(count(8))]
+        com = [take(64) for _ in range(count(64))]
+        if at != len(b):
+            raise ValueError("trailing bytes after a serialized ShowGroth16")
+        return ShowGroth16(proof, comh, c, s, com)
 
 
 def _inputs_array(inputs) -> np.ndarray:

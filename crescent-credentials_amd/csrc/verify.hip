@@ -11,6 +11,19 @@
 //                 and of the inputs (< r); gamma_abc[0] + Σ partials -> prepared inputs (affine)
 //   k_vfy_miller  one lane per proof: the multi-Miller loop over (A, B on the fly), (prepared inputs, gamma), (C, delta)
 //   k_vfy_final   one lane per proof: final exponentiation, == alpha_g1_beta_g2 -> one verdict byte
+//
+// cg_verify_show_batch verifies what a relying party receives instead: `ShowGroth16::verify` (creds/src/groth16rand.rs:232-306)
+// for a batch of showings that share one io_types layout, up to the Merlin transcript, which stays with the host.  The key
+// also carries a table of vk.delta_g1 (the last one), and a chunk of showings runs
+//   k_show_terms  one lane per (showing, term): the fixed-base terms x_j·gamma_abc[j+1] of the revealed inputs and
+//                 s·gamma_abc[i+1], s·delta_g1 of the DLogPoK responses from the tables; then, in waves of their own, the
+//                 variable-base terms c·y_i by double-and-add                                          -> XYZZ partials
+//   k_vfy_check   as above on the re-randomised proof, with no inputs
+//   k_show_check  one lane per showing: checked deserialisation of com_hidden and the committed points, revealed inputs,
+//                 responses and c < r; com_hidden + gamma_abc[0] + Σ committed + Σ revealed partials -> prepared inputs
+//   k_show_k      one lane per (showing, statement): k_i = Σ_j s_ij·base_ij + c·y_i (creds/src/dlog.rs:137-145) from the
+//                 partials, affine, written as ark-serialize's compressed G1 (what the transcript absorbs under b"k")
+//   k_vfy_miller, k_vfy_final   unchanged
 #include <memory>
 
 #include "common.hpp"
@@ -145,7 +158,8 @@ static void parse_pvk(const uint8_t* data, uint64_t len, HostPvk& k) {   // data
     if (r.off != len) throw HipError(CG_ERR_PARSE, "trailing bytes after PreparedVerifyingKey");
 }
 
-// fixed-base tables of gamma_abc[1..]: tab[(i·NWIN + w)·VWIN + d] = d·2^(8w)·gamma_abc[i+1], affine (one batch inversion)
+// fixed-base tables of gabc[1..]: tab[(i·NWIN + w)·VWIN + d] = d·2^(8w)·gabc[i+1], affine (one batch inversion).  The key
+// passes gamma_abc_g1 followed by delta_g1, so table n_inputs is delta_g1's.
 static void build_tables(const std::vector<G1Affine>& gabc, std::vector<G1Affine>& tab) {
     const uint64_t ell = gabc.size() - 1;
     const uint64_t total = ell * NWIN * VWIN;
@@ -289,6 +303,117 @@ __global__ __launch_bounds__(VBLOCK) void k_vfy_final(const Fq12* __restrict__ f
     verdict[p] = some && r == alpha_beta ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
 }
 
+// ---- showings (ShowGroth16::verify, groth16rand.rs:232-306) ------------------------------------------------------------
+// One call's layout.  A showing's partials are [n_fixed fixed-base terms | n_var variable-base terms]: the revealed inputs,
+// then (with a DLogPoK) the n_resp responses in the order dlog.rs:135-145 meets them, then c·y_i per statement.
+struct ShowShape {
+    uint32_t n_rev, n_com, n_resp;     // revealed inputs, committed inputs, responses = 2·n_com + n_hidden + 1
+    uint32_t n_fixed, n_var;           // n_rev (+ n_resp), 0 or n_com + 1
+    uint32_t n_terms;                  // n_fixed + n_var
+};
+
+// an uncompressed G1 point as the variable-base lanes use it: no checks (k_show_check makes them, and a showing that fails
+// them has its k bytes zeroed), flags stripped
+__device__ __forceinline__ G1Affine dev_g1_unchecked(const uint32_t* w) {
+    if ((w[15] >> 30) == 1u) return G1Affine::inf();
+    bool ignored = true;
+    G1Affine p;
+    p.x = dev_fq(w, ignored);
+    p.y = dev_fq(w + 8, ignored, 0xC0000000u);
+    return p;
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_show_terms(const uint32_t* __restrict__ revealed, const uint32_t* __restrict__ pok_s,
+                                                      const uint32_t* __restrict__ pok_c, const uint32_t* __restrict__ com_hidden,
+                                                      const uint32_t* __restrict__ committed, uint64_t n, ShowShape sh,
+                                                      const uint32_t* __restrict__ tab_of, const G1Affine* __restrict__ tab,
+                                                      G1XYZZ* __restrict__ part) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t n_fixed_lanes = n * sh.n_fixed;
+    if (g < n_fixed_lanes) {
+        const uint64_t p = g / sh.n_fixed;
+        const uint32_t t = (uint32_t)(g % sh.n_fixed);
+        const uint32_t* x = t < sh.n_rev ? revealed + 8 * (p * sh.n_rev + t) : pok_s + 8 * (p * sh.n_resp + (t - sh.n_rev));
+        const G1Affine* tb = tab + (uint64_t)tab_of[t] * NWIN * VWIN;
+        G1XYZZ acc = G1XYZZ::inf();
+        for (int w = 0; w < NWIN; ++w) {
+            const uint32_t d = (x[w >> 2] >> (8 * (w & 3))) & 0xFFu;
+            if (d) madd(acc, tb[w * VWIN + d]);
+        }
+        part[p * sh.n_terms + t] = acc;
+        return;
+    }
+    // the variable-base lanes (a chain ~10x as long) start at a workgroup of their own
+    const uint64_t var_at = (n_fixed_lanes + VBLOCK - 1) / VBLOCK * VBLOCK;
+    if (g < var_at || g - var_at >= n * sh.n_var) return;
+    const uint64_t v = g - var_at;
+    const uint64_t p = v / sh.n_var;
+    const uint32_t i = (uint32_t)(v % sh.n_var);
+    const G1Affine y = dev_g1_unchecked(i < sh.n_com ? committed + 16 * (p * sh.n_com + i) : com_hidden + 16 * p);
+    const uint32_t* c = pok_c + 8 * p;
+    // c < r < 2^254 (a challenge is 248 bits, dlog.rs:97-99); the doublings before the first set bit return at once
+    G1XYZZ acc = G1XYZZ::inf();
+    for (int wi = 7; wi >= 0; --wi) {
+        const uint32_t cw = c[wi];
+        for (int b = wi == 7 ? 29 : 31; b >= 0; --b) {
+            acc = dbl(acc);
+            if ((cw >> b) & 1u) madd(acc, y);
+        }
+    }
+    part[p * sh.n_terms + sh.n_fixed + i] = acc;
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_show_check(const uint32_t* __restrict__ revealed, const uint32_t* __restrict__ pok_s,
+                                                      const uint32_t* __restrict__ pok_c, const uint32_t* __restrict__ com_hidden,
+                                                      const uint32_t* __restrict__ committed, uint64_t n, ShowShape sh,
+                                                      const G1XYZZ* __restrict__ part, G1Affine g0, ParsedProof* __restrict__ out,
+                                                      uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    bool ok = true;
+    G1XYZZ acc = G1XYZZ::from_affine(g0);                         // groth16rand.rs:246
+    madd(acc, dev_g1(com_hidden + 16 * p, ok));
+    for (uint32_t i = 0; i < sh.n_com; ++i) madd(acc, dev_g1(committed + 16 * (p * sh.n_com + i), ok));      // :269
+    for (uint32_t j = 0; j < sh.n_rev; ++j) {                     // :279
+        ok = ok && limbs_below(revealed + 8 * (p * sh.n_rev + j), FrP::N);
+        add(acc, part[p * sh.n_terms + j]);
+    }
+    if (sh.n_var) {
+        ok = ok && limbs_below(pok_c + 8 * p, FrP::N);
+        for (uint32_t j = 0; j < sh.n_resp; ++j) ok = ok && limbs_below(pok_s + 8 * (p * sh.n_resp + j), FrP::N);
+    }
+    out[p].pi = to_affine(acc);
+    if (!ok) status[p] = ST_MALFORMED;
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_show_k(uint64_t n, ShowShape sh, const G1XYZZ* __restrict__ part,
+                                                  const uint8_t* __restrict__ status, uint32_t* __restrict__ k_out) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * sh.n_var) return;
+    const uint64_t p = g / sh.n_var;
+    const uint32_t i = (uint32_t)(g % sh.n_var);
+    uint32_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (status[p] == ST_OK) {
+        // statement i < n_com: (gamma_abc[.], delta_g1); the last one: the hidden inputs' bases, then delta_g1
+        const uint32_t lo = i < sh.n_com ? 2 * i : 2 * sh.n_com;
+        const uint32_t hi = i < sh.n_com ? 2 * i + 2 : sh.n_resp;
+        const G1XYZZ* pt = part + p * sh.n_terms;
+        G1XYZZ acc = pt[sh.n_fixed + i];
+        for (uint32_t j = lo; j < hi; ++j) add(acc, pt[sh.n_rev + j]);
+        const G1Affine a = to_affine(acc);
+        if (a.is_inf()) {
+            o[7] = 0x40000000u;                                   // SWFlags::PointAtInfinity
+        } else {
+            const Fq x = from_mont(a.x), y = from_mont(a.y), ny = from_mont(neg(a.y));
+#pragma unroll
+            for (int l = 0; l < 8; ++l) o[l] = x.l[l];
+            if (limbs_below(ny.l, y.l)) o[7] |= 0x80000000u;      // SWFlags::YIsNegative: y > -y
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < 8; ++l) k_out[8 * g + l] = o[l];
+}
+
 }  // namespace
 
 struct cg_pvk {
@@ -307,6 +432,9 @@ struct cg_pvk {
     DevBuf<G1XYZZ> d_part;
     DevBuf<ParsedProof> d_parsed;
     DevBuf<Fq12> d_f;
+    // cg_verify_show_batch's own: grown one by one, since their sizes follow the call's layout
+    DevBuf<uint8_t> s_rev, s_comh, s_comm, s_c, s_s, s_k;
+    DevBuf<uint32_t> s_tab_of;
     ~cg_pvk() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
 };
 
@@ -317,8 +445,9 @@ extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len,
         HostPvk hk;
         parse_pvk(pvk_bytes, len, hk);           // host only: a parse error is reported before any HIP call
         if (hk.vk.gamma_abc.empty()) return fail(CG_ERR_MALFORMED_KEY, "gamma_abc_g1 is empty");
-        std::vector<G1Affine> tab;
-        build_tables(hk.vk.gamma_abc, tab);
+        std::vector<G1Affine> bases = hk.vk.gamma_abc, tab;
+        bases.push_back(hk.vk.delta_g1);            // the Pedersen / DLogPoK base of a showing (groth16rand.rs:133, :274)
+        build_tables(bases, tab);
         int dev = device;
         if (dev < 0) CG_HIP(hipGetDevice(&dev));
         CG_HIP(hipSetDevice(dev));
@@ -391,6 +520,110 @@ extern "C" int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inpu
             k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->d_f.p, k->d_status.p, m, k->alpha_beta, k->d_verdict.p);
             CG_KERNEL_CHECK();
             CG_HIP(hipMemcpyAsync(verdicts + off, k->d_verdict.p, m, hipMemcpyDeviceToHost, k->st));
+            CG_HIP(hipStreamSynchronize(k->st));
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+template <class T>
+static void grow(DevBuf<T>& b, uint64_t count) {
+    if (b.n < count) b.alloc(count);
+}
+
+extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, const uint8_t* revealed,
+                                    const uint8_t* rand_proofs, const uint8_t* com_hidden, const uint8_t* committed,
+                                    const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_io != k->n_inputs)
+        return fail(CG_ERR_MALFORMED_KEY, "%llu io types for a key with gamma_abc_g1.len() = %llu", (unsigned long long)n_io,
+                    (unsigned long long)(k->n_inputs + 1));
+    if (n_io && !io_types) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    // the layout: which table each fixed-base term walks (table n_inputs is delta_g1's)
+    std::vector<uint32_t> rev_tab, hid_tab, resp_tab;
+    for (uint64_t i = 0; i < n_io; ++i) {
+        switch (io_types[i]) {
+            case CG_IO_REVEALED: rev_tab.push_back((uint32_t)i); break;
+            case CG_IO_HIDDEN: hid_tab.push_back((uint32_t)i); break;
+            case CG_IO_COMMITTED:
+                resp_tab.push_back((uint32_t)i);
+                resp_tab.push_back((uint32_t)n_io);
+                break;
+            default: return fail(CG_ERR_INVALID_ARGUMENT, "io_types[%llu] = %u is no PublicIOType", (unsigned long long)i, io_types[i]);
+        }
+    }
+    if (n == 0) return CG_OK;
+    const bool pok = pok_c != nullptr;
+    ShowShape sh;
+    sh.n_rev = (uint32_t)rev_tab.size();
+    sh.n_com = (uint32_t)(resp_tab.size() / 2);
+    resp_tab.insert(resp_tab.end(), hid_tab.begin(), hid_tab.end());
+    resp_tab.push_back((uint32_t)n_io);
+    sh.n_resp = (uint32_t)resp_tab.size();
+    sh.n_fixed = sh.n_rev + (pok ? sh.n_resp : 0);
+    sh.n_var = pok ? sh.n_com + 1 : 0;
+    sh.n_terms = sh.n_fixed + sh.n_var;
+    if (!rand_proofs || !com_hidden || !verdicts || (sh.n_rev && !revealed) || (sh.n_com && !committed) || (pok && (!pok_s || !k_out)))
+        return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<uint32_t> tab_of = rev_tab;
+    if (pok) tab_of.insert(tab_of.end(), resp_tab.begin(), resp_tab.end());
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
+        grow(k->d_proofs, chunk * 256);
+        grow(k->d_status, chunk);
+        grow(k->d_verdict, chunk);
+        grow(k->d_parsed, chunk);
+        grow(k->d_f, chunk);
+        grow(k->d_part, chunk * sh.n_terms + 1);
+        grow(k->s_rev, chunk * sh.n_rev * 32 + 32);
+        grow(k->s_comh, chunk * 64);
+        grow(k->s_comm, chunk * sh.n_com * 64 + 64);
+        grow(k->s_c, chunk * 32);
+        grow(k->s_s, chunk * sh.n_resp * 32);
+        grow(k->s_k, chunk * (sh.n_com + 1) * 32);
+        grow(k->s_tab_of, tab_of.size() + 1);
+        h2d_sync(k->s_tab_of.p, tab_of.data(), tab_of.size() * sizeof(uint32_t), k->st);
+        const uint32_t n_stmt = sh.n_com + 1;
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            CG_HIP(hipMemcpyAsync(k->d_proofs.p, rand_proofs + off * 256, m * 256, hipMemcpyHostToDevice, k->st));
+            CG_HIP(hipMemcpyAsync(k->s_comh.p, com_hidden + off * 64, m * 64, hipMemcpyHostToDevice, k->st));
+            if (sh.n_rev) CG_HIP(hipMemcpyAsync(k->s_rev.p, revealed + off * sh.n_rev * 32, m * sh.n_rev * 32, hipMemcpyHostToDevice, k->st));
+            if (sh.n_com) CG_HIP(hipMemcpyAsync(k->s_comm.p, committed + off * sh.n_com * 64, m * sh.n_com * 64, hipMemcpyHostToDevice, k->st));
+            if (pok) {
+                CG_HIP(hipMemcpyAsync(k->s_c.p, pok_c + off * 32, m * 32, hipMemcpyHostToDevice, k->st));
+                CG_HIP(hipMemcpyAsync(k->s_s.p, pok_s + off * sh.n_resp * 32, m * sh.n_resp * 32, hipMemcpyHostToDevice, k->st));
+            }
+            const uint32_t *d_rev = (const uint32_t*)k->s_rev.p, *d_s = (const uint32_t*)k->s_s.p, *d_c = (const uint32_t*)k->s_c.p,
+                           *d_comh = (const uint32_t*)k->s_comh.p, *d_comm = (const uint32_t*)k->s_comm.p;
+            if (sh.n_terms) {
+                const uint32_t blocks = ceil_div(m * sh.n_fixed, VBLOCK) + ceil_div(m * sh.n_var, VBLOCK);
+                k_show_terms<<<blocks, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->s_tab_of.p,
+                                                                           k->tab.p, k->d_part.p);
+                CG_KERNEL_CHECK();
+            }
+            const uint32_t grid = ceil_div(m, VBLOCK);
+            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->d_proofs.p, d_rev, m, 0u, k->d_part.p, k->g0, k->d_parsed.p,
+                                                    k->d_status.p);
+            CG_KERNEL_CHECK();
+            k_show_check<<<grid, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->d_part.p, k->g0, k->d_parsed.p,
+                                                     k->d_status.p);
+            CG_KERNEL_CHECK();
+            if (pok) {
+                k_show_k<<<ceil_div(m * n_stmt, VBLOCK), VBLOCK, 0, k->st>>>(m, sh, k->d_part.p, k->d_status.p, (uint32_t*)k->s_k.p);
+                CG_KERNEL_CHECK();
+            }
+            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->d_parsed.p, k->d_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
+                                                     k->delta_live, k->d_f.p);
+            CG_KERNEL_CHECK();
+            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->d_f.p, k->d_status.p, m, k->alpha_beta, k->d_verdict.p);
+            CG_KERNEL_CHECK();
+            CG_HIP(hipMemcpyAsync(verdicts + off, k->d_verdict.p, m, hipMemcpyDeviceToHost, k->st));
+            if (pok) CG_HIP(hipMemcpyAsync(k_out + off * n_stmt * 32, k->s_k.p, m * n_stmt * 32, hipMemcpyDeviceToHost, k->st));
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;

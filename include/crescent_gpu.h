@@ -588,6 +588,34 @@ int cg_pvk_num_inputs(const cg_pvk* k, uint64_t* n);
  * (SynthesisError::MalformedVerifyingKey).  Any n; calls on one handle serialise, different handles are independent. */
 int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inputs, const uint8_t* proofs, uint64_t n,
                     uint8_t* verdicts);
+/* Replaces: `ShowGroth16::verify` (creds/src/groth16rand.rs:232-306, called at creds/src/lib.rs:630 and :832) for n
+ * showings under one key and ONE io_types layout (an endpoint has one proof spec), up to the Merlin transcript:
+ *   - the Groth16 half entirely: the prepared inputs com_hidden + gamma_abc[0] + sum committed_i +
+ *     sum_{revealed j} x_j * gamma_abc[j+1] (:246-279), then `verify_proof_with_prepared_inputs`
+ *     (forks/groth16/src/verifier.rs:44-65) -> verdicts[i];
+ *   - the group arithmetic of `DLogPoK::verify` (creds/src/dlog.rs:134-153): per statement i the recomputed Schnorr
+ *     commitment k_i = sum_j s_ij * base_ij + c * y_i, written to k_out as the 32 bytes `add_to_transcript(b"k", ..)`
+ *     appends (ark-serialize COMPRESSED G1).  y_i is the i-th committed point, com_hidden for the last statement.
+ * NOT done here: the transcript itself and the comparison `c == self.c` (dlog.rs:130-132,147-152,166-174).  The host
+ * feeds the bases, k_out and y into its own Merlin transcript and compares the challenge; a showing is valid when its
+ * verdict is CG_VERIFY_ACCEPT and that comparison holds ("Verifying showings").
+ * io_types: one byte per public input (creds/src/structs.rs:33-37), n_io must equal cg_pvk_num_inputs, else
+ *   CG_ERR_MALFORMED_KEY; a byte above 2 is CG_ERR_INVALID_ARGUMENT.  With n_revealed / n_hidden / n_committed of each:
+ * revealed:    n x n_revealed x 32 B canonical Fr, in input order (:260-264)
+ * rand_proofs: n x 256 B, cg_prove's layout
+ * com_hidden:  n x 64 B ark-serialize uncompressed G1;  committed: n x n_committed x 64 B, same, in input order
+ * pok_c:       n x 32 B canonical Fr; NULL = the Groth16 half only (pok_s and k_out are then not touched)
+ * pok_s:       n x n_resp x 32 B, n_resp = 2 * n_committed + n_hidden + 1, statement-major as dlog.rs:135-145 reads them:
+ *              per committed input the response for gamma_abc[i+1], then for delta_g1 (:272-275); then one per hidden
+ *              input, then the one for delta_g1 (:266,280)
+ * verdicts:    n x CG_VERIFY_*;  k_out: n x (n_committed + 1) x 32 B
+ * CG_VERIFY_MALFORMED (that showing only, its k_out bytes zero): rand_proof fails cg_verify_batch's checks, com_hidden
+ * or a committed point fails ark's checked G1 deserialisation, or a revealed input, a response or c is >= r.
+ * Argument errors are reported before any HIP call; n = 0 is CG_OK. */
+enum { CG_IO_REVEALED = 0, CG_IO_HIDDEN = 1, CG_IO_COMMITTED = 2 };
+int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, const uint8_t* revealed,
+                         const uint8_t* rand_proofs, const uint8_t* com_hidden, const uint8_t* committed,
+                         const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts, uint8_t* k_out);
 void cg_pvk_free(cg_pvk* k);
 /* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
  * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the

@@ -11,7 +11,7 @@ use ark_groth16::r1cs_to_qap::{LibsnarkReduction, R1CSToQAP};
 use ark_groth16::{Proof, ProvingKey};
 use ark_poly::EvaluationDomain;
 use ark_relations::r1cs::{ConstraintMatrices, ConstraintSystemRef, SynthesisError};
-use ark_serialize::CanonicalDeserialize;
+use ark_serialize::{CanonicalDeserialize, CanonicalSerialize};
 use std::collections::HashMap;
 use std::ffi::CStr;
 use std::sync::{Arc, Mutex, OnceLock};
@@ -656,4 +656,97 @@ pub fn msm_g2(bases: &[G2Affine], scalars: &[Fr]) -> Result<G2Affine, SynthesisE
     let x = Fq2::new(Fq::from_le_bytes_mod_order(&out[..32]), Fq::from_le_bytes_mod_order(&out[32..64]));
     let y = Fq2::new(Fq::from_le_bytes_mod_order(&out[64..96]), Fq::from_le_bytes_mod_order(&out[96..]));
     Ok(G2Affine::new_unchecked(x, y))
+}
+
+/// A `PreparedVerifyingKey` resident on one GPU (`cg_pvk_load`): what a verifier endpoint keeps per proof spec.
+pub struct GpuVerifyingKey {
+    h: *mut sys::cg_pvk,
+}
+unsafe impl Send for GpuVerifyingKey {}
+unsafe impl Sync for GpuVerifyingKey {} // calls on one handle serialise inside the library
+
+/// One showing as `ShowGroth16::verify` reads it (creds/src/groth16rand.rs:38-45), borrowed from the caller's struct.
+pub struct ShowRef<'a> {
+    pub rand_proof: &'a Proof<Bn254>,
+    pub com_hidden_inputs: &'a G1Affine,
+    pub commited_inputs: &'a [G1Affine],
+    pub pok_c: &'a Fr,
+    pub pok_s: &'a [Vec<Fr>],
+    /// the revealed public inputs, in input order (groth16rand.rs:260-264)
+    pub revealed: &'a [Fr],
+}
+
+/// What `GpuVerifyingKey::verify_show_batch` returns for one showing.
+pub struct ShowOutcome {
+    /// `verify_proof_with_prepared_inputs` said true; false covers a rejected and a malformed showing alike
+    pub groth16_valid: bool,
+    /// the recomputed k_i of `DLogPoK::verify` (creds/src/dlog.rs:137-145), each as the 32 bytes
+    /// `add_to_transcript(&mut ts, b"k", &k_i)` appends; all zero when the showing is malformed
+    pub k: Vec<[u8; 32]>,
+}
+
+impl GpuVerifyingKey {
+    /// `pvk_bytes`: the PreparedVerifyingKey as `serialize_uncompressed` writes it (creds/src/utils.rs:186 reads it back).
+    pub fn load(pvk_bytes: &[u8], device: i32) -> Result<Self, SynthesisError> {
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe { sys::cg_pvk_load(&mut h, pvk_bytes.as_ptr(), pvk_bytes.len() as u64, device) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(Self { h })
+    }
+
+    /// The GPU share of `ShowGroth16::verify` (groth16rand.rs:232-306) for showings of one proof spec: the Groth16 half
+    /// whole, and the recomputed Schnorr commitments of the DLogPoK.  The Merlin transcript stays here on the host:
+    /// absorb the bases, `k` and y exactly as dlog.rs:130-152 does, derive the challenge (:166-169) and compare it with
+    /// `pok_inputs.c`; a showing is valid when that holds and `groth16_valid` is true ("Verifying showings").
+    pub fn verify_show_batch(&self, io_types: &[u8], shows: &[ShowRef]) -> Result<Vec<ShowOutcome>, SynthesisError> {
+        let n_com = io_types.iter().filter(|t| **t == sys::CG_IO_COMMITTED).count();
+        let n_hid = io_types.iter().filter(|t| **t == sys::CG_IO_HIDDEN).count();
+        let n_rev = io_types.iter().filter(|t| **t == sys::CG_IO_REVEALED).count();
+        let n = shows.len();
+        let (mut rev, mut proofs, mut comh, mut comm, mut c, mut s) = (Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new());
+        for sh in shows {
+            let shape_ok = sh.revealed.len() == n_rev
+                && sh.commited_inputs.len() == n_com
+                && sh.pok_s.len() == n_com + 1
+                && sh.pok_s.iter().take(n_com).all(|v| v.len() == 2)
+                && sh.pok_s[n_com].len() == n_hid + 1;
+            if !shape_ok {
+                return Err(SynthesisError::MalformedVerifyingKey);
+            }
+            rev.extend(canonical_bytes(sh.revealed));
+            // ark-serialize uncompressed, the layout cg_prove writes and cg_verify_show_batch reads
+            sh.rand_proof.serialize_uncompressed(&mut proofs).map_err(|_| SynthesisError::AssignmentMissing)?;
+            sh.com_hidden_inputs.serialize_uncompressed(&mut comh).map_err(|_| SynthesisError::AssignmentMissing)?;
+            for p in sh.commited_inputs {
+                p.serialize_uncompressed(&mut comm).map_err(|_| SynthesisError::AssignmentMissing)?;
+            }
+            c.extend(canonical_bytes(std::slice::from_ref(sh.pok_c)));
+            for si in sh.pok_s {
+                s.extend(canonical_bytes(si));
+            }
+        }
+        let mut verdicts = vec![0u8; n];
+        let mut k = vec![0u8; n * (n_com + 1) * 32];
+        let rc = unsafe {
+            sys::cg_verify_show_batch(self.h, io_types.as_ptr(), io_types.len() as u64, rev.as_ptr(), proofs.as_ptr(), comh.as_ptr(),
+                                      comm.as_ptr(), c.as_ptr(), s.as_ptr(), n as u64, verdicts.as_mut_ptr(), k.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((0..n)
+            .map(|i| ShowOutcome {
+                groth16_valid: verdicts[i] == sys::CG_VERIFY_ACCEPT,
+                k: k[i * (n_com + 1) * 32..(i + 1) * (n_com + 1) * 32].chunks(32).map(|b| b.try_into().unwrap()).collect(),
+            })
+            .collect())
+    }
+}
+
+impl Drop for GpuVerifyingKey {
+    fn drop(&mut self) {
+        unsafe { sys::cg_pvk_free(self.h) }
+    }
 }

@@ -16,6 +16,12 @@ pub const CG_FLAG_CHECK_WITNESS: i32 = 256;
 pub const CG_ERR_POLY_DEGREE_TOO_LARGE: c_int = -5;
 pub const CG_ERR_MALFORMED_KEY: c_int = -6;
 pub const CG_ERR_UNSATISFIED: c_int = -8;
+pub const CG_VERIFY_REJECT: u8 = 0;
+pub const CG_VERIFY_ACCEPT: u8 = 1;
+pub const CG_VERIFY_MALFORMED: u8 = 2;
+pub const CG_IO_REVEALED: u8 = 0;
+pub const CG_IO_HIDDEN: u8 = 1;
+pub const CG_IO_COMMITTED: u8 = 2;
 
 #[repr(C)]
 pub struct cg_proving_key {
@@ -149,6 +155,7 @@ pub enum cg_ctx {}
 pub enum cg_partial {}
 pub enum cg_msm_ctx {}
 pub enum cg_qap_ctx {}
+pub enum cg_pvk {}
 
 extern "C" {
     pub fn cg_init(n_devices: c_int, device_ids: *const c_int) -> c_int;
@@ -313,4 +320,23 @@ extern "C" {
         timings: *mut cg_timings,
     ) -> c_int;
     pub fn cg_msm_free(ctx: *mut cg_msm_ctx);
+    // verification: a PreparedVerifyingKey resident on a device, proofs and showings in batches
+    pub fn cg_pvk_load(out: *mut *mut cg_pvk, pvk_bytes: *const u8, len: u64, device: i32) -> c_int;
+    pub fn cg_pvk_num_inputs(k: *const cg_pvk, n: *mut u64) -> c_int;
+    pub fn cg_verify_batch(k: *mut cg_pvk, inputs: *const u8, n_inputs: u64, proofs: *const u8, n: u64, verdicts: *mut u8) -> c_int;
+    pub fn cg_verify_show_batch(
+        k: *mut cg_pvk,
+        io_types: *const u8,
+        n_io: u64,
+        revealed: *const u8,
+        rand_proofs: *const u8,
+        com_hidden: *const u8,
+        committed: *const u8,
+        pok_c: *const u8,
+        pok_s: *const u8,
+        n: u64,
+        verdicts: *mut u8,
+        k_out: *mut u8,
+    ) -> c_int;
+    pub fn cg_pvk_free(k: *mut cg_pvk);
 }
