@@ -65,27 +65,6 @@ CG_HD Affine29<F> load_table_point(const uint32_t* __restrict__ table, uint32_t 
     return a;
 }
 
-// The bucket accumulation's form: a negated y is left as 2N − y limb-wise (limbs below 2^30, value below 2N).  Its only
-// uses in madd29 are one product against a normalised operand (2^30·2^29 stays inside the column bound) and the
-// start of a run, which normalises it; the eight-step carry chain per entry is saved.  Fq only: an Fq2 product wants
-// its smaller operand normalised (field29.hpp).
-CG_HD Affine29<Fq29> load_table_point_lazy_y(const uint32_t* __restrict__ table, uint32_t idx, bool negate) {
-    constexpr int AFF = Words29<Fq29>::AFF;
-    const uint4* p = reinterpret_cast<const uint4*>(table + (size_t)idx * AFF);
-    uint32_t w[AFF];
-#pragma unroll
-    for (int i = 0; i < AFF / 4; ++i) {
-        uint4 v = p[i];
-        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-    Affine29<Fq29> a;
-    load_coord(a.x, w);
-    load_coord(a.y, w + AFF / 2);
-    Fq29 ny = sub<2, 1>(Fq29::zero(), a.y);
-    if (negate) a.y = ny;
-    return a;
-}
-
 // the signed accumulation's form: both coordinates as stored (the digit's sign is applied inside madd29s, as a multiplier)
 CG_HD Affine29<Fq29> load_table_point_plain(const uint32_t* __restrict__ table, uint32_t idx) {
     constexpr int AFF = Words29<Fq29>::AFF;

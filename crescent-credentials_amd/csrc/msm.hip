@@ -304,9 +304,9 @@ __device__ __forceinline__ void for_each_digit_c(const uint32_t (&s)[8], Fn f) {
 // the buckets do not matter (the sum is a group element).  So the entries are never sorted: they are PLACED.
 //   level 1  k_part_count   every block walks its tile of scalars, extracts the signed digits and counts them by the
 //                           high bits of the bucket key in LDS; the block's counts go to its row of `blk_hist` and,
-//                           with one atomic per non-empty bin, to the global histogram
-//            k_part_plan    one block: entry total, segment length and count for the accumulation, bin starts
-//                           (exclusive scan), and the chunk table of level 2
+//                           with one atomic per non-empty bin, to the global histogram; the block that finishes last
+//                           makes the plan (part_plan_block): entry total, segment length and count for the
+//                           accumulation, bin starts (exclusive scan), and the chunk table of level 2
 //            k_part_place   the same walk again; a block reserves its range of every bin with one global atomic and
 //                           hands out slots inside it with LDS atomics: digit extraction is fused into the placement,
 //                           so the entry list is written once and never read back by a "sort"
@@ -426,7 +426,6 @@ __global__ void __launch_bounds__(PART_THREADS) k_part_count(PartShape sh, const
     // block meets at the barrier, one thread counts the block in.  No __threadfence(): at agent scope that is an L2
     // write-back + invalidate, and with it in every wave of this kernel the pipeline lost 17 % (profiles/r04_f_fold_ab.txt);
     // the s_waitcnt writes nothing back.
-    if (!pa.start1) return;            // tuning builds, CG_PLAN_LAUNCH=1 (A/B aid): the plan is made by a launch of its own
     __shared__ uint32_t is_last;
     __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0) (gfx9 encoding: expcnt and lgkmcnt left at their maxima)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -490,11 +489,6 @@ __device__ __forceinline__ void part_plan_block(int bits1, const PlanArgs& pa, c
     const uint32_t chunks = block_exclusive_scan(lds, B1);
     for (uint32_t k = threadIdx.x; k < B1; k += blockDim.x) pa.chunk0[k] = lds[k];
     if (threadIdx.x == 0) { pa.chunk0[B1] = chunks; plan[PLAN_CHUNKS] = chunks; }
-}
-
-__global__ void __launch_bounds__(1024) k_part_plan(int bits1, PlanArgs pa, const uint32_t* hist1, uint32_t* plan) {
-    extern __shared__ uint32_t lds[];
-    part_plan_block(bits1, pa, hist1, plan, lds);
 }
 
 // a plan taken over with another engine's entries: the segment geometry is re-cut for THIS engine's accumulation kernel
@@ -632,7 +626,7 @@ static void launch_part_level1_c(bool count, const PartShape& sh, uint32_t tiles
 }
 static void launch_part_level1(bool count, const PartShape& sh, uint32_t tiles, size_t lds, hipStream_t st, const Fr* scalars,
                                const uint8_t* valid, uint32_t* blk_hist, uint32_t* hist1, uint32_t* plan, const uint32_t* start1,
-                               uint32_t* cur1, uint64_t* out, const PlanArgs& pa = PlanArgs{}) {
+                               uint32_t* cur1, uint64_t* out, const PlanArgs& pa) {
 #define CG_PART_CASE(C) case C: launch_part_level1_c<C>(count, sh, tiles, lds, st, scalars, valid, blk_hist, hist1, plan, start1, cur1, out, pa); break;
     switch (sh.c) {
         CG_PART_CASE(10) CG_PART_CASE(11) CG_PART_CASE(12) CG_PART_CASE(13) CG_PART_CASE(14) CG_PART_CASE(15) CG_PART_CASE(16)
@@ -747,73 +741,18 @@ __device__ __forceinline__ void flush_run(uint32_t key, const XYZZ29<F29T>& acc,
     }
 }
 
-#if defined(CG_ACCUM_WAVES)      // A/B aid: force the occupancy target of the G1 accumulation (default: what 116 VGPRs give, 4)
-#define CG_ACCUM_ATTR __attribute__((amdgpu_waves_per_eu(CG_ACCUM_WAVES, CG_ACCUM_WAVES)))
-#else
-#define CG_ACCUM_ATTR
-#endif
-template <class F29T>
-__global__ void __launch_bounds__(256) CG_ACCUM_ATTR k_accum_affine(const uint64_t* __restrict__ entries, const uint32_t* __restrict__ plan,
-                                                      const uint32_t* __restrict__ table,
-                                                      uint32_t* __restrict__ bucket_sums, uint32_t* __restrict__ part_keys,
-                                                      uint32_t* __restrict__ part_pts) {
-    constexpr int ACC = Words29<F29T>::ACC;
-    const uint32_t N = plan[PLAN_N], L = plan[PLAN_L], T = plan[PLAN_T];   // written by k_part_plan
-    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    const bool final_level = (T == 1);
-    uint32_t beg = t * L;
-    uint32_t end = beg + L < N ? beg + L : N;
-    XYZZ29<F29T> acc;
-    bool inf = true;
-    // the next entry is fetched an iteration ahead: the table gather, whose address it holds, can go out as soon as the
-    // iteration starts instead of after a first memory round trip (CG_NO_ENTRY_PREFETCH: A/B aid)
-#if defined(CG_NO_ENTRY_PREFETCH)
-    uint32_t cur = (uint32_t)(entries[beg] >> 32);
-#else
-    uint64_t next_ent = entries[beg];
-    uint32_t cur = (uint32_t)(next_ent >> 32);
-#endif
-    bool first = true;
-    for (uint32_t k = beg; k < end; ++k) {
-#if defined(CG_NO_ENTRY_PREFETCH)
-        const uint64_t ent = entries[k];
-#else
-        const uint64_t ent = next_ent;
-        if (k + 1 < end) next_ent = entries[k + 1];
-#endif
-        const uint32_t key = (uint32_t)(ent >> 32), v = (uint32_t)ent;
-        if (key != cur) {
-            flush_run(cur, acc, inf, first, final_level, t, bucket_sums, part_keys, part_pts);
-            first = false;
-            inf = true;
-            cur = key;
-        }
-        Affine29<F29T> p = load_table_point_lazy_y(table, v & 0x7fffffffu, (v >> 31) != 0);
-        madd29(acc, inf, p);
-    }
-    if (final_level) {
-        store_acc(bucket_sums + (size_t)cur * ACC, acc, inf);
-    } else if (first) {  // the whole segment is one run
-        part_keys[2 * t] = cur;
-        store_acc(part_pts + (size_t)(2 * t) * ACC, acc, inf);
-        part_keys[2 * t + 1] = cur;
-        store_acc(part_pts + (size_t)(2 * t + 1) * ACC, acc, true);
-    } else {
-        part_keys[2 * t + 1] = cur;
-        store_acc(part_pts + (size_t)(2 * t + 1) * ACC, acc, inf);
-    }
-}
-
 // ---- G1 on SIGNED limbs (round 5): the kernel the prove path runs ---------------------------------------------------------
-// The same walk with the lane's running accumulator in the signed form of curve29.hpp (G1AccS / madd29s): the differences
-// of the mixed addition are fused into the products that precede them, the sign of a digit enters as a multiplier instead
-// of a negated y, and the sign of Y flips instead of being subtracted - ~140 of the ~2180 instructions of an addition go.
+// A lane walks its segment of the grouped entries, adds the table point of every entry to a running accumulator and flushes
+// the accumulator whenever the bucket key changes.  The accumulator is in the signed form of curve29.hpp (G1AccS / madd29s):
+// the differences of the mixed addition are fused into the products that precede them, the sign of a digit enters as a
+// multiplier instead of a negated y, and the sign of Y flips instead of being subtracted - ~140 of the ~2180 instructions of
+// an addition on unsigned limbs (round 4's kernel; profiles/r05_f_signed_vs_unsigned.txt) go.
 // A flushed run leaves as a SIGNED record (curve29.hpp store_acc_signed: the accumulator as it is, marked); load_acc brings
 // it to the stored (unsigned) invariant in the kernels that read it - a flush runs for a lane or two of a wave in 71 % of the
 // loop's iterations, so every instruction taken out of it is taken out of the loop.
+// (The template parameter only keeps the symbol k_accum_affine_g1s<256> that the profiles and tools/rocpd_*.py key on.)
 template <int BLOCK = 256>
-__global__ void __launch_bounds__(BLOCK) CG_ACCUM_ATTR k_accum_affine_g1s(const uint64_t* __restrict__ entries, const uint32_t* __restrict__ plan,
+__global__ void __launch_bounds__(BLOCK) k_accum_affine_g1s(const uint64_t* __restrict__ entries, const uint32_t* __restrict__ plan,
                                                           const uint32_t* __restrict__ table,
                                                           uint32_t* __restrict__ bucket_sums, uint32_t* __restrict__ part_keys,
                                                           uint32_t* __restrict__ part_pts) {
@@ -830,7 +769,9 @@ __global__ void __launch_bounds__(BLOCK) CG_ACCUM_ATTR k_accum_affine_g1s(const 
     uint32_t end = beg + L < N ? beg + L : N;
     G1AccS acc;
     bool inf = true;
-    uint64_t next_ent = entries[beg];                  // fetched an iteration ahead (see k_accum_affine)
+    // the next entry is fetched an iteration ahead: the table gather, whose address it holds, can go out as soon as the
+    // iteration starts instead of after a first memory round trip (profiles/r02_j_inflight_and_tuning.txt)
+    uint64_t next_ent = entries[beg];
     uint32_t cur = (uint32_t)(next_ent >> 32);
     bool first = true;
     for (uint32_t k = beg; k < end; ++k) {
@@ -958,7 +899,7 @@ k_accum_affine_g2(const uint64_t* __restrict__ entries, const uint32_t* __restri
     uint32_t beg = t * L;
     uint32_t end = beg + L < N ? beg + L : N;
     bool inf = true;
-    uint64_t next_ent = entries[beg];                  // fetched an iteration ahead, as in k_accum_affine
+    uint64_t next_ent = entries[beg];                  // fetched an iteration ahead, as in k_accum_affine_g1s
     uint32_t cur = (uint32_t)(next_ent >> 32);
     bool first = true;
     for (uint32_t k = beg; k < end; ++k) {
@@ -990,12 +931,7 @@ k_accum_affine_g2(const uint64_t* __restrict__ entries, const uint32_t* __restri
 // ---- the same over Fq2 with every value split over a lane pair (g2pair.hpp): accumulator in registers, no LDS -----------
 // Lanes 2p and 2p + 1 take segment p together; they share every branch (same entries, same keys), so the DPP exchanges
 // inside pr_madd always find their partner active.
-#if defined(CG_G2PAIR_WAVES)     // A/B aid: force the occupancy target
-#define CG_G2PAIR_ATTR __attribute__((amdgpu_waves_per_eu(CG_G2PAIR_WAVES, CG_G2PAIR_WAVES)))
-#else
-#define CG_G2PAIR_ATTR
-#endif
-__global__ void __launch_bounds__(256) CG_G2PAIR_ATTR
+__global__ void __launch_bounds__(256)
 k_accum_affine_g2_pair(const uint64_t* __restrict__ entries, const uint32_t* __restrict__ plan, const uint32_t* __restrict__ table,
                        uint32_t* __restrict__ bucket_sums, uint32_t* __restrict__ part_keys, uint32_t* __restrict__ part_pts) {
     constexpr int ACC = Words29<Fq2_29>::ACC;
@@ -1008,7 +944,7 @@ k_accum_affine_g2_pair(const uint64_t* __restrict__ entries, const uint32_t* __r
     const uint32_t end = beg + L < N ? beg + L : N;
     PairAcc acc;
     bool inf = true;
-    uint64_t next_ent = entries[beg];                  // fetched an iteration ahead, as in k_accum_affine
+    uint64_t next_ent = entries[beg];                  // fetched an iteration ahead, as in k_accum_affine_g1s
     uint32_t cur = (uint32_t)(next_ent >> 32);
     bool first = true;
     for (uint32_t k = beg; k < end; ++k) {
@@ -1054,13 +990,7 @@ static bool g2_pair_kernel(bool latency_mode) {
     if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
     return latency_mode;
 }
-}  // namespace cg
-// the batch-affine pair rounds (an experiment that measured 16-21 % slower, profiles/r03_s_batch_affine.txt) are only in
-// builds made with -DCG_WITH_BATCH_AFFINE (tools/ab_build.sh); the shipped library does not carry them
-#ifdef CG_WITH_BATCH_AFFINE
-#include "batchaff.hpp"
-#endif
-namespace cg {
+
 // threads per workgroup of the wave-per-unit kernels around the accumulation (k_combine_wave, k_bucket_chunks,
 // k_bucket_chunk_sums: no barrier, no LDS - any multiple of 64 is legal).  FOUR waves, not one (round 5): a 256-thread
 // workgroup lands one wave on each SIMD of a CU, single-wave workgroups are placed unevenly and their long dependent chains
@@ -1084,23 +1014,7 @@ static void launch_accum_affine(const uint64_t* entries, const uint32_t* plan, u
         if (!g2_pair_kernel(latency_mode)) k_accum_affine_g2<<<ceil_div(T_max, 256), 256, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
         else k_accum_affine_g2_pair<<<ceil_div(2ull * T_max, 256), 256, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
     } else {
-        // (tuning builds: CG_ACCUM_UNSIGNED=1 runs round 4's kernel on unsigned limbs - the A/B reference)
-        static const bool unsigned_ref = CG_TUNE_ENV("ACCUM_UNSIGNED") != nullptr && CG_TUNE_ENV("ACCUM_UNSIGNED")[0] == '1';
-        if (unsigned_ref) k_accum_affine<F29T><<<ceil_div(T_max, 256), 256, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
-        else {
-#ifdef CG_TUNING
-            // CG_ACCUM_BLOCK=64 / 128 / 512 / 1024: the kernel has no barrier, so any workgroup size is legal - smaller ones measure
-            // -3.5 % in the pipeline, 512 -0.6 %, 1024 -2 % (profiles/r05_ab_accum_workgroup_size.txt: a 256-thread workgroup puts one
-            // wave on each SIMD of a CU)
-            static const uint32_t blk = [] { const char* e = CG_TUNE_ENV("ACCUM_BLOCK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v == 64 || v == 128 || v == 512 || v == 1024 ? v : 0); }();
-            if (blk == 512) k_accum_affine_g1s<512><<<ceil_div(T_max, 512u), 512, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
-            else if (blk == 1024) k_accum_affine_g1s<1024><<<ceil_div(T_max, 1024u), 1024, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
-            else if (blk) k_accum_affine_g1s<256><<<ceil_div(T_max, blk), blk, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
-            else k_accum_affine_g1s<256><<<ceil_div(T_max, 256), 256, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
-#else
-            k_accum_affine_g1s<256><<<ceil_div(T_max, 256), 256, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
-#endif
-        }
+        k_accum_affine_g1s<256><<<ceil_div(T_max, 256), 256, 0, st>>>(entries, plan, table, bucket_sums, part_keys, part_pts);
     }
 }
 
@@ -1449,13 +1363,10 @@ __global__ void __launch_bounds__(256) k_bit_sums(const uint32_t* __restrict__ r
 // engine
 // ---------------------------------------------------------------------------------------------
 static constexpr uint32_t ACC_TARGET_THREADS = 256u * 4u * 4u * 64u;  // CUs x SIMDs x waves x lanes: one fully resident round
-// the G2 accumulation runs a lane PAIR per segment at CG_G2PAIR_WAVES waves per SIMD (g2pair.hpp): one resident round
-#if !defined(CG_G2PAIR_WAVES)
-#define CG_G2PAIR_RESIDENT_WAVES 2u
-#else
-#define CG_G2PAIR_RESIDENT_WAVES ((uint32_t)(CG_G2PAIR_WAVES))
-#endif
-static constexpr uint32_t ACC_TARGET_PAIRS = 256u * 4u * CG_G2PAIR_RESIDENT_WAVES * 64u / 2u;
+// the G2 accumulation runs a lane PAIR per segment (g2pair.hpp) at the two waves per SIMD that k_accum_affine_g2_pair's
+// 207 VGPRs allow: one resident round
+static constexpr uint32_t G2PAIR_RESIDENT_WAVES = 2;
+static constexpr uint32_t ACC_TARGET_PAIRS = 256u * 4u * G2PAIR_RESIDENT_WAVES * 64u / 2u;
 // segments of one fully resident round of the engine's accumulation kernel
 template <class F29T> static uint32_t acc_target_segments(bool latency_mode) {
     // CG_ACC_QUARTERS (tuning aid, throughput contexts): lanes of the largest accumulation launch in quarters of a resident
@@ -1534,36 +1445,6 @@ void MsmEngine<F>::init(const MsmBases<F>* b, hipStream_t zero_stream) {
             colp_buf.alloc((size_t)ceil_div(R, RED_CHUNK) * C * wins * ACC);
         }
     }
-#ifdef CG_WITH_BATCH_AFFINE
-    ba_rounds = 0;
-    if constexpr (Words29<F29T>::NF == 1) {
-        if (const char* e = CG_TUNE_ENV("BA_ROUNDS"); e && ba_allowed) ba_rounds = atoi(e) < 0 ? 0 : (atoi(e) > 6 ? 6 : atoi(e));
-        if (const char* e = CG_TUNE_ENV("BA_SLOTS")) { const int v = atoi(e); if (v >= 1 && v <= 1024) ba_B = (uint32_t)v; }
-    }
-    if (ba_rounds) {
-        uint64_t ncap = cap_entries, out1 = 0, out2 = 0;
-        for (int r = 0; r < ba_rounds; ++r) {
-            const uint64_t scap = (ncap + 1) / 2;
-            ba_tcap[r] = (uint32_t)((ceil_div(scap, (uint64_t)ba_B) + 63) & ~(uint64_t)63);
-            uint64_t ocap = scap + nbuckets_total;
-            if (ocap > ncap) ocap = ncap;
-            if (r == 0) out1 = ocap;
-            if (r == 1) out2 = ocap;
-            ncap = ocap;
-        }
-        const size_t lanes = ba_tcap[0], slots = (size_t)lanes * ba_B;
-        ba_prefix.alloc(slots * 9);
-        ba_split.alloc(slots / 64 + 1);
-        ba_exc.alloc(slots / 64 + 1);
-        ba_wpre.alloc(slots / 64 + 1);
-        ba_totals.alloc(lanes * 9);
-        ba_inv.alloc(lanes * 9);
-        ba_chain.alloc((lanes + BA_GROUP) * 9);
-        ba_rec_a.alloc((out1 + 1) * BA_REC);
-        ba_rec_b.alloc((out2 + 1) * BA_REC);
-        ba_plan.alloc((size_t)(ba_rounds + 1) * BAP_WORDS + PLAN_WORDS);
-    }
-#endif
     // both start out zeroed (load time: a synchronous memset); per MSM they are either re-zeroed by the MSM's own last
     // kernels (zero_at_end) or filled at its start
     // (On a stream of its own and WAITED for: hipMemset on device memory returns before the fill has run, and the legacy
@@ -1596,10 +1477,6 @@ void MsmEngine<F>::device_bytes(uint64_t& entries, uint64_t& pieces, uint64_t& o
     pieces += own_mem.piece_bytes();
     other += blk_hist.bytes() + counters.bytes() + starts.bytes() + bucket_sums.bytes() + rows_buf.bytes() + cols_buf.bytes() +
              rowp_buf.bytes() + colp_buf.bytes();
-#ifdef CG_WITH_BATCH_AFFINE
-    other += ba_prefix.bytes() + ba_totals.bytes() + ba_inv.bytes() + ba_chain.bytes() + ba_wpre.bytes() + ba_rec_a.bytes() +
-             ba_rec_b.bytes() + ba_plan.bytes() + ba_split.bytes() + ba_exc.bytes();
-#endif
 }
 
 static float elapsed_ms(hipEvent_t a, hipEvent_t b) {
@@ -1651,18 +1528,9 @@ void MsmEngine<F>::digits(const Fr* scalars_dev, uint64_t n, hipStream_t st) {
     PlanArgs pa;
     pa.start1 = start1; pa.chunk0 = chunk0; pa.target_threads = acc_target_segments<F29T>(latency_mode); pa.min_L = min_L;
     pa.two_level = bits2 ? 1 : 0;
-    static const bool plan_launch = CG_TUNE_ENV("PLAN_LAUNCH") != nullptr && CG_TUNE_ENV("PLAN_LAUNCH")[0] == '1';   // tuning builds: the reference path of the A/B
-    if (plan_launch) {
-        PlanArgs none = pa;
-        none.start1 = nullptr;
-        launch_part_level1(true, sh, tiles, (size_t)B1 * 4, st, scalars_dev, bases->valid.p, blk_hist.p, hist1, plan, nullptr, nullptr, nullptr, none);
-        CG_KERNEL_CHECK();
-        k_part_plan<<<1, 1024, (size_t)B1 * 4, st>>>(bits1, pa, hist1, plan);
-    } else {
-        launch_part_level1(true, sh, tiles, (size_t)B1 * 4, st, scalars_dev, bases->valid.p, blk_hist.p, hist1, plan, nullptr, nullptr, nullptr, pa);
-    }
+    launch_part_level1(true, sh, tiles, (size_t)B1 * 4, st, scalars_dev, bases->valid.p, blk_hist.p, hist1, plan, nullptr, nullptr, nullptr, pa);
     CG_KERNEL_CHECK();
-    launch_part_level1(false, sh, tiles, (size_t)B1 * 4, st, scalars_dev, bases->valid.p, blk_hist.p, nullptr, nullptr, start1, cur1, mem().ent_a.p);
+    launch_part_level1(false, sh, tiles, (size_t)B1 * 4, st, scalars_dev, bases->valid.p, blk_hist.p, nullptr, nullptr, start1, cur1, mem().ent_a.p, pa);
     CG_KERNEL_CHECK();
     if (bits2) {
         const uint32_t B2 = 1u << bits2;
@@ -1702,46 +1570,11 @@ void MsmEngine<F>::accumulate(hipStream_t st) {
         const uint32_t* plan = counters.p;
         const uint64_t* grouped = adopted ? adopted : this->grouped();
         CG_HIP(hipEventRecord(ev_t[3], st));
-#ifdef CG_WITH_BATCH_AFFINE
-        bool ba_done = false;
-        if constexpr (Words29<F29T>::NF == 1) {
-            if (ba_rounds) {
-                // R pair rounds (batchaff.hpp), then the XYZZ accumulation over what is left under its own plan
-                uint32_t* plan2 = ba_plan.p + (size_t)(ba_rounds + 1) * BAP_WORDS;
-                k_ba_begin<<<1, 1, 0, st>>>(plan, ba_plan.p, ba_B);
-                CG_KERNEL_CHECK();
-                const uint32_t* recs_in = nullptr;
-                for (int r = 0; r < ba_rounds; ++r) {
-                    const uint32_t* bp = ba_plan.p + (size_t)r * BAP_WORDS;
-                    const bool last = r + 1 == ba_rounds;
-                    uint32_t* out = (r & 1) ? ba_rec_b.p : ba_rec_a.p;
-                    const uint32_t grid = ceil_div(ba_tcap[r], 256u);
-                    if (r == 0) k_ba_forward<0><<<grid, 256, 0, st>>>(grouped, bases->table.p, nullptr, bp, ba_B, ba_prefix.p, ba_totals.p, ba_split.p, ba_exc.p);
-                    else k_ba_forward<1><<<grid, 256, 0, st>>>(nullptr, nullptr, recs_in, bp, ba_B, ba_prefix.p, ba_totals.p, ba_split.p, ba_exc.p);
-                    CG_KERNEL_CHECK();
-                    k_ba_scan<<<1, 1024, 0, st>>>(ba_split.p, ba_wpre.p, bp, last ? nullptr : ba_plan.p + (size_t)(r + 1) * BAP_WORDS, ba_B,
-                                                  last ? plan2 : nullptr, acc_target_segments<F29T>(latency_mode), min_L);
-                    CG_KERNEL_CHECK();
-                    k_ba_invert<<<ceil_div(ceil_div(ba_tcap[r], BA_GROUP), 64u), 64, 0, st>>>(ba_totals.p, bp, ba_chain.p, ba_inv.p);
-                    CG_KERNEL_CHECK();
-                    if (r == 0) k_ba_backward<0><<<grid, 256, 0, st>>>(grouped, bases->table.p, nullptr, bp, ba_B, ba_prefix.p, ba_inv.p, ba_split.p, ba_exc.p, ba_wpre.p, out);
-                    else k_ba_backward<1><<<grid, 256, 0, st>>>(nullptr, nullptr, recs_in, bp, ba_B, ba_prefix.p, ba_inv.p, ba_split.p, ba_exc.p, ba_wpre.p, out);
-                    CG_KERNEL_CHECK();
-                    recs_in = out;
-                }
-                k_accum_records<<<ceil_div(max_segments, 256u), 256, 0, st>>>(recs_in, plan2, bucket_sums.p, mem().part_keys_a.p, mem().part_pts_a.p);
-                CG_KERNEL_CHECK();
-                plan = plan2;
-                ba_done = true;
-            }
-        }
-        if (!ba_done)
-#endif
         // tuning builds: KNOCK_ACCUM leaves the accumulation AND the combine levels out (the pieces would be stale),
         // KNOCK_COMBINE the combine levels, KNOCK_TAIL the bucket reduction - wrong sums, the time of the rest
         static const bool knock_accum = CG_TUNE_ENV("KNOCK_ACCUM") != nullptr, knock_combine = CG_TUNE_ENV("KNOCK_COMBINE") != nullptr;
         if (!knock_accum)
-        launch_accum_affine<F29T>(grouped, plan, max_segments, bases->table.p, bucket_sums.p, mem().part_keys_a.p, mem().part_pts_a.p, latency_mode, st);
+            launch_accum_affine<F29T>(grouped, plan, max_segments, bases->table.p, bucket_sums.p, mem().part_keys_a.p, mem().part_pts_a.p, latency_mode, st);
         CG_KERNEL_CHECK();
         CG_HIP(hipEventRecord(ev_t[4], st));
         // combine the segments' pieces wave by wave until one wave covers them all (k_combine_wave); the grids cover the

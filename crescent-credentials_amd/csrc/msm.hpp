@@ -101,15 +101,6 @@ struct MsmEngine {
     bool zero_at_end = false;
     bool counters_clean = false, buckets_clean = false;
     bool latency_mode = false;        // set before init(): short segments (one proof at a time matters more than proofs per second)
-#ifdef CG_WITH_BATCH_AFFINE
-    // batch-affine pair rounds in front of the accumulation (batchaff.hpp; G1 only; 0 = off)
-    bool ba_allowed = true;           // set before init()
-    int ba_rounds = 0;
-    uint32_t ba_B = 32;               // slots chained per lane
-    uint32_t ba_tcap[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launch bound (lanes) of every round
-    DevBuf<uint32_t> ba_prefix, ba_totals, ba_inv, ba_chain, ba_wpre, ba_rec_a, ba_rec_b, ba_plan;
-    DevBuf<uint64_t> ba_split, ba_exc;
-#endif
     // valid once the stream has been synchronised
     uint32_t n_entries() const { return h_plan.p ? h_plan.p[0] : 0; }
     uint32_t n_nonzero() const { return h_plan.p ? h_plan.p[3] : 0; }

@@ -398,11 +398,7 @@ static int translate_exception() { return cg::translate_current_exception(); }
 extern "C" const char* cg_last_error(void) { return last_error().c_str(); }
 
 extern "C" const char* cg_version(void) {
-#ifdef CG_WITH_BATCH_AFFINE
-    return "crescent_gpu 0.1 (gfx950; BN254 Groth16 prove path: MSM G1/G2 + NTT + witness map) [experiment build: batch-affine]";
-#else
     return "crescent_gpu 0.1 (gfx950; BN254 Groth16 prove path: MSM G1/G2 + NTT + witness map)";
-#endif
 }
 
 extern "C" int cg_init(int n_devices, const int* device_ids) {
@@ -510,9 +506,6 @@ static std::unique_ptr<ProofSlot> make_slot(cg_ctx* c, const MsmBases<Fq>* bh, c
     for (auto& e : sl->ev_t) CG_HIP(hipEventCreate(&e));
     const bool latency = c->latency || lone;
     sl->eh.latency_mode = sl->el.latency_mode = sl->ea.latency_mode = sl->eb1.latency_mode = sl->eb2.latency_mode = latency;
-#ifdef CG_WITH_BATCH_AFFINE
-    if (CG_TUNE_ENV("BA_H_ONLY")) sl->el.ba_allowed = sl->ea.ba_allowed = sl->eb1.ba_allowed = false;   // experiment switch
-#endif
     if (serial) {
         sl->eh.shared_mem = sl->el.shared_mem = sl->ea.shared_mem = sl->eb1.shared_mem = sl->eb2.shared_mem = &sl->scratch;
         const bool zero_at_end = !(CG_TUNE_ENV("NO_ZERO_AT_END") && CG_TUNE_ENV("NO_ZERO_AT_END")[0] == '1');     // A/B aid (tuning builds)

@@ -150,7 +150,7 @@ def madd(F, inv, k):
     X2 = B(1.0, 1.0)
     Y2 = F.sub(B(0.0, 0.0), B(1.0, 1.0), 2, 1)             # table y, possibly negated: 2N - y ...
     if F is not Fq:
-        Y2 = F.norm(Y2)                                    # ... left lazy over Fq (load_table_point_lazy_y), normalised over Fq2
+        Y2 = F.norm(Y2)                                    # ... bounded as left lazy over Fq (looser than what load_table_point hands madd29: it normalises), normalised over Fq2
     U2 = F.mul(X2, ZZ1)
     S2 = F.mul(Y2, ZZZ1)
     P = F.norm(F.sub(U2, X1, k["KX"], 1))
