@@ -1249,13 +1249,13 @@ static constexpr uint32_t RED_CHUNK = 32;
 // lanes 32..63 its columns (-> colp[tile row][col]).  Both halves have read the whole tile when the loop ends, and nobody
 // else reads it, so the wave then ZEROES the tile (zero_after): the bucket array is left empty for the next MSM and the
 // fill launch that opened every accumulation is gone.
+// (bx, w: the workgroup's index among those of this bucket matrix, and the window - blockIdx.x / .y of a launch of its own)
 template <class F29T>
-__global__ void __launch_bounds__(256) k_bucket_chunks(uint32_t* __restrict__ buckets, uint32_t R, uint32_t C,
-                                                      uint32_t* __restrict__ rowp, uint32_t* __restrict__ colp, int zero_after) {
+__device__ __forceinline__ void bucket_chunks_block(const uint32_t bx, const uint32_t w, uint32_t* __restrict__ buckets, uint32_t R, uint32_t C,
+                                                    uint32_t* __restrict__ rowp, uint32_t* __restrict__ colp, int zero_after) {
     constexpr int ACC = Words29<F29T>::ACC;
-    const uint32_t w = blockIdx.y;
     const uint32_t KC = (C + RED_CHUNK - 1) / RED_CHUNK, KR = (R + RED_CHUNK - 1) / RED_CHUNK;
-    const uint32_t tile = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);      // a wave per tile, 1 or 4 waves per workgroup
+    const uint32_t tile = bx * (blockDim.x >> 6) + (threadIdx.x >> 6);      // a wave per tile, 1 or 4 waves per workgroup
     if (tile >= KR * KC) return;
     const uint32_t tr = tile / KC, tc = tile - tr * KC;
     const uint32_t lane = threadIdx.x & 63u, i = lane & 31u;
@@ -1289,15 +1289,20 @@ __global__ void __launch_bounds__(256) k_bucket_chunks(uint32_t* __restrict__ bu
         }
     }
 }
+template <class F29T>
+__global__ void __launch_bounds__(256) k_bucket_chunks(uint32_t* __restrict__ buckets, uint32_t R, uint32_t C,
+                                                      uint32_t* __restrict__ rowp, uint32_t* __restrict__ colp, int zero_after) {
+    bucket_chunks_block<F29T>(blockIdx.x, blockIdx.y, buckets, R, C, rowp, colp, zero_after);
+}
 // Row_r = Σ_k rowp[r][k] (KC chunks), Col_col = Σ_k colp[k][col] (KR chunks): one lane each
 template <class F29T>
-__global__ void __launch_bounds__(256) k_bucket_chunk_sums(const uint32_t* __restrict__ rowp, const uint32_t* __restrict__ colp, uint32_t R,
-                                                          uint32_t C, uint32_t* __restrict__ rows, uint32_t* __restrict__ cols) {
+__device__ __forceinline__ void bucket_chunk_sums_block(const uint32_t bx, const uint32_t w, const uint32_t* __restrict__ rowp,
+                                                        const uint32_t* __restrict__ colp, uint32_t R, uint32_t C,
+                                                        uint32_t* __restrict__ rows, uint32_t* __restrict__ cols) {
     constexpr int ACC = Words29<F29T>::ACC;
-    const uint32_t w = blockIdx.y;
     const uint32_t KC = (C + RED_CHUNK - 1) / RED_CHUNK, KR = (R + RED_CHUNK - 1) / RED_CHUNK;
     const uint32_t n_row = (R + 63u) & ~63u;
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t t = bx * blockDim.x + threadIdx.x;
     XYZZ29<F29T> acc;
     bool inf = true;
     if (t < n_row) {
@@ -1321,6 +1326,11 @@ __global__ void __launch_bounds__(256) k_bucket_chunk_sums(const uint32_t* __res
         store_acc(cols + ((size_t)w * C + col) * ACC, acc, inf);
     }
 }
+template <class F29T>
+__global__ void __launch_bounds__(256) k_bucket_chunk_sums(const uint32_t* __restrict__ rowp, const uint32_t* __restrict__ colp, uint32_t R,
+                                                          uint32_t C, uint32_t* __restrict__ rows, uint32_t* __restrict__ cols) {
+    bucket_chunk_sums_block<F29T>(blockIdx.x, blockIdx.y, rowp, colp, R, C, rows, cols);
+}
 
 // block b < rbits: Σ_{r: bit b of r} Row_r;  block rbits + k: Σ_{col: bit k of (col + 1)} Col_col;  blockIdx.y = window
 // `out` and `plan_out` are HOST memory (PinnedBuf::dev): the MSM's last kernel hands its few KB of per-bit sums and the
@@ -1328,19 +1338,21 @@ __global__ void __launch_bounds__(256) k_bucket_chunk_sums(const uint32_t* __res
 // zero_words != 0 (engines whose MSMs follow each other on one stream): this being the MSM's last kernel, it also leaves the
 // partition counters (`plan`, zero_words words: plan | histograms | cursors) zeroed for the next MSM - the fill launch that
 // opened every MSM before.
+// (b, w: the block's index among the nbits = rbits + cbits1 blocks of a window, and the window, of `wins` - blockIdx.x / .y of
+// a launch of its own)
 template <class F29T>
-__global__ void __launch_bounds__(256) k_bit_sums(const uint32_t* __restrict__ rows, uint32_t R, uint32_t rbits,
-                                                  const uint32_t* __restrict__ cols, uint32_t C, uint32_t* __restrict__ out,
-                                                  uint32_t* plan, uint32_t* __restrict__ plan_out, uint32_t zero_words) {
+__device__ __forceinline__ void bit_sums_block(const uint32_t b, const uint32_t w, const uint32_t nbits, const uint32_t wins,
+                                               const uint32_t* __restrict__ rows, uint32_t R, uint32_t rbits,
+                                               const uint32_t* __restrict__ cols, uint32_t C, uint32_t* __restrict__ out,
+                                               uint32_t* plan, uint32_t* __restrict__ plan_out, uint32_t zero_words) {
     constexpr int ACC = Words29<F29T>::ACC;
     extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
-    const uint32_t w = blockIdx.y, b = blockIdx.x;
     if (w == 0 && b == 0 && threadIdx.x < PLAN_WORDS) {
         plan_out[threadIdx.x] = plan[threadIdx.x];
         if (zero_words) plan[threadIdx.x] = 0;
     }
     if (zero_words) {
-        const uint32_t nthr = gridDim.x * gridDim.y * blockDim.x, me = (w * gridDim.x + b) * blockDim.x + threadIdx.x;
+        const uint32_t nthr = nbits * wins * blockDim.x, me = (w * nbits + b) * blockDim.x + threadIdx.x;
         for (uint32_t k = PLAN_WORDS + me; k < zero_words; k += nthr) plan[k] = 0;
     }
     const bool is_row = b < rbits;
@@ -1356,7 +1368,56 @@ __global__ void __launch_bounds__(256) k_bit_sums(const uint32_t* __restrict__ r
         }
     }
     block_tree_sum(acc, inf, sm);
-    if (threadIdx.x == 0) store_acc(out + ((size_t)w * gridDim.x + b) * ACC, acc, inf);
+    if (threadIdx.x == 0) store_acc(out + ((size_t)w * nbits + b) * ACC, acc, inf);
+}
+template <class F29T>
+__global__ void __launch_bounds__(256) k_bit_sums(const uint32_t* __restrict__ rows, uint32_t R, uint32_t rbits,
+                                                  const uint32_t* __restrict__ cols, uint32_t C, uint32_t* __restrict__ out,
+                                                  uint32_t* plan, uint32_t* __restrict__ plan_out, uint32_t zero_words) {
+    bit_sums_block<F29T>(blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, rows, R, rbits, cols, C, out, plan, plan_out, zero_words);
+}
+
+// The same three kernels over the bucket sets of up to RED_BATCH_MAX engines at once (one window each: precomputed tables): the
+// G1 MSMs of a proof on a one-stream slot leave their buckets un-reduced and ONE chain of three launches reduces them all.
+// Each of these kernels is a serial chain of additions per lane, ~0.2 - 0.3 ms however few its waves, and three of a proof's
+// four G1 bucket sets are 64 tiles: four chains one after another cost four times what one costs.  A workgroup finds its job
+// from the jobs' block counts and then does, statement for statement, what a block of the job's own launch does.
+static constexpr int RED_BATCH_MAX = 4;
+struct RedJob {
+    uint32_t *buckets, *rowp, *colp, *rows, *cols;
+    uint32_t *out, *plan, *plan_out;        // out, plan_out: host memory (see k_bit_sums)
+    uint32_t R, C, rbits, cbits1;
+    uint32_t zero_words;                    // != 0: leave the buckets and the partition counters zeroed (zero_at_end)
+};
+struct RedBatch {
+    RedJob job[RED_BATCH_MAX];
+    uint32_t end[RED_BATCH_MAX];            // job j's blocks are [end[j - 1], end[j]) of the launch
+    uint32_t n;
+};
+// -> the job of this workgroup; bx: the workgroup's index within it
+__device__ __forceinline__ uint32_t red_batch_job(const RedBatch& B, uint32_t& bx) {
+    uint32_t j = 0;
+    bx = blockIdx.x;
+    while (j + 1 < B.n && blockIdx.x >= B.end[j]) bx = blockIdx.x - B.end[j++];
+    return j;
+}
+template <class F29T>
+__global__ void __launch_bounds__(256) k_bucket_chunks_batch(const RedBatch B) {
+    uint32_t bx;
+    const RedJob& J = B.job[red_batch_job(B, bx)];
+    bucket_chunks_block<F29T>(bx, 0u, J.buckets, J.R, J.C, J.rowp, J.colp, J.zero_words ? 1 : 0);
+}
+template <class F29T>
+__global__ void __launch_bounds__(256) k_bucket_chunk_sums_batch(const RedBatch B) {
+    uint32_t bx;
+    const RedJob& J = B.job[red_batch_job(B, bx)];
+    bucket_chunk_sums_block<F29T>(bx, 0u, J.rowp, J.colp, J.R, J.C, J.rows, J.cols);
+}
+template <class F29T>
+__global__ void __launch_bounds__(256) k_bit_sums_batch(const RedBatch B) {
+    uint32_t bx;
+    const RedJob& J = B.job[red_batch_job(B, bx)];
+    bit_sums_block<F29T>(bx, 0u, J.rbits + J.cbits1, 1u, J.rows, J.R, J.rbits, J.cols, J.C, J.out, J.plan, J.plan_out, J.zero_words);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1558,10 +1619,20 @@ void MsmEngine<F>::adopt(const uint64_t* grouped_entries, const uint32_t* plan_d
     adopted = n ? grouped_entries : nullptr;
 }
 
+// A/B aid (tuning builds): the LDS-tree reduction for every engine
+static bool red_force_tree() {
+    static const bool v = CG_TUNE_ENV("RED_TREE") != nullptr;
+    return v;
+}
+
 // phase 2: accumulate the grouped entries into the buckets, combine the segments, reduce the buckets; the per-bit sums
 // and the plan (entry count, statistics) are copied to pinned memory.  Nothing here waits for the host.
+// defer_reduction (G1 engines of a one-stream slot): stop after the combine levels - the buckets keep the MSM's sums until
+// enqueue_reduction_batch reduces them with the other G1 bucket sets of the proof.  An engine the batched kernels do not
+// serve (the LDS-tree reduction of latency engines, a bucket set per window, no scalars at all) reduces here all the same.
 template <class F>
-void MsmEngine<F>::accumulate(hipStream_t st) {
+void MsmEngine<F>::accumulate(hipStream_t st, bool defer_reduction) {
+    reduction_pending = false;
     // the bucket array is empty when the accumulation starts: left so by the reduction of this engine's previous MSM
     // (k_bucket_chunks, zero_at_end) or filled here
     if (!buckets_clean) fill_zero(bucket_sums.p, bucket_sums.bytes(), st);
@@ -1598,7 +1669,8 @@ void MsmEngine<F>::accumulate(hipStream_t st) {
     // thread while it is open (a context being freed or loaded next to a context's first proof: "operation failed due
     // to a previous error during capture", met by tests/test_gpu_e2e_files.py under concurrent callers).  No capture, no
     // such window (profiles/r03_j_reduction_graph.txt).
-    enqueue_reduction(st);
+    if (defer_reduction && n_scalars && bases->precomputed && !latency_mode && !red_force_tree()) reduction_pending = true;
+    else enqueue_reduction(st);
     CG_HIP(hipEventRecord(ev_t[5], st));
 }
 
@@ -1608,7 +1680,7 @@ void MsmEngine<F>::enqueue_reduction(hipStream_t st) {
     const uint32_t nb = 1u << (bases->c - 1);
     const uint32_t C = 1u << red_cbits(bases->c), R = nb / C;
     const size_t lds = (size_t)256 * ACC * 4;
-    static const bool force_tree = CG_TUNE_ENV("RED_TREE") != nullptr;      // A/B aid (tuning builds)
+    const bool force_tree = red_force_tree();
     static const bool knock_tail = CG_TUNE_ENV("KNOCK_TAIL") != nullptr;
     if (knock_tail) return;             // buckets_clean / counters_clean stay false: the next MSM fills them
     if (latency_mode || force_tree) {   // a block per row / column with an LDS tree: depth log, more additions
@@ -1629,6 +1701,56 @@ void MsmEngine<F>::enqueue_reduction(hipStream_t st) {
                                                           h_plan.dev(), zero_at_end ? (uint32_t)counters.n : 0u);
     CG_KERNEL_CHECK();
     counters_clean = zero_at_end;
+}
+
+// ONE chain of the three reduction launches for those of `engines` whose accumulate() deferred its reduction; each of them
+// is left as its own enqueue_reduction leaves it.  ev_t[5] of the LAST of them is recorded again behind the chain: its
+// ms_total() carries the chain's time (the others' end with their combine levels).
+void enqueue_reduction_batch(MsmEngine<Fq>* const* engines, int n, hipStream_t st) {
+    typedef MsmEngine<Fq>::F29T F29T;
+    constexpr int ACC = MsmEngine<Fq>::ACC;
+    static const bool knock_tail = CG_TUNE_ENV("KNOCK_TAIL") != nullptr;
+    const uint32_t tb = tail_block<F29T>();
+    RedBatch chunks, sums, bits;
+    MsmEngine<Fq>* in[RED_BATCH_MAX];
+    uint32_t m = 0;
+    for (int k = 0; k < n; ++k) {
+        MsmEngine<Fq>* e = engines[k];
+        if (!e || !e->reduction_pending) continue;
+        e->reduction_pending = false;
+        if (knock_tail) continue;             // as enqueue_reduction: the next MSM fills buckets and counters
+        if (m == RED_BATCH_MAX) throw HipError(CG_ERR_INVALID_ARGUMENT, "more bucket sets than one reduction batch holds");
+        const uint32_t nb = 1u << (e->bases->c - 1);
+        RedJob J;
+        J.C = 1u << red_cbits(e->bases->c); J.R = nb / J.C;
+        J.rbits = (uint32_t)e->red_rbits; J.cbits1 = (uint32_t)e->red_cbits1;
+        J.buckets = e->bucket_sums.p; J.rowp = e->rowp_buf.p; J.colp = e->colp_buf.p; J.rows = e->rows_buf.p; J.cols = e->cols_buf.p;
+        J.out = e->h_result.dev(); J.plan = e->counters.p; J.plan_out = e->h_plan.dev();
+        J.zero_words = e->zero_at_end ? (uint32_t)e->counters.n : 0u;
+        const uint32_t KC = ceil_div(J.C, RED_CHUNK), KR = ceil_div(J.R, RED_CHUNK);
+        const uint32_t lanes_b = ((J.R + 63u) & ~63u) + J.C;
+        const uint32_t e0 = m ? chunks.end[m - 1] : 0u, e1 = m ? sums.end[m - 1] : 0u, e2 = m ? bits.end[m - 1] : 0u;
+        chunks.job[m] = sums.job[m] = bits.job[m] = J;
+        chunks.end[m] = e0 + ceil_div(KR * KC, tb / 64u);
+        sums.end[m] = e1 + ceil_div(lanes_b, tb);
+        bits.end[m] = e2 + J.rbits + J.cbits1;
+        in[m++] = e;
+    }
+    if (!m) return;
+    for (uint32_t k = m; k < RED_BATCH_MAX; ++k) {     // (never read: a defined kernel argument all the same)
+        chunks.job[k] = sums.job[k] = bits.job[k] = chunks.job[0];
+        chunks.end[k] = chunks.end[m - 1]; sums.end[k] = sums.end[m - 1]; bits.end[k] = bits.end[m - 1];
+    }
+    chunks.n = sums.n = bits.n = m;
+    k_bucket_chunks_batch<F29T><<<chunks.end[m - 1], tb, 0, st>>>(chunks);
+    CG_KERNEL_CHECK();
+    for (uint32_t k = 0; k < m; ++k) in[k]->buckets_clean = in[k]->zero_at_end;
+    k_bucket_chunk_sums_batch<F29T><<<sums.end[m - 1], tb, 0, st>>>(sums);
+    CG_KERNEL_CHECK();
+    k_bit_sums_batch<F29T><<<bits.end[m - 1], 256, (size_t)256 * ACC * 4, st>>>(bits);
+    CG_KERNEL_CHECK();
+    for (uint32_t k = 0; k < m; ++k) in[k]->counters_clean = in[k]->zero_at_end;
+    CG_HIP(hipEventRecord(in[m - 1]->ev_t[5], st));
 }
 
 // ---- host: lazy 29-bit accumulator -> saturated Montgomery(2^256) XYZZ ---------------------------------

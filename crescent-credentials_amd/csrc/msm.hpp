@@ -105,8 +105,11 @@ struct MsmEngine {
     uint32_t n_entries() const { return h_plan.p ? h_plan.p[0] : 0; }
     uint32_t n_nonzero() const { return h_plan.p ? h_plan.p[3] : 0; }
     void enqueue_reduction(hipStream_t st);
+    // accumulate(st, true) left the buckets un-reduced: enqueue_reduction_batch owes this engine its reduction
+    bool reduction_pending = false;
     // timing events (recorded on the MSM's own stream): digits start, sort begin/end, level-1
-    // accumulation kernel begin/end, result ready
+    // accumulation kernel begin/end, result ready (an engine whose reduction is deferred: combine levels done; the last
+    // engine of a batch: the batched reduction done)
     hipEvent_t ev_t[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     float ms_total() const;   // digits start -> result ready (valid after the stream is synchronised)
     float ms_sort() const;
@@ -134,10 +137,15 @@ struct MsmEngine {
     const uint64_t* adopted = nullptr;    // non-null: the grouped entries of the engine adopted for the current MSM
     // phase 2: accumulate, combine, reduce; per-bit sums and the plan copied to pinned memory.  Neither phase waits
     // for the host.
-    void accumulate(hipStream_t st);
+    // defer_reduction: the bucket reduction is left to enqueue_reduction_batch where the batched kernels serve this engine
+    void accumulate(hipStream_t st, bool defer_reduction = false);
     // after the stream has been synchronised: the MSM value (host arithmetic, Montgomery 2^256 form)
     XYZZ<F> value() const;
 };
+
+// One chain of reduction launches on `st` for the engines among `engines` (null entries allowed) whose last accumulate()
+// deferred its bucket reduction; what the host reads of an engine afterwards is what its own reduction would have left.
+void enqueue_reduction_batch(MsmEngine<Fq>* const* engines, int n, hipStream_t st);
 
 // Two changes of basis made ONCE per key so that a proof needs four transforms instead of seven (G1 only).
 //

@@ -1243,6 +1243,11 @@ static int knock_mask() {
 //   phase 1   one-stream slot: all four MSMs, grouped and accumulated one after another on stream 0.
 //             five-stream slot: streams 1-4 wait for what stream 0 holds; the digits of l, a, b1, b2 on streams 1-4.
 //   phase 2   five-stream slot: the four accumulations (each waits for its own entry count).  one-stream slot: nothing.
+//   tails     one-stream slot of an unsharded context, after the h accumulation: ONE batched chain reduces the bucket sets of
+//             l, a, b1 and h, whose accumulations left them un-reduced (defer; msm.hip enqueue_reduction_batch).  The
+//             engines keep their own bucket arrays, counters and result buffers, so nothing needs a reduction before the next
+//             MSM starts - only before collect() waits.  Five-stream slots, shards, the two-call form: every MSM reduces
+//             its own buckets as it ends.
 // operands (prover.rs:70-74, 84-89, 265-266):  l: l_query[i] x w[l + i];  a, b1, b2: query[1 + i] x w[1 + i]
 struct Schedule {
     ProofSlot* const S;
@@ -1250,7 +1255,9 @@ struct Schedule {
     uint64_t n_l, n_a;
     bool run_l, run_a, run_b1, run_b2;     // all but b1 (a proof with r = 0 skips it, prover.rs:102-112) run outside KNOCK runs
     bool b2_adopts;
+    bool defer;
     Schedule(const cg_ctx* c, ProofSlot* slot, const Fr* w_dev, bool skip_b1) : S(slot) {
+        defer = S->one_stream && c->shard_count == 1;
         w_l = w_dev + (c->folded ? 0 : c->l) + c->rl.lo;          // folded l query: one base per wire
         w_a = w_dev + 1 + c->ra.lo;
         n_l = c->rl.hi - c->rl.lo;
@@ -1266,11 +1273,11 @@ struct Schedule {
         if (S->one_stream) {
             // every MSM grouped and accumulated before the next one starts: the engines share the slot's scratch (entry
             // lists, segment pieces), which is what a slot's memory mostly is
-            if (run_l) { S->el.digits(w_l, n_l, s0); S->el.accumulate(s0); }
-            if (run_a) { S->ea.digits(w_a, n_a, s0); S->ea.accumulate(s0); }
+            if (run_l) { S->el.digits(w_l, n_l, s0); S->el.accumulate(s0, defer); }
+            if (run_a) { S->ea.digits(w_a, n_a, s0); S->ea.accumulate(s0, defer); }
             if (run_b1) S->eb1.digits(w_a, n_a, s0);
             if (b2_adopts) S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, s0);    // b1's list is still in the scratch ...
-            if (run_b1) S->eb1.accumulate(s0);
+            if (run_b1) S->eb1.accumulate(s0, defer);
             if (run_b2 && !b2_adopts) S->eb2.digits(w_a, n_a, s0);
             if (run_b2) S->eb2.accumulate(s0);                                             // ... until here
             return;
@@ -1294,6 +1301,12 @@ struct Schedule {
         if (run_a) S->ea.accumulate(S->st[2]);
         if (run_b1) S->eb1.accumulate(S->st[3]);
         if (run_b2) S->eb2.accumulate(S->st[4]);
+    }
+    // run_h: the h MSM was queued (with `defer`), the last G1 accumulation of the stream
+    void tails(bool run_h) const {
+        if (!defer) return;
+        MsmEngine<Fq>* const g1[4] = {run_l ? &S->el : nullptr, run_a ? &S->ea : nullptr, run_b1 ? &S->eb1 : nullptr, run_h ? &S->eh : nullptr};
+        enqueue_reduction_batch(g1, 4, S->st[0]);
     }
 };
 
@@ -1355,7 +1368,8 @@ static int prove_partial_impl(cg_ctx* c, ProofSlot* S, const Fr* w_dev, bool ski
     if (tm) CG_HIP(hipEventRecord(S->ev_t[1], s0));
     if (!(knock & 32)) S->eh.digits(h_scalars, c->rh.hi - c->rh.lo, s0);
     sch.phase2();
-    if (!(knock & 32)) S->eh.accumulate(s0);
+    if (!(knock & 32)) S->eh.accumulate(s0, sch.defer);
+    sch.tails(!(knock & 32));
     if (while_gpu_runs) (*while_gpu_runs)();      // host work that needs no MSM value
     return collect(c, S, !sch.run_b1, supplied != nullptr, true, t0, P, tm, ts);
 }

@@ -178,7 +178,9 @@ enum {
 typedef struct cg_timings {
     float upload_ms;       /* host -> device copy of the assignment (0 for *_dev entry points) */
     float witness_map_ms;  /* "R1CS to QAP witness map" */
-    float msm_h_ms;        /* "Compute C": h_query MSM */
+    float msm_h_ms;        /* "Compute C": h_query MSM.  A throughput context reduces the buckets of its four G1 MSMs in ONE
+                            * batched chain behind the h MSM, the last on the proof's stream: that chain's time is counted
+                            * here, and msm_l_ms, msm_a_ms, msm_b1_ms then end with the MSM's last combine level */
     float msm_l_ms;        /* "Compute C": l_query MSM */
     float msm_a_ms;        /* "Compute A" */
     float msm_b1_ms;       /* "Compute B in G1" */
