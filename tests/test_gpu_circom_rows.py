@@ -3,8 +3,8 @@
 The instances (tests/circom_rows.py) carry rows at every boundary of the sliced sparse product (wmap29.hip k_sell29, up to
 8 levels of 8-term pieces), transposed columns of exactly 4096 and 4097 terms (the setup's k_spmv / k_spmv_long split in
 ntt.hip), a wire repeated hundreds of times in one row and pairs c, r - c on one (row, wire) (the doubling and cancelling
-branches of the C fold, ecntt.hip k_ec_terms + msm.hip sum_xyzz_by_key), and a row of exactly 8^8 terms, the longest the
-layout holds.  Two sizes: SMALL (D = 2^8) where the Python oracle is affordable, MEDIUM (D = 2^17, ~3.8 M terms, a
+branches of the G1 C fold only, ecntt.hip k_ec_terms + msm.hip sum_xyzz_by_key; the same-x branches of the G2 bucket
+accumulations are tests/test_gpu_g2_coincident.py's), and a row of exactly 8^8 terms, the longest the layout holds.  Two sizes: SMALL (D = 2^8) where the Python oracle is affordable, MEDIUM (D = 2^17, ~3.8 M terms, a
 dictionary of more than 2^20 coefficients in A)."""
 import hashlib
 import random
