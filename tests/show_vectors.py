@@ -162,3 +162,114 @@ def jwt_like_layout(ell):
     for i in range(2, min(ell, 2 + max(1, ell // 4))):
         io[i] = HIDDEN
     return io
+
+
+# ---- value-level vectors for showings (tests/test_verify_values_cpu.py, tests/test_gpu_verify_values.py) ---------------
+def clone(sh: Show, **kw) -> Show:
+    d = dict(rand_proof=sh.rand_proof, com_hidden=sh.com_hidden, committed=list(sh.committed), c=sh.c, s=[list(si) for si in sh.s],
+             revealed=list(sh.revealed))
+    d.update(kw)
+    return Show(**d)
+
+
+# challenges around the ends of k_show_terms' double-and-add: it starts at bit 253, make_show draws c < 2^248
+C_VALUES = [0, 1, (1 << 248) - 1, 1 << 253, R - 1]
+
+
+def pattern_showings(sh: Show, patterns):
+    """len(patterns) copies of an accepting showing with c overwritten by C_VALUES in rotation and response j of copy v by
+    pattern (j + v) mod len(patterns): every response table meets every pattern.  No valid proofs of knowledge, and they
+    need not be: the Groth16 verdict depends on neither c nor s, and k is whatever dlog.rs:137-145 recomputes."""
+    out = []
+    for v in range(len(patterns)):
+        s, j = [], 0
+        for si in sh.s:
+            s.append([patterns[(j + t + v) % len(patterns)][1] for t in range(len(si))])
+            j += len(si)
+        out.append(clone(sh, c=C_VALUES[v % len(C_VALUES)], s=s))
+    return out
+
+
+def check_chain(vk, io_types, sh: Show):
+    """k_show_check's chain: gamma_abc[0] + com_hidden + committed points + revealed partials -> (events, prepared inputs)"""
+    import verify_vectors as V
+    gabc = vk["gamma_abc_g1"]
+    rev = [gabc[i + 1] for i, t in enumerate(io_types) if t == REVEALED]
+    return V.chain_events(gabc[0], [sh.com_hidden] + list(sh.committed) + [_aff(_mul(P, x)) for P, x in zip(rev, sh.revealed)])
+
+
+def k_chain(vk, io_types, sh: Show, i):
+    """k_show_k's chain of statement i: c·y_i + s_i0·base_i0 + s_i1·base_i1 + ... -> (events, k_i)"""
+    import verify_vectors as V
+    bases = verifier_bases(vk, io_types)[i]
+    return V.chain_events(_aff(_mul(sh.y[i], sh.c)), [_aff(_mul(P, s)) for P, s in zip(bases, sh.s[i])])
+
+
+def coincident_show_cases():
+    """honest (accepting) showings under one gamma = 1 key and the layout [C, C, H, R, R, R] whose partial sums coincide
+    inside k_show_check's chain or inside one statement's k_show_k chain, by the choice of z, the commitment randomness or
+    the nonces.  Returns (vk, io_types, two ordinary showings, [(name, Show, chain, expected events, final sum is O)]) with
+    chain = "check" or the statement index."""
+    import random
+    import verify_vectors as V
+    rng = random.Random(0x5C01)
+    inv = lambda v: pow(v, R - 2, R)
+    alpha, beta, delta = (rng.randrange(1, R) for _ in range(3))
+    ks = [rng.randrange(1, R) for _ in range(7)]
+    xs = [rng.randrange(1, R) for _ in range(6)]
+    sc = (alpha, beta, 1, delta, ks)
+    vk = V.synthetic_vk(*sc[:4], ks)
+    proof = V.synthetic_proof(sc, xs, a=rng.randrange(1, R), b=rng.randrange(1, R))
+    io = jwt_like_layout(6)
+    assert io == [COMMITTED, COMMITTED, HIDDEN, REVEALED, REVEALED, REVEALED]
+    di = inv(delta)
+    r0, r1, z, c = rng.randrange(1, R), rng.randrange(1, R), rng.randrange(1, R), rng.randrange(1, 1 << 248)
+    hid = lambda zz: (xs[2] * ks[3] + zz * delta) % R          # com_hidden's scalar
+    y0 = lambda rr: (xs[0] * ks[1] + rr * delta) % R           # committed[0]'s scalar
+    y1 = (xs[1] * ks[2] + r1 * delta) % R
+    show = lambda **kw: make_show(vk, proof, xs, io, rng, **dict(dict(rs=[r0, r1], z=z, c=c), **kw))
+    ordinary = [make_show(vk, proof, xs, io, rng), make_show(vk, proof, xs, io, rng)]
+    cases = []
+    # k_show_check: g0, then madd(com_hidden), madd(committed[0]), madd(committed[1]), add(revealed partials)
+    cases.append(("com_hidden = g0: madd's dbl_affine branch", show(z=(ks[0] - xs[2] * ks[3]) * di % R), "check",
+                  ["double", "add", "add", "add", "add", "add"], False))
+    cases.append(("com_hidden = -g0: O, then committed[0] restarts the chain", show(z=(-ks[0] - xs[2] * ks[3]) * di % R), "check",
+                  ["cancel", "restart", "add", "add", "add", "add"], False))
+    cases.append(("committed[0] = g0 + com_hidden", show(rs=[(ks[0] + hid(z) - xs[0] * ks[1]) * di % R, r1]), "check",
+                  ["add", "double", "add", "add", "add", "add"], False))
+    zz = (xs[3] * ks[4] - ks[0] - xs[2] * ks[3] - y0(r0) - y1) * di % R
+    cases.append(("the first revealed partial equals the running sum", show(z=zz), "check",
+                  ["add", "add", "add", "double", "add", "add"], False))
+    # k_show_k: c·y, then add(s_0·base_0), add(s_1·base_1), with s_j = rho_j - c·secret_j
+    for stmt, base0, secret0, secret1, ysc, what in ((0, ks[1], xs[0], r0, y0(r0), "committed statement 0"),
+                                                      (2, ks[3], xs[2], z, hid(z), "the hidden statement")):
+        cy = c * ysc % R
+        rho1 = rng.randrange(1, R)
+        s1 = (rho1 - c * secret1) % R
+        assert s1
+        s0 = cy * inv(base0) % R
+        cases.append(("%s: s_0 base_0 = c y, a doubling at the first add" % what, show(rho={stmt: [(s0 + c * secret0) % R, rho1]}),
+                      stmt, ["double", "add"], False))
+        cases.append(("%s: s_0 base_0 = -c y, s_1 base_1 != O: O mid-chain, k != O" % what,
+                      show(rho={stmt: [(-s0 + c * secret0) % R, rho1]}), stmt, ["cancel", "restart"], False))
+    rho0 = rng.randrange(1, R)
+    s0 = (rho0 - c * xs[2]) % R
+    cy = c * hid(z) % R
+    s1 = (cy + s0 * ks[3]) * di % R
+    cases.append(("the hidden statement: s_1 base_1 = c y + s_0 base_0, a doubling at the second add",
+                  show(rho={2: [rho0, (s1 + c * z) % R]}), 2, ["add", "double"], False))
+    s1 = (cy - s0 * ks[3]) * di % R
+    cases.append(("the hidden statement: s_0 base_0 + s_1 base_1 = c y, so k = 2 c y by plain additions",
+                  show(rho={2: [rho0, (s1 + c * z) % R]}), 2, ["add", "add"], False))
+    return vk, io, ordinary, cases
+
+
+def pattern_show_base():
+    """(vk, io_types, an accepting showing) for pattern_showings: the `mixed` layout with ell = 6 under a gamma = 1 key"""
+    import verify_vectors as V
+    rng, sc = V.synthetic_scalars(6, 0x5A77, gamma=1)
+    xs = [rng.randrange(R) for _ in range(6)]
+    vk = V.synthetic_vk(*sc[:4], sc[4])
+    proof = V.synthetic_proof(sc, xs, a=rng.randrange(1, R), b=rng.randrange(1, R))
+    io = jwt_like_layout(6)
+    return vk, io, make_show(vk, proof, xs, io, rng)
