@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <chrono>
 #include <mutex>
 #include <shared_mutex>
 #include <stdexcept>
@@ -236,6 +237,10 @@ void fill_zero(void* dst, size_t bytes, hipStream_t st);
 
 inline uint32_t ceil_div(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 inline int ilog2_ceil(uint64_t n) { int l = 0; while ((1ull << l) < n) ++l; return l; }
+// host-clock milliseconds since t0 (load timings; a timing that ends in a synchronisation)
+inline float ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // ---- host-side byte <-> field conversions --------------------------------------------------------
 template <class F>

@@ -1884,10 +1884,6 @@ __global__ void __launch_bounds__(256) k_gather_points(const uint32_t* __restric
     out_valid[k] = valid[j];
 }
 
-static float ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // h query -> coset evaluation basis (ecntt.hip), then the usual window rows over the slice h_first + k·h_stride, k < h_count
 void build_h_bases_folded(MsmBases<Fq>& out_h, const uint32_t* h_row0, const uint8_t* h_valid, uint64_t n_h, int logn, uint64_t h_first,
                           uint64_t h_stride, uint64_t h_count, int c_h, hipStream_t st, float* ms_fold, float* ms_tables) {

@@ -122,6 +122,25 @@ using namespace cg;
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
+// The five MSMs of a proof, in the order the ABI uses everywhere: cg_ctx_info.window_bits[5], the 384-byte partials record,
+// ProofSlot::st[0..4].  The first four are over G1, the last over G2.
+enum Query { Q_H = 0, Q_L, Q_A, Q_B1, Q_B2, N_QUERIES, N_G1 = Q_B2 };
+
+// f(q, x...) for each of the five, in that order, x being query q's member of every set given: the tables of a KeyTables,
+// the engines of a ProofSlot, the sums of a Partials (a generic lambda takes the Fq / Fq2 split)
+template <class Fn, class... Sets>
+static void each_query(Fn f, Sets&... sets) {
+    for (int q = 0; q < N_G1; ++q) f(q, sets.g1[q]...);
+    f((int)Q_B2, sets.b2...);
+}
+
+// The window tables of the key's five queries in one arrangement.  A context holds the arrangement in force; a staged load's
+// worker builds the final one beside it and swaps the two (staged_worker).
+struct KeyTables {
+    MsmBases<Fq> g1[N_G1];
+    MsmBases<Fq2> b2;
+};
+
 // Per-proof working set: everything a proof in flight writes.  A context owns `n_slots` of them so that
 // several proofs can overlap on one GPU (the latency-bound tails of one proof hide under the bulk kernels
 // of another); the key tables, matrices and NTT tables are shared and read-only.
@@ -133,8 +152,8 @@ struct ProofSlot {
     // one-stream slots: the five MSMs of a proof run one after another, so their entry lists and segment pieces live in
     // ONE scratch sized for the largest (declared before the engines that point into it: destroyed after them)
     MsmScratch scratch;
-    MsmEngine<Fq> eh, el, ea, eb1;
-    MsmEngine<Fq2> eb2;
+    MsmEngine<Fq> g1[N_G1];            // h, l, a, b1 (Query)
+    MsmEngine<Fq2> b2;
     DevBuf<Fr> h_canon;
     DevBuf<Fr> q2;                     // cg_prove_partial_q_finish2: the second side's slice when it arrives in host memory (made on first use)
     const Fr* knock_h = nullptr;       // tuning builds (KNOCK & 16): the h scalars of this slot's first proof, reused
@@ -222,8 +241,17 @@ public:
 // statistics of one finished proof's assignment-driven MSMs (window re-tune; the window choice of a staged load)
 struct TuneStats {
     bool valid = false;
-    struct Q { uint64_t n_scalars = 0; double nonzero = 0, entries = 0; int W0 = 0; } l, a, b1, b2;
+    struct Q { uint64_t n_scalars = 0; double nonzero = 0, entries = 0; int W0 = 0; } q[N_QUERIES];      // (none of h: its scalars are uniform)
 };
+// The window for the n_bases points of an assignment-driven query, from the statistics of a proof that ran it with q.W0 > 0
+// windows: every non-zero scalar has a digit in one window, a full-width one in the other W0 - 1 as well.
+static int window_from_stats(uint64_t n_bases, const TuneStats::Q& q) {
+    const double nz = q.nonzero;
+    double nz_full = q.W0 > 1 ? (q.entries - nz) / (double)(q.W0 - 1) : 0.0;
+    if (nz_full < 0) nz_full = 0;
+    if (nz_full > nz) nz_full = nz;
+    return msm_best_window(n_bases, nz - nz_full, nz_full);
+}
 
 struct cg_ctx {
     ~cg_ctx() {
@@ -245,8 +273,7 @@ struct cg_ctx {
     FixedBase<Fq2> fb_delta_g2;
     // scalar ranges (into the MSM operand numbering) owned by this shard
     Range rh, rl, ra;   // h: [0, D-1), l: [0, M-l), a/b: [0, M-1)
-    MsmBases<Fq> bh, bl, ba, bb1;
-    MsmBases<Fq2> bb2;
+    KeyTables tables;
     DevCsr A, B, C;
     Csr29 dA, dB, dC;
     NttDomain dom;
@@ -351,8 +378,7 @@ struct cg_ctx {
 // when the slots are made and after a re-tune has re-sized them
 static uint64_t slot_device_bytes(const ProofSlot& S, uint64_t part[4]) {
     uint64_t ent = S.scratch.entry_bytes(), pcs = S.scratch.piece_bytes(), oth = 0;
-    S.eh.device_bytes(ent, pcs, oth); S.el.device_bytes(ent, pcs, oth); S.ea.device_bytes(ent, pcs, oth);
-    S.eb1.device_bytes(ent, pcs, oth); S.eb2.device_bytes(ent, pcs, oth);
+    each_query([&](int, const auto& e) { e.device_bytes(ent, pcs, oth); }, S);
     part[0] = ent; part[1] = pcs; part[2] = oth;
     part[3] = S.wm.device_bytes() + S.h_canon.bytes();
     return ent + pcs + oth + part[3];
@@ -429,10 +455,6 @@ extern "C" int cg_set_device(int32_t device) {
 
 extern "C" uint64_t cg_domain_size(const cg_ctx* ctx) { return ctx ? ctx->D : 0; }
 
-static float ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // one query of the key -> its tables.  precompute = false keeps row 0 only (the warm-up arrangement of a staged load: keys
 // carry the window, one bucket set per window).  ms_copy / ms_tables: host-clock milliseconds of the copy + import and of
 // the table rows.
@@ -459,8 +481,7 @@ static void load_query(MsmBases<F>& bases, const uint8_t* bytes, uint32_t form, 
 // rec: what a slot of this set asks for, measured on the set's first slot (built buffer by buffer) and used to size the ONE
 // device and ONE page-locked allocation every later slot is carved from.
 struct SlotRecipe { size_t dev_bytes = 0, host_bytes = 0; };
-static std::unique_ptr<ProofSlot> make_slot(cg_ctx* c, const MsmBases<Fq>* bh, const MsmBases<Fq>* bl, const MsmBases<Fq>* ba,
-                                            const MsmBases<Fq>* bb1, const MsmBases<Fq2>* bb2, hipStream_t zs, SlotRecipe& rec, bool lone = false,
+static std::unique_ptr<ProofSlot> make_slot(cg_ctx* c, const KeyTables& tables, hipStream_t zs, SlotRecipe& rec, bool lone = false,
                                             const std::vector<hipStream_t>& borrow = {}) {
     CG_HIP(hipSetDevice(c->device));
     std::unique_ptr<ProofSlot> sl(new ProofSlot());
@@ -505,13 +526,13 @@ static std::unique_ptr<ProofSlot> make_slot(cg_ctx* c, const MsmBases<Fq>* bh, c
     sl->one_stream = serial;
     for (auto& e : sl->ev_t) CG_HIP(hipEventCreate(&e));
     const bool latency = c->latency || lone;
-    sl->eh.latency_mode = sl->el.latency_mode = sl->ea.latency_mode = sl->eb1.latency_mode = sl->eb2.latency_mode = latency;
-    if (serial) {
-        sl->eh.shared_mem = sl->el.shared_mem = sl->ea.shared_mem = sl->eb1.shared_mem = sl->eb2.shared_mem = &sl->scratch;
-        const bool zero_at_end = !(CG_TUNE_ENV("NO_ZERO_AT_END") && CG_TUNE_ENV("NO_ZERO_AT_END")[0] == '1');     // A/B aid (tuning builds)
-        sl->eh.zero_at_end = sl->el.zero_at_end = sl->ea.zero_at_end = sl->eb1.zero_at_end = sl->eb2.zero_at_end = zero_at_end;
-    }
-    sl->eh.init(bh, zs); sl->el.init(bl, zs); sl->ea.init(ba, zs); sl->eb1.init(bb1, zs); sl->eb2.init(bb2, zs);
+    const bool zero_at_end = serial && !(CG_TUNE_ENV("NO_ZERO_AT_END") && CG_TUNE_ENV("NO_ZERO_AT_END")[0] == '1');     // A/B aid (tuning builds)
+    each_query([&](int, auto& e, const auto& t) {
+        e.latency_mode = latency;
+        if (serial) e.shared_mem = &sl->scratch;
+        e.zero_at_end = zero_at_end;
+        e.init(&t, zs);
+    }, *sl, tables);
     if (c->external_q) {      // only the landing buffer of a slice that arrives in host memory, and the input flag
         sl->h_canon.alloc(c->rh.hi - c->rh.lo ? c->rh.hi - c->rh.lo : 1);
         sl->wm.h_bad_input.alloc(1);
@@ -525,8 +546,7 @@ static std::unique_ptr<ProofSlot> make_slot(cg_ctx* c, const MsmBases<Fq>* bh, c
 
 // The lone slots of a throughput context (cg_ctx::acquire).  A device with no room left for them does without: the context
 // then proves every proof on a one-stream slot.
-static void add_lone_slot(cg_ctx* c, std::vector<std::unique_ptr<ProofSlot>>& slots, const MsmBases<Fq>* bh, const MsmBases<Fq>* bl,
-                          const MsmBases<Fq>* ba, const MsmBases<Fq>* bb1, const MsmBases<Fq2>* bb2, hipStream_t zs) {
+static void add_lone_slot(cg_ctx* c, std::vector<std::unique_ptr<ProofSlot>>& slots, const KeyTables& tables, hipStream_t zs) {
     if (c->n_lone <= 0) return;
     try {
         SlotRecipe own;                       // its buffers are a latency slot's: measured, not the one-stream slots' recipe
@@ -537,7 +557,7 @@ static void add_lone_slot(cg_ctx* c, std::vector<std::unique_ptr<ProofSlot>>& sl
         for (int k = 0; k < c->n_lone; ++k) {
             std::vector<hipStream_t> borrow;
             while (borrow.size() < 5 && next > 2 && !slots[next - 1]->lone) borrow.push_back(slots[--next]->st[0]);   // (never the first two slots')
-            slots.push_back(make_slot(c, bh, bl, ba, bb1, bb2, zs, own, true, borrow));
+            slots.push_back(make_slot(c, tables, zs, own, true, borrow));
         }
     } catch (const HipError& e) {
         if (e.code != CG_ERR_OUT_OF_MEMORY) throw;
@@ -565,8 +585,8 @@ static void staged_worker(cg_ctx* c) {
         CG_HIP(hipSetDevice(c->device));
         // The final arrangement under construction; after the swap these hold the WARM-UP tables and slots, which are
         // released when this scope ends - outside the gate.
-        MsmBases<Fq> bh, bl, ba, bb1;
-        MsmBases<Fq2> bb2;
+        KeyTables tables;
+        const KeyTables& row0 = c->tables;        // the warm-up arrangement: what the final tables are expanded from
         std::vector<std::unique_ptr<ProofSlot>> slots;
         int64_t table_bytes = 0;
         auto stop = [&] { if (c->cancel.load()) throw WorkerCancelled(); };
@@ -576,21 +596,16 @@ static void staged_worker(cg_ctx* c) {
         bool all_from_proof = true;
         // the window of an assignment-driven query: from a finished warm-up proof's digit statistics when one is there
         // (msm_best_window, as the one-time re-tune of a synchronous load chooses it), else by size
-        auto window_for = [&](uint64_t n, int which) {
+        auto window_for = [&](uint64_t n, Query which) {
             if (wb > 0) return wb;
             if (!ts.valid) {
                 std::lock_guard<std::mutex> lk(c->warm_mu);
                 ts = c->warm_stats;
             }
             // a proof with r = 0 skips b1 (prover.rs:102-112): same scalars and identity pattern as b2
-            const TuneStats::Q& q = which == 0 ? ts.l : which == 1 ? ts.a : (which == 2 && ts.b1.n_scalars) ? ts.b1 : ts.b2;
+            const TuneStats::Q& q = ts.q[which == Q_B1 && !ts.q[Q_B1].n_scalars ? Q_B2 : which];
             if (!ts.valid) all_from_proof = false;
-            if (ts.valid && q.n_scalars && q.W0 > 0) {
-                double nz = q.nonzero, nz_full = q.W0 > 1 ? (q.entries - nz) / (double)(q.W0 - 1) : 0.0;
-                if (nz_full < 0) nz_full = 0;
-                if (nz_full > nz) nz_full = nz;
-                return msm_best_window(n ? n : 1, nz - nz_full, nz_full);
-            }
+            if (ts.valid && q.n_scalars && q.W0 > 0) return window_from_stats(n ? n : 1, q);
             return msm_default_window(n ? n : 1, true);
         };
         // The FIRST proof goes first.  A host that loads and proves once (create_client_state) is waiting for exactly that
@@ -607,25 +622,25 @@ static void staged_worker(cg_ctx* c) {
             // The h query first.  Its scalars are the quotient's values - uniform whatever the witness - so its window is the
             // size-based one; and its change of basis is the longest step: by the time it is done the first warm-up proof
             // has normally finished and the other four windows can be chosen from it.
-            build_h_bases_folded(bh, c->bh.table.p, c->bh.valid.p, D - 1, c->logD, 0, 1, D, wb > 0 ? wb : msm_default_window(D, true), st,
+            const MsmBases<Fq>&h0 = row0.g1[Q_H], &l0 = row0.g1[Q_L];
+            build_h_bases_folded(tables.g1[Q_H], h0.table.p, h0.valid.p, D - 1, c->logD, 0, 1, D, wb > 0 ? wb : msm_default_window(D, true), st,
                                  &ms_fold, &ms_tables);
             stop();
             // tuning builds, CG_FAULT_STAGED=1 (fault injection for tests/fault_retune_child.py): fail here as an allocation of the
             // final tables would.  The shipped library carries no such switch.
             if (const char* f = CG_TUNE_ENV("FAULT_STAGED")) if (f[0] == '1') throw HipError(CG_ERR_OUT_OF_MEMORY, "injected: out of device memory while building the final arrangement");
-            build_l_bases_folded(bl, c->bh.table.p, c->bh.valid.p, D - 1, c->logD, c->bl.table.p, c->bl.valid.p, l, M, c->c_transposed, c->m,
+            build_l_bases_folded(tables.g1[Q_L], h0.table.p, h0.valid.p, D - 1, c->logD, l0.table.p, l0.valid.p, l, M, c->c_transposed, c->m,
                                  c->dom.vanishing_inv, 0, M,
-                                 [&] { return window_for(M, 0); }, st, &ms_fold, &ms_tables);
-            stop();
+                                 [&] { return window_for(M, Q_L); }, st, &ms_fold, &ms_tables);
             const auto tt = std::chrono::steady_clock::now();
-            ba.build_from_row0(c->ba.table.p, c->ba.valid.p, c->ba.n, window_for(c->ba.n, 1), st);
-            CG_HIP(hipStreamSynchronize(st));
-            stop();
-            bb1.build_from_row0(c->bb1.table.p, c->bb1.valid.p, c->bb1.n, window_for(c->bb1.n, 2), st);
-            CG_HIP(hipStreamSynchronize(st));
-            stop();
-            bb2.build_from_row0(c->bb2.table.p, c->bb2.valid.p, c->bb2.n, window_for(c->bb2.n, 3), st);
-            CG_HIP(hipStreamSynchronize(st));
+            auto expand = [&](auto& t, const auto& from, Query q) {      // a, b1, b2: the same points, their window rows
+                stop();
+                t.build_from_row0(from.table.p, from.valid.p, from.n, window_for(from.n, q), st);
+                CG_HIP(hipStreamSynchronize(st));
+            };
+            expand(tables.g1[Q_A], row0.g1[Q_A], Q_A);
+            expand(tables.g1[Q_B1], row0.g1[Q_B1], Q_B1);
+            expand(tables.b2, row0.b2, Q_B2);
             ms_tables += ms_since(tt);
             from_proof = wb == 0 && ts.valid && all_from_proof;
         }
@@ -635,10 +650,10 @@ static void staged_worker(cg_ctx* c) {
             ScopedStream zs;
             SlotRecipe rec;
             for (int k = 0; k < c->n_slots_final; ++k) {
-                slots.push_back(make_slot(c, &bh, &bl, &ba, &bb1, &bb2, zs, rec));
+                slots.push_back(make_slot(c, tables, zs, rec));
                 stop();
             }
-            add_lone_slot(c, slots, &bh, &bl, &ba, &bb1, &bb2, zs);
+            add_lone_slot(c, slots, tables, zs);
             CG_HIP(hipStreamSynchronize(zs));
             ms_slots = ms_since(tt);
         }
@@ -646,11 +661,10 @@ static void staged_worker(cg_ctx* c) {
             const auto tw = std::chrono::steady_clock::now();
             std::unique_lock<TuneGate> lk(c->tune_mu);       // the proofs in flight drain; new ones wait for the swap
             ms_wait = ms_since(tw);
-            std::swap(c->bh, bh); std::swap(c->bl, bl); std::swap(c->ba, ba); std::swap(c->bb1, bb1); std::swap(c->bb2, bb2);
+            std::swap(c->tables, tables);
             c->slots.swap(slots);
-            for (auto& sl : c->slots) {       // the engines were cut for the tables where they were built
-                sl->eh.bases = &c->bh; sl->el.bases = &c->bl; sl->ea.bases = &c->ba; sl->eb1.bases = &c->bb1; sl->eb2.bases = &c->bb2;
-            }
+            for (auto& sl : c->slots)         // the engines were cut for the tables where they were built
+                each_query([](int, auto& e, const auto& t) { e.bases = &t; }, *sl, c->tables);
             c->folded = true;
             c->rh = {0, D};
             c->rl = {0, M};
@@ -667,7 +681,7 @@ static void staged_worker(cg_ctx* c) {
             // pipeline in turn (9 s of them measured behind a sixteen-slot context under four callers).  With the gate held
             // nothing is in flight and they take microseconds each.
             slots.clear();
-            bh = MsmBases<Fq>(); bl = MsmBases<Fq>(); ba = MsmBases<Fq>(); bb1 = MsmBases<Fq>(); bb2 = MsmBases<Fq2>();
+            tables = KeyTables();
             std::vector<uint64_t>().swap(c->c_transposed.ptr);
             std::vector<uint32_t>().swap(c->c_transposed.row);
             std::vector<uint8_t>().swap(c->c_transposed.coeff);
@@ -837,42 +851,41 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
                 c->lt.domain_ms = ms_since(t);
             }
             AllocScope booking(&c->table_bytes);
-            if (staged) {
-                // every query as its row-0 table: what the warm-up arrangement proves on and what the worker expands
-                load_query<Fq>(c->bh, pk->h_query, form, 0, D - 1, 0, false, s0, &c->lt.key_copy_ms, &c->lt.key_copy_ms);
-                load_query<Fq>(c->bl, pk->l_query, form, 0, M - l, 0, false, s0, &c->lt.key_copy_ms, &c->lt.key_copy_ms);
-                load_query<Fq>(c->ba, pk->a_query, form, 1, M - 1, 0, false, s0, &c->lt.key_copy_ms, &c->lt.key_copy_ms);
-                load_query<Fq>(c->bb1, pk->b_g1_query, form, 1, M - 1, 0, false, s0, &c->lt.key_copy_ms, &c->lt.key_copy_ms);
-                load_query<Fq2>(c->bb2, pk->b_g2_query, form, 1, M - 1, 0, false, s0, &c->lt.key_copy_ms, &c->lt.key_copy_ms);
+            KeyTables& T = c->tables;
+            // one query of the key -> its table: this shard's part of it; a staged load keeps every query as its row-0 table,
+            // which is what the warm-up arrangement proves on and what the worker expands (booked as key copy, rows and all).
+            // A staged load is never sharded (`staged` above), so there rh, rl and ra are the whole queries: [0, D-1), [0, M-l), [0, M-1)
+            auto load = [&](auto& table, const uint8_t* bytes, uint64_t first, Range part) {
+                load_query(table, bytes, form, first + part.lo, part.hi - part.lo, staged ? 0 : wb, !staged, s0, &c->lt.key_copy_ms,
+                           staged ? &c->lt.key_copy_ms : &c->lt.window_tables_ms);
+            };
+            if (folded_now) {
+                // every shard transforms the whole queries (the DFT mixes all points) and keeps its own ranges of the results
+                const auto t = std::chrono::steady_clock::now();
+                DevBuf<G1Affine> th(D), tl(M - l ? M - l : 1);
+                import_bases<Fq>(pk->h_query, form, D - 1, th.p, s0);
+                import_bases<Fq>(pk->l_query, form, M - l, tl.p, s0);
+                c->lt.key_copy_ms += ms_since(t);
+                const uint64_t nh = c->rh.hi - c->rh.lo, nl = c->rl.hi - c->rl.lo;
+                build_hl_bases_folded(T.g1[Q_H], T.g1[Q_L], th.p, D - 1, logD, tl.p, l, M, abc[2], m, c->dom.vanishing_inv,
+                                      c->h_strided ? (uint64_t)c->shard_rank : c->rh.lo, c->h_strided ? (uint64_t)c->shard_count : 1, nh,
+                                      wb > 0 ? wb : msm_default_window(nh ? nh : 1, true), c->rl.lo, nl,
+                                      wb > 0 ? wb : msm_default_window(nl ? nl : 1, true), s0, &c->lt.fold_ms, &c->lt.window_tables_ms);
             } else {
-                if (c->folded) {
-                    // every shard transforms the whole queries (the DFT mixes all points) and keeps its own ranges of the results
-                    const auto t = std::chrono::steady_clock::now();
-                    DevBuf<G1Affine> th(D), tl(M - l ? M - l : 1);
-                    import_bases<Fq>(pk->h_query, form, D - 1, th.p, s0);
-                    import_bases<Fq>(pk->l_query, form, M - l, tl.p, s0);
-                    c->lt.key_copy_ms += ms_since(t);
-                    const uint64_t nh = c->rh.hi - c->rh.lo, nl = c->rl.hi - c->rl.lo;
-                    build_hl_bases_folded(c->bh, c->bl, th.p, D - 1, logD, tl.p, l, M, abc[2], m, c->dom.vanishing_inv,
-                                          c->h_strided ? (uint64_t)c->shard_rank : c->rh.lo, c->h_strided ? (uint64_t)c->shard_count : 1, nh,
-                                          wb > 0 ? wb : msm_default_window(nh ? nh : 1, true), c->rl.lo, nl,
-                                          wb > 0 ? wb : msm_default_window(nl ? nl : 1, true), s0, &c->lt.fold_ms, &c->lt.window_tables_ms);
-                } else {
-                    load_query<Fq>(c->bh, pk->h_query, form, c->rh.lo, c->rh.hi - c->rh.lo, wb, true, s0, &c->lt.key_copy_ms, &c->lt.window_tables_ms);
-                    load_query<Fq>(c->bl, pk->l_query, form, c->rl.lo, c->rl.hi - c->rl.lo, wb, true, s0, &c->lt.key_copy_ms, &c->lt.window_tables_ms);
-                }
-                load_query<Fq>(c->ba, pk->a_query, form, 1 + c->ra.lo, c->ra.hi - c->ra.lo, wb, true, s0, &c->lt.key_copy_ms, &c->lt.window_tables_ms);    // query[1..] (prover.rs:266)
-                load_query<Fq>(c->bb1, pk->b_g1_query, form, 1 + c->ra.lo, c->ra.hi - c->ra.lo, wb, true, s0, &c->lt.key_copy_ms, &c->lt.window_tables_ms);
-                load_query<Fq2>(c->bb2, pk->b_g2_query, form, 1 + c->ra.lo, c->ra.hi - c->ra.lo, wb, true, s0, &c->lt.key_copy_ms, &c->lt.window_tables_ms);
+                load(T.g1[Q_H], pk->h_query, 0, c->rh);
+                load(T.g1[Q_L], pk->l_query, 0, c->rl);
             }
+            load(T.g1[Q_A], pk->a_query, 1, c->ra);             // query[1..] (prover.rs:266)
+            load(T.g1[Q_B1], pk->b_g1_query, 1, c->ra);
+            load(T.b2, pk->b_g2_query, 1, c->ra);
             {   // the G2 MSM may take over b1's grouped entries only if the two queries vanish together (generator.rs:162,168
                 // makes them b_i(τ)·G1 and b_i(τ)·G2; a key from elsewhere is not trusted to)
-                const uint64_t nb = c->bb1.n;
-                c->b_same_identities = nb == c->bb2.n;
+                const uint64_t nb = T.g1[Q_B1].n;
+                c->b_same_identities = nb == T.b2.n;
                 if (c->b_same_identities && nb) {
                     std::vector<uint8_t> v1(nb), v2(nb);
-                    CG_HIP(hipMemcpyAsync(v1.data(), c->bb1.valid.p, nb, hipMemcpyDeviceToHost, s0));
-                    CG_HIP(hipMemcpyAsync(v2.data(), c->bb2.valid.p, nb, hipMemcpyDeviceToHost, s0));
+                    CG_HIP(hipMemcpyAsync(v1.data(), T.g1[Q_B1].valid.p, nb, hipMemcpyDeviceToHost, s0));
+                    CG_HIP(hipMemcpyAsync(v2.data(), T.b2.valid.p, nb, hipMemcpyDeviceToHost, s0));
                     CG_HIP(hipStreamSynchronize(s0));
                     c->b_same_identities = v1 == v2;
                 }
@@ -914,7 +927,7 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
         const int n_now = staged ? std::min(n_slots, 4) : n_slots;
         if (staged) c->folded = false;                    // the arrangement in force until the swap
         SlotRecipe slot_recipe;
-        for (int k = 0; k < n_now; ++k) c->slots.push_back(make_slot(c.get(), &c->bh, &c->bl, &c->ba, &c->bb1, &c->bb2, s0, slot_recipe));
+        for (int k = 0; k < n_now; ++k) c->slots.push_back(make_slot(c.get(), c->tables, s0, slot_recipe));
         CG_HIP(hipStreamSynchronize(s0));
         // Four shared copy-only streams when the runtime's hardware queues hold them beside the proof streams one each
         // (GPU_MAX_HW_QUEUES is the HIP runtime's own variable; cg_init asks for 20); with fewer queues four shared streams
@@ -942,7 +955,7 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
         c->n_lone = (!c->latency && n_slots > 1 && !(opt && (opt->flags & CG_FLAG_NO_LONE_SLOT))) ? std::min(2, n_slots - 1) : 0;
         if (const char* e = CG_TUNE_ENV("LONE_SLOTS")) if (c->n_lone) c->n_lone = atoi(e);      // tuning builds (A/B aid)
         if (!staged) {                                    // (a staged load's warm-up slots are few and short-lived: the worker adds it)
-            add_lone_slot(c.get(), c->slots, &c->bh, &c->bl, &c->ba, &c->bb1, &c->bb2, s0);
+            add_lone_slot(c.get(), c->slots, c->tables, s0);
             CG_HIP(hipStreamSynchronize(s0));
         }
         c->lt.slots_ms = ms_since(t_slots);
@@ -1055,7 +1068,7 @@ struct SuppliedH {
 };
 // Queues on the slot's stream 0 what makes them the h MSM's operand: the copy of a host slice to this shard's place in the
 // slot's h vector, the input check the witness map would have made (canonical assignment) and the same check of what
-// arrived instead of it.  -> where eh.digits reads them
+// arrived instead of it.  -> where the h engine's digits() reads them
 static const Fr* supplied_h_scalars(cg_ctx* c, ProofSlot* S, const Fr* w_dev, const SuppliedH& h) {
     hipStream_t s0 = S->st[0];
     const uint64_t nq = c->rh.hi - c->rh.lo;
@@ -1088,7 +1101,7 @@ static const Fr* witness_map_or_check(cg_ctx* c, ProofSlot* S, const Fr* w_dev, 
 }
 
 struct Partials {
-    G1Affine h, l, a, b1;
+    G1Affine g1[N_G1];                 // h, l, a, b1 (Query)
     G2Affine b2;
 };
 
@@ -1266,47 +1279,48 @@ struct Schedule {
         run_l = !(knock & 1); run_a = !(knock & 2); run_b1 = !skip_b1 && !(knock & 4); run_b2 = !(knock & 8);
         // b1 and b2 take the same scalars against bases that vanish together: with equal windows the grouped entry list of
         // one IS the other's, so the G2 MSM skips its own grouping (five launches, ~0.9 % of a proof's instructions)
-        b2_adopts = run_b1 && run_b2 && !no_share_b() && c->b_same_identities && S->eb2.can_adopt(S->eb1) && n_a > 0;
+        b2_adopts = run_b1 && run_b2 && !no_share_b() && c->b_same_identities && S->b2.can_adopt(S->g1[Q_B1]) && n_a > 0;
     }
     void phase1() const {
         hipStream_t s0 = S->st[0];
         if (S->one_stream) {
             // every MSM grouped and accumulated before the next one starts: the engines share the slot's scratch (entry
             // lists, segment pieces), which is what a slot's memory mostly is
-            if (run_l) { S->el.digits(w_l, n_l, s0); S->el.accumulate(s0, defer); }
-            if (run_a) { S->ea.digits(w_a, n_a, s0); S->ea.accumulate(s0, defer); }
-            if (run_b1) S->eb1.digits(w_a, n_a, s0);
-            if (b2_adopts) S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, s0);    // b1's list is still in the scratch ...
-            if (run_b1) S->eb1.accumulate(s0, defer);
-            if (run_b2 && !b2_adopts) S->eb2.digits(w_a, n_a, s0);
-            if (run_b2) S->eb2.accumulate(s0);                                             // ... until here
+            if (run_l) { S->g1[Q_L].digits(w_l, n_l, s0); S->g1[Q_L].accumulate(s0, defer); }
+            if (run_a) { S->g1[Q_A].digits(w_a, n_a, s0); S->g1[Q_A].accumulate(s0, defer); }
+            if (run_b1) S->g1[Q_B1].digits(w_a, n_a, s0);
+            if (b2_adopts) S->b2.adopt(S->g1[Q_B1].grouped(), S->g1[Q_B1].counters.p, n_a, s0);    // b1's list is still in the scratch ...
+            if (run_b1) S->g1[Q_B1].accumulate(s0, defer);
+            if (run_b2 && !b2_adopts) S->b2.digits(w_a, n_a, s0);
+            if (run_b2) S->b2.accumulate(s0);                                             // ... until here
             return;
         }
         CG_HIP(hipEventRecord(S->ev_w, s0));
         for (int i = 1; i < 5; ++i) CG_HIP(hipStreamWaitEvent(S->st[i], S->ev_w, 0));
-        if (run_l) S->el.digits(w_l, n_l, S->st[1]);
-        if (run_a) S->ea.digits(w_a, n_a, S->st[2]);
-        if (run_b1) S->eb1.digits(w_a, n_a, S->st[3]);
+        if (run_l) S->g1[Q_L].digits(w_l, n_l, S->st[1]);
+        if (run_a) S->g1[Q_A].digits(w_a, n_a, S->st[2]);
+        if (run_b1) S->g1[Q_B1].digits(w_a, n_a, S->st[3]);
         if (b2_adopts) {
             CG_HIP(hipEventRecord(S->ev_b1, S->st[3]));
             CG_HIP(hipStreamWaitEvent(S->st[4], S->ev_b1, 0));
-            S->eb2.adopt(S->eb1.grouped(), S->eb1.counters.p, n_a, S->st[4]);
+            S->b2.adopt(S->g1[Q_B1].grouped(), S->g1[Q_B1].counters.p, n_a, S->st[4]);
         } else if (run_b2) {
-            S->eb2.digits(w_a, n_a, S->st[4]);
+            S->b2.digits(w_a, n_a, S->st[4]);
         }
     }
     void phase2() const {
         if (S->one_stream) return;
-        if (run_l) S->el.accumulate(S->st[1]);
-        if (run_a) S->ea.accumulate(S->st[2]);
-        if (run_b1) S->eb1.accumulate(S->st[3]);
-        if (run_b2) S->eb2.accumulate(S->st[4]);
+        if (run_l) S->g1[Q_L].accumulate(S->st[1]);
+        if (run_a) S->g1[Q_A].accumulate(S->st[2]);
+        if (run_b1) S->g1[Q_B1].accumulate(S->st[3]);
+        if (run_b2) S->b2.accumulate(S->st[4]);
     }
     // run_h: the h MSM was queued (with `defer`), the last G1 accumulation of the stream
     void tails(bool run_h) const {
         if (!defer) return;
-        MsmEngine<Fq>* const g1[4] = {run_l ? &S->el : nullptr, run_a ? &S->ea : nullptr, run_b1 ? &S->eb1 : nullptr, run_h ? &S->eh : nullptr};
-        enqueue_reduction_batch(g1, 4, S->st[0]);
+        // in the order their accumulations were queued: the batch's last engine carries the event that ends it
+        MsmEngine<Fq>* const batch[N_G1] = {run_l ? &S->g1[Q_L] : nullptr, run_a ? &S->g1[Q_A] : nullptr, run_b1 ? &S->g1[Q_B1] : nullptr, run_h ? &S->g1[Q_H] : nullptr};
+        enqueue_reduction_batch(batch, N_G1, S->st[0]);
     }
 };
 
@@ -1320,30 +1334,23 @@ static int collect(cg_ctx* c, ProofSlot* S, bool skip_b1, bool h_supplied, bool 
                    Partials& P, cg_timings* tm, TuneStats& ts) {
     wait_for_slot(c, S);
     if (int e = input_verdict(c, S, h_supplied, c->check_witness && !h_supplied)) return e;
-    P.h = to_affine(S->eh.value());
-    P.l = to_affine(S->el.value());
-    P.a = to_affine(S->ea.value());
-    P.b1 = skip_b1 ? G1Affine::inf() : to_affine(S->eb1.value());
-    P.b2 = to_affine(S->eb2.value());
+    const auto skipped = [&](int q) { return q == Q_B1 && skip_b1; };      // no MSM ran: no sum, no events, no counts
+    P.g1[Q_B1] = G1Affine::inf();
+    each_query([&](int q, auto& sum, const auto& e) { if (!skipped(q)) sum = to_affine(e.value()); }, P, *S);
     if (knock_mask() && tm) { memset(tm, 0, sizeof(*tm)); tm = nullptr; }       // an engine left out has no events to read
     if (tm) {
         memset(tm, 0, sizeof(*tm));
-        tm->msm_h_ms = S->eh.ms_total();
-        tm->msm_l_ms = S->el.ms_total();
-        tm->msm_a_ms = S->ea.ms_total();
-        tm->msm_b1_ms = skip_b1 ? 0.f : S->eb1.ms_total();
-        tm->msm_b2_ms = S->eb2.ms_total();
+        float* const msm_ms[N_QUERIES] = {&tm->msm_h_ms, &tm->msm_l_ms, &tm->msm_a_ms, &tm->msm_b1_ms, &tm->msm_b2_ms};
+        each_query([&](int q, const auto& e) { if (!skipped(q)) *msm_ms[q] = e.ms_total(); }, *S);
         if (in_one_call) {
             tm->witness_map_ms = ev_ms(S->ev_t[0], S->ev_t[1]);
-            tm->accum_g1_ms = S->eh.ms_accum() + S->el.ms_accum() + S->ea.ms_accum() + (skip_b1 ? 0.f : S->eb1.ms_accum());
-            tm->accum_g2_ms = S->eb2.ms_accum();
-            tm->sort_ms = S->eh.ms_sort() + S->el.ms_sort() + S->ea.ms_sort() + (skip_b1 ? 0.f : S->eb1.ms_sort()) + S->eb2.ms_sort();
-            tm->entries_g1 = (uint64_t)S->eh.n_entries() + S->el.n_entries() + S->ea.n_entries() + (skip_b1 ? 0 : S->eb1.n_entries());
-            tm->entries_g2 = S->eb2.n_entries();
-            tm->accum_g1_launches = (S->eh.n_entries() != 0) + (S->el.n_entries() != 0) + (S->ea.n_entries() != 0) + (!skip_b1 && S->eb1.n_entries() != 0);
-            tm->accum_g2_launches = S->eb2.n_entries() != 0;
-            tm->msm_g1_pairs = S->eh.n_scalars + S->el.n_scalars + S->ea.n_scalars + (skip_b1 ? 0 : S->eb1.n_scalars);
-            tm->msm_g2_pairs = S->eb2.n_scalars;
+            // one engine's figures into its group's totals (the sort time is one total for both groups)
+            auto add = [&](const auto& e, float& accum_ms, uint64_t& entries, uint32_t& launches, uint64_t& pairs) {
+                accum_ms += e.ms_accum(); tm->sort_ms += e.ms_sort(); entries += e.n_entries(); launches += e.n_entries() != 0; pairs += e.n_scalars;
+            };
+            for (int q = 0; q < N_G1; ++q)
+                if (!skipped(q)) add(S->g1[q], tm->accum_g1_ms, tm->entries_g1, tm->accum_g1_launches, tm->msm_g1_pairs);
+            add(S->b2, tm->accum_g2_ms, tm->entries_g2, tm->accum_g2_launches, tm->msm_g2_pairs);
         }
         tm->total_ms = ms_since(t0);
     }
@@ -1366,9 +1373,9 @@ static int prove_partial_impl(cg_ctx* c, ProofSlot* S, const Fr* w_dev, bool ski
     const Fr* h_scalars = (knock & 16) && S->knock_h ? S->knock_h : witness_map_or_check(c, S, w_dev, supplied);
     if (knock & 16) S->knock_h = h_scalars;
     if (tm) CG_HIP(hipEventRecord(S->ev_t[1], s0));
-    if (!(knock & 32)) S->eh.digits(h_scalars, c->rh.hi - c->rh.lo, s0);
+    if (!(knock & 32)) S->g1[Q_H].digits(h_scalars, c->rh.hi - c->rh.lo, s0);
     sch.phase2();
-    if (!(knock & 32)) S->eh.accumulate(s0, sch.defer);
+    if (!(knock & 32)) S->g1[Q_H].accumulate(s0, sch.defer);
     sch.tails(!(knock & 32));
     if (while_gpu_runs) (*while_gpu_runs)();      // host work that needs no MSM value
     return collect(c, S, !sch.run_b1, supplied != nullptr, true, t0, P, tm, ts);
@@ -1403,7 +1410,7 @@ static void assemble_impl(const cg_ctx* c, const Partials& S, const uint8_t r[32
     // A = r*delta + a_query[0] + msm_a + alpha   (:96, 256-274)
     G1XYZZ g_a = r_g1;
     madd(g_a, c->a0);
-    madd(g_a, S.a);
+    madd(g_a, S.g1[Q_A]);
     madd(g_a, c->alpha_g1);
     G1XYZZ s_g_a = scalar_mul_bytes(g_a, s);                   // :98
     // B in G1 (:102-112)
@@ -1411,7 +1418,7 @@ static void assemble_impl(const cg_ctx* c, const Partials& S, const uint8_t r[32
     if (!r_zero) {
         g1_b = pre->s_g1;
         madd(g1_b, c->b1_0);
-        madd(g1_b, S.b1);
+        madd(g1_b, S.g1[Q_B1]);
         madd(g1_b, c->beta_g1);
     }
     // B in G2 (:116-117)
@@ -1424,19 +1431,16 @@ static void assemble_impl(const cg_ctx* c, const Partials& S, const uint8_t r[32
     G1XYZZ g_c = s_g_a;
     add(g_c, r_g1_b);
     add(g_c, neg(rs_delta));
-    madd(g_c, S.l);
-    madd(g_c, S.h);
+    madd(g_c, S.g1[Q_L]);
+    madd(g_c, S.g1[Q_H]);
     g1_serialize_uncompressed(to_affine(g_a), proof_out);          // Proof { a, b, c } (:131-135; data_structures.rs:7-14)
     g2_serialize_uncompressed(to_affine(g2_b), proof_out + 64);
     g1_serialize_uncompressed(to_affine(g_c), proof_out + 192);
 }
 
 static void partials_to_bytes(const Partials& P, uint8_t out[384]) {
-    g1_export_canonical(P.h, out);
-    g1_export_canonical(P.l, out + 64);
-    g1_export_canonical(P.a, out + 128);
-    g1_export_canonical(P.b1, out + 192);
-    g2_export_canonical(P.b2, out + 256);
+    for (int q = 0; q < N_G1; ++q) g1_export_canonical(P.g1[q], out + 64 * q);
+    g2_export_canonical(P.b2, out + 64 * N_G1);
 }
 
 // One-time window re-tuning from the digit statistics of a finished proof.  The statistics are copied out of the
@@ -1452,18 +1456,17 @@ static TuneStats::Q tune_stats_of(const MsmEngine<F>& e) {
 }
 static void snapshot_tune_stats(const cg_ctx* c, const ProofSlot* S, bool skip_b1, TuneStats& ts) {
     if (c->fixed_window || c->tuned || c->retune_attempts >= RETUNE_MAX_ATTEMPTS) return;
-    ts.l = tune_stats_of(S->el); ts.a = tune_stats_of(S->ea); ts.b2 = tune_stats_of(S->eb2);
-    if (!skip_b1) ts.b1 = tune_stats_of(S->eb1);
+    each_query([&](int q, const auto& e) { if (q != Q_H && !(q == Q_B1 && skip_b1)) ts.q[q] = tune_stats_of(e); }, *S);
     ts.valid = true;
 }
-// a query's table changed size: every slot's engine for it is re-sized (the first slot's change is booked)
-template <class F>
-static void reinit_engines(cg_ctx* c, MsmEngine<F> ProofSlot::*eng, const MsmBases<F>& bases) {
+// query `which`'s table changed size: every slot's engine for it is re-sized (the first slot's change is booked)
+static void reinit_engines(cg_ctx* c, int which) {
     try {
         // tuning builds, CG_FAULT_RETUNE=1 (fault injection for tests/test_gpu_host_and_ranks.py): fail here as an allocation
         // would, table rebuilt and engines not yet re-sized.  The shipped library carries no such switch.
         if (const char* f = CG_TUNE_ENV("FAULT_RETUNE")) if (f[0] == '1') throw HipError(CG_ERR_OUT_OF_MEMORY, "injected: out of device memory while re-sizing the proof slots");
-        for (size_t k = 0; k < c->slots.size(); ++k) ((*c->slots[k]).*eng).init(&bases);
+        for (auto& sl : c->slots)
+            if (which == Q_B2) sl->b2.init(&c->tables.b2); else sl->g1[which].init(&c->tables.g1[which]);
     } catch (...) {
         c->broken = true;     // the table is already the new one: engines and table no longer agree
         throw;
@@ -1475,50 +1478,45 @@ static int rebuild_booked(cg_ctx* c, MsmBases<F>& bases, int window, hipStream_t
     return bases.rebuild(window, st);
 }
 template <class F>
-static void retune_query(cg_ctx* c, MsmBases<F>& bases, MsmEngine<F> ProofSlot::*eng, const TuneStats::Q& q, hipStream_t st) {
+static void retune_query(cg_ctx* c, int which, MsmBases<F>& bases, TuneStats::Q q, hipStream_t st) {
     if (!q.n_scalars || !bases.n) return;
-    const int W0 = q.W0 > 0 ? q.W0 : bases.W;      // the window count of the tables the statistics were taken on
-    double nz = q.nonzero, N = q.entries;
-    double nz_full = W0 > 1 ? (N - nz) / (double)(W0 - 1) : 0.0;
-    if (nz_full < 0) nz_full = 0;
-    if (nz_full > nz) nz_full = nz;
-    const int best = msm_best_window(bases.n, nz - nz_full, nz_full);
+    if (q.W0 <= 0) q.W0 = bases.W;                 // the window count of the tables the statistics were taken on
+    const int best = window_from_stats(bases.n, q);
     if (best == bases.c) return;
     const int rc = rebuild_booked(c, bases, best, st);
     if (rc < 0) { c->retune_skipped_memory++; return; }
-    if (rc > 0) reinit_engines(c, eng, bases);
+    if (rc > 0) reinit_engines(c, which);
 }
 static void maybe_retune(cg_ctx* c, const TuneStats& ts) {
     if (c->warmup.load()) {
         // a staged load's warm-up arrangement: nothing to re-tune (its tables are row 0 only).  The first representative
         // proof's statistics go to the worker, which chooses the FINAL windows from them before it expands those tables.
         c->warmup_proofs++;
-        if (ts.valid && ts.a.nonzero * 64 >= (double)ts.a.n_scalars) {
+        if (ts.valid && ts.q[Q_A].nonzero * 64 >= (double)ts.q[Q_A].n_scalars) {
             std::lock_guard<std::mutex> lk(c->warm_mu);
             if (!c->warm_stats.valid) c->warm_stats = ts;
         }
         return;
     }
     if (!ts.valid || c->fixed_window || c->tuned) return;
-    if (!ts.l.n_scalars && !ts.a.n_scalars) return;
+    if (!ts.q[Q_L].n_scalars && !ts.q[Q_A].n_scalars) return;
     // A degenerate assignment (all zero, or next to it) says nothing about the proofs to come: its statistics would pick
     // the narrowest window and the widest tables for good.  Keep the size-based windows and wait for a representative
     // proof - a bounded number of times.
-    if (ts.a.nonzero * 64 < (double)ts.a.n_scalars) { c->retune_attempts++; return; }
+    if (ts.q[Q_A].nonzero * 64 < (double)ts.q[Q_A].n_scalars) { c->retune_attempts++; return; }
     std::unique_lock<TuneGate> lk(c->tune_mu);     // waits for the proofs in flight to drain
     if (c->tuned) return;
     c->retune_attempts++;
     try {
         CG_HIP(hipSetDevice(c->device));
         hipStream_t st = c->slots[0]->st[0];
-        retune_query<Fq>(c, c->bl, &ProofSlot::el, ts.l, st);
-        retune_query<Fq>(c, c->ba, &ProofSlot::ea, ts.a, st);
-        if (ts.b1.n_scalars) retune_query<Fq>(c, c->bb1, &ProofSlot::eb1, ts.b1, st);
-        retune_query<Fq2>(c, c->bb2, &ProofSlot::eb2, ts.b2, st);
-        if (!ts.b1.n_scalars && c->bb1.c != c->bb2.c) {         // b1 was skipped (r = 0): same scalars and identity pattern as b2
-            const int rc = rebuild_booked(c, c->bb1, c->bb2.c, st);
+        // l, a, b1, b2 (h's scalars are uniform whatever the witness; a query the proof skipped has no scalars: nothing done)
+        each_query([&](int q, auto& bases) { if (q != Q_H) retune_query(c, q, bases, ts.q[q], st); }, c->tables);
+        MsmBases<Fq>& b1 = c->tables.g1[Q_B1];
+        if (!ts.q[Q_B1].n_scalars && b1.c != c->tables.b2.c) {         // b1 was skipped (r = 0): same scalars and identity pattern as b2
+            const int rc = rebuild_booked(c, b1, c->tables.b2.c, st);
             if (rc < 0) c->retune_skipped_memory++;
-            if (rc > 0) reinit_engines(c, &ProofSlot::eb1, c->bb1);
+            if (rc > 0) reinit_engines(c, Q_B1);
         }
         c->tuned = true;
         account_slot(c);
@@ -1682,8 +1680,8 @@ static int partial_finish(cg_partial* p, const SuppliedH& supplied, bool two_sid
     ProofSlot* S = p->f.S;
     try {
         CG_HIP(hipSetDevice(c->device));
-        S->eh.digits(supplied_h_scalars(c, S, p->f.w_dev, supplied), c->rh.hi - c->rh.lo, S->st[0]);
-        S->eh.accumulate(S->st[0]);
+        S->g1[Q_H].digits(supplied_h_scalars(c, S, p->f.w_dev, supplied), c->rh.hi - c->rh.lo, S->st[0]);
+        S->g1[Q_H].accumulate(S->st[0]);
         Partials P;
         TuneStats ts;
         if (int e = collect(c, S, p->skip_b1, true, false, p->t0, P, timings, ts)) return e;
@@ -1750,17 +1748,16 @@ extern "C" int cg_assemble(cg_ctx* ctx, const uint8_t* partials, uint32_t n_shar
     if (int e = check_rs(r, s)) return e;
     CallGuard inside(ctx);
     try {
-        G1XYZZ h = G1XYZZ::inf(), l = G1XYZZ::inf(), a = G1XYZZ::inf(), b1 = G1XYZZ::inf();
+        G1XYZZ g1[N_G1] = {G1XYZZ::inf(), G1XYZZ::inf(), G1XYZZ::inf(), G1XYZZ::inf()};
         G2XYZZ b2 = G2XYZZ::inf();
         for (uint32_t k = 0; k < n_shards; ++k) {
             const uint8_t* p = partials + (size_t)k * 384;
-            madd(h, g1_import(p, CG_FORM_CANONICAL));
-            madd(l, g1_import(p + 64, CG_FORM_CANONICAL));
-            madd(a, g1_import(p + 128, CG_FORM_CANONICAL));
-            madd(b1, g1_import(p + 192, CG_FORM_CANONICAL));
-            madd(b2, g2_import(p + 256, CG_FORM_CANONICAL));
+            for (int q = 0; q < N_G1; ++q) madd(g1[q], g1_import(p + 64 * q, CG_FORM_CANONICAL));
+            madd(b2, g2_import(p + 64 * N_G1, CG_FORM_CANONICAL));
         }
-        Partials S{to_affine(h), to_affine(l), to_affine(a), to_affine(b1), to_affine(b2)};
+        Partials S;
+        for (int q = 0; q < N_G1; ++q) S.g1[q] = to_affine(g1[q]);
+        S.b2 = to_affine(b2);
         assemble_impl(ctx, S, r, s, proof_out);
         return CG_OK;
     } catch (...) {
@@ -1860,8 +1857,7 @@ extern "C" int cg_ctx_get_info(cg_ctx* ctx, cg_ctx_info* out) {
         CG_HIP(hipMemGetInfo(&free_b, &total_b));
         out->device_free_bytes = free_b;
         out->device_total_bytes = total_b;
-        out->window_bits[0] = ctx->bh.c; out->window_bits[1] = ctx->bl.c; out->window_bits[2] = ctx->ba.c;
-        out->window_bits[3] = ctx->bb1.c; out->window_bits[4] = ctx->bb2.c;
+        each_query([&](int q, const auto& t) { out->window_bits[q] = t.c; }, ctx->tables);
         out->tuned = ctx->tuned ? 1 : 0;
         out->retune_skipped_for_memory = ctx->retune_skipped_memory;
         out->retune_attempts = ctx->retune_attempts;
