@@ -31,6 +31,7 @@ CG_FLAG_CHECK_WITNESS = 256
 CG_ERR_UNSATISFIED = -8
 CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
 CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED = 0, 1, 2      # PublicIOType, creds/src/structs.rs:33-37
+CG_SHOW_MADE, CG_SHOW_MALFORMED = 1, 2
 
 
 class CrescentGpuError(RuntimeError):
@@ -239,6 +240,11 @@ _SIGNATURES = {
     "cg_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cg_verify_show_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cg_show_rand_count": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cg_show_commit_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_show_respond_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_void_p]),
     "cg_pvk_free": (None, [C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
@@ -302,6 +308,14 @@ def scalars_to_array(vals: Sequence[int]) -> np.ndarray:
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def show_rand_count(io_types) -> int:
+    """the scalars one showing of this layout consumes (cg_show_rand_count): 3 + n_committed + n_resp"""
+    io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+    n = C.c_uint64()
+    _check(lib().cg_show_rand_count(_ptr(io) if io.size else None, io.size, C.byref(n)))
+    return int(n.value)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1142,6 +1156,87 @@ class Groth16:
                                           None if pc is None else ptr(pc), None if ps is None else ptr(ps), n, _ptr(verdicts),
                                           None if k is None else _ptr(k)))
         return verdicts[:n], (None if k is None else k[:n])
+
+    @staticmethod
+    def show_commit_batch_packed(pvk: "PreparedVerifyingKey", io_types, proofs, inputs, rand):
+        """cg_show_commit_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = proofs / 256): the GPU
+        half of `ClientState::show_groth16` (creds/src/groth16rand.rs:100-187) before the transcript.  Returns
+        (rand_proofs n x 256, com_hidden n x 64, committed n x n_committed x 64, k_bytes n x (n_committed + 1) x 32,
+        status n) as uint8 arrays; a CG_SHOW_MALFORMED showing has zero bytes everywhere."""
+        io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+        n_com = int((io == CG_IO_COMMITTED).sum())
+        pb = _u8(proofs)
+        if pb.size % 256:
+            raise ValueError("proofs must be n x 256 bytes")
+        n = pb.size // 256
+        n_rand = show_rand_count(io)
+        ib, rb = _u8(inputs, 32 * io.size * n), _u8(rand, 32 * n_rand * n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        rp, comh, comm = np.zeros((m, 256), np.uint8), np.zeros((m, 64), np.uint8), np.zeros((m, max(n_com, 1), 64), np.uint8)
+        k, status = np.zeros((m, n_com + 1, 32), np.uint8), np.zeros(m, np.uint8)
+        _check(lib().cg_show_commit_batch(pvk._h, ptr(io), io.size, ptr(pb), ptr(ib), ptr(rb), n, _ptr(rp), _ptr(comh), _ptr(comm),
+                                          _ptr(k), _ptr(status)))
+        return rp[:n], comh[:n], comm[:n, :n_com], k[:n], status[:n]
+
+    @staticmethod
+    def show_respond_batch(io_types, inputs, rand, pok_c, status=None) -> np.ndarray:
+        """cg_show_respond_batch (host only): the responses s_ij = rho_ij - c * secret_ij of `DLogPoK::prove`
+        (creds/src/dlog.rs:101-109) for the challenges pok_c (n x 32 B, or n ints) the host's transcript produced.  inputs,
+        rand, status: as given to / returned by show_commit_batch_packed.  Returns n x n_resp x 32 uint8."""
+        io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+        n_rand = show_rand_count(io)
+        n_resp = n_rand - 3 - int((io == CG_IO_COMMITTED).sum())
+        if isinstance(pok_c, (list, tuple)):
+            pok_c = b"".join(int(c).to_bytes(32, "little") for c in pok_c)
+        cb = _u8(pok_c)
+        if cb.size % 32:
+            raise ValueError("pok_c must be n x 32 bytes")
+        n = cb.size // 32
+        ib, rb = _u8(inputs, 32 * io.size * n), _u8(rand, 32 * n_rand * n)
+        st = None if status is None else _u8(status, n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        out = np.zeros((max(n, 1), n_resp, 32), np.uint8)
+        _check(lib().cg_show_respond_batch(ptr(io), io.size, ptr(ib), ptr(rb), ptr(cb), None if st is None else ptr(st), n, _ptr(out)))
+        return out[:n]
+
+    @staticmethod
+    def show_batch(pvk: "PreparedVerifyingKey", io_types, states, challenge, rand=None) -> List["ShowGroth16"]:
+        """`ClientState::show_groth16` (creds/src/groth16rand.rs:100-187) for n client states of one layout: commit on the
+        GPU, the caller's transcript, respond on the host.  states: a sequence of (proof bytes or Proof, inputs);
+        rand: per state its show_rand_count scalars in the header's order (ints); None draws them with
+        `secrets.randbelow` (r1, r2 non-zero, as prover.rs:234-237 redraws them) - a host that keeps the openings
+        (committed_input_openings = the r_i, input_com_randomness = z) draws them itself and passes them in;
+        challenge(i, k_bytes, committed, com_hidden) -> int is the host's Merlin transcript (dlog.rs:56-99): it gets state
+        i's (n_committed + 1) x 32 compressed k_i, its n_committed x 64 committed points and its 64-byte com_hidden, and
+        returns c.  This package ships no Merlin.  A malformed state (status CG_SHOW_MALFORMED) raises ValueError."""
+        io = [int(t) for t in io_types]
+        n = len(states)
+        if n == 0:
+            return []
+        if rand is None:
+            import secrets
+            n_rand = show_rand_count(io)
+            rand = [[1 + secrets.randbelow(FR_MODULUS - 1) for _ in range(2)] + [secrets.randbelow(FR_MODULUS) for _ in range(n_rand - 2)]
+                    for _ in range(n)]
+        n_com, n_hid = io.count(CG_IO_COMMITTED), io.count(CG_IO_HIDDEN)
+        fr = lambda v: int(v).to_bytes(32, "little")
+        proofs = b"".join(p.data if isinstance(p, Proof) else bytes(p) for p, _ in states)
+        inputs = np.concatenate([_inputs_array(x) for _, x in states])
+        rb = _u8(b"".join(fr(v) for row in rand for v in row))
+        rp, comh, comm, k, status = Groth16.show_commit_batch_packed(pvk, io, proofs, inputs, rb)
+        bad = np.nonzero(status != CG_SHOW_MADE)[0]
+        if bad.size:
+            raise ValueError("client state %d is malformed (its proof, an input or a random scalar)" % int(bad[0]))
+        cs = [int(challenge(i, k[i], comm[i], comh[i])) for i in range(n)]
+        s = Groth16.show_respond_batch(io, inputs, rb, cs)
+        out = []
+        for i in range(n):
+            flat = [int.from_bytes(s[i, j].tobytes(), "little") for j in range(s.shape[1])]
+            pok_s = [flat[2 * j:2 * j + 2] for j in range(n_com)] + [flat[2 * n_com:]]
+            assert len(pok_s[-1]) == n_hid + 1
+            out.append(ShowGroth16(rp[i].tobytes(), comh[i].tobytes(), cs[i], pok_s, [comm[i, j].tobytes() for j in range(n_com)]))
+        return out
 
     @classmethod
     def clear_cache(cls):

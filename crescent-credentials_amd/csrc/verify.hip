@@ -24,6 +24,19 @@
 //   k_show_k      one lane per (showing, statement): k_i = Σ_j s_ij·base_ij + c·y_i (creds/src/dlog.rs:137-145) from the
 //                 partials, affine, written as ark-serialize's compressed G1 (what the transcript absorbs under b"k")
 //   k_vfy_miller, k_vfy_final   unchanged
+//
+// cg_show_commit_batch creates such showings: `ClientState::show_groth16` (creds/src/groth16rand.rs:100-187) for a batch of
+// client states that share one io_types layout, again up to the Merlin transcript, with every random scalar given by the
+// caller.  The key also carries a table of the G1 generator (after delta_g1's) and one of vk.delta_g2 over Fq2, and a
+// chunk of client states runs
+//   k_mk_check    one lane per state: the proof's coordinates, flags and curve equations (no [r]B = O), read inputs and
+//                 scalars < r, r1 and r2 non-zero                                                       -> one status byte
+//   k_mk_fixed    one lane per (state, fixed-base term): secrets and nonces times gamma_abc[i+1] / delta_g1, and
+//                 (Σ r_i + z)·G, from the tables                                                        -> XYZZ partials
+//   k_mk_var      r1^-1·A and r2·A by double-and-add; in waves of their own r1·(B + r2·delta_g2) over Fq2   -> XYZZ partials
+//   k_mk_out      one lane per (state, output point): A', B', C'' = C + r2·A - (Σ r_i + z)·G, com_hidden, the committed
+//                 points and the k_i of DLogPoK::prove (creds/src/dlog.rs:60-75), affine, as ark-serialize writes them
+// cg_show_respond_batch, the responses once the host's transcript has produced c, is host arithmetic.
 #include <memory>
 
 #include "common.hpp"
@@ -110,6 +123,13 @@ struct KeyRd {
     }
 };
 
+// the G2 generator, canonical limbs x.c0, x.c1, y.c0, y.c1 (ark-bn254 g2.rs; zkey.rs:442-460)
+constexpr uint32_t G2_GEN[4][8] = {
+    {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu},
+    {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u},
+    {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u},
+    {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u}};
+
 struct HostVk {
     G1Affine alpha_g1, delta_g1;
     G2Affine beta_g2, gamma_g2, delta_g2;
@@ -159,38 +179,40 @@ static void parse_pvk(const uint8_t* data, uint64_t len, HostPvk& k) {   // data
 }
 
 // fixed-base tables of gabc[1..]: tab[(i·NWIN + w)·VWIN + d] = d·2^(8w)·gabc[i+1], affine (one batch inversion).  The key
-// passes gamma_abc_g1 followed by delta_g1, so table n_inputs is delta_g1's.
-static void build_tables(const std::vector<G1Affine>& gabc, std::vector<G1Affine>& tab) {
+// passes gamma_abc_g1 followed by delta_g1 and the G1 generator, so table n_inputs is delta_g1's and table n_inputs + 1 the
+// generator's; over Fq2 the same walk makes the one table of delta_g2.
+template <class F>
+static void build_tables(const std::vector<Affine<F>>& gabc, std::vector<Affine<F>>& tab) {
     const uint64_t ell = gabc.size() - 1;
     const uint64_t total = ell * NWIN * VWIN;
-    std::vector<G1XYZZ> pts(total);
+    std::vector<XYZZ<F>> pts(total);
     for (uint64_t i = 0; i < ell; ++i) {
-        G1XYZZ step = G1XYZZ::from_affine(gabc[i + 1]);
+        XYZZ<F> step = XYZZ<F>::from_affine(gabc[i + 1]);
         for (int w = 0; w < NWIN; ++w) {
-            G1XYZZ* row = &pts[(i * NWIN + w) * VWIN];
-            row[0] = G1XYZZ::inf();
+            XYZZ<F>* row = &pts[(i * NWIN + w) * VWIN];
+            row[0] = XYZZ<F>::inf();
             for (int d = 1; d < VWIN; ++d) {
                 row[d] = row[d - 1];
                 add(row[d], step);
             }
-            G1XYZZ next = row[VWIN - 1];
+            XYZZ<F> next = row[VWIN - 1];
             add(next, step);
             step = next;
         }
     }
     // batch affine: t_j = zz_j·zzz_j, one inversion of their product
-    std::vector<Fq> pref(total);
-    Fq acc = Fq::one();
+    std::vector<F> pref(total);
+    F acc = F::one();
     for (uint64_t j = 0; j < total; ++j) {
         pref[j] = acc;
         if (!pts[j].is_inf()) acc = mul(acc, mul(pts[j].zz, pts[j].zzz));
     }
-    Fq ia = inv(acc);
+    F ia = inv(acc);
     tab.resize(total);
     for (uint64_t j = total; j-- > 0;) {
-        if (pts[j].is_inf()) { tab[j] = G1Affine::inf(); continue; }
-        const Fq t = mul(pts[j].zz, pts[j].zzz);
-        const Fq it = mul(ia, pref[j]);          // 1 / t_j
+        if (pts[j].is_inf()) { tab[j] = Affine<F>::inf(); continue; }
+        const F t = mul(pts[j].zz, pts[j].zzz);
+        const F it = mul(ia, pref[j]);          // 1 / t_j
         ia = mul(ia, t);
         tab[j] = {mul(pts[j].x, mul(it, pts[j].zzz)), mul(pts[j].y, mul(it, pts[j].zz))};
     }
@@ -227,6 +249,8 @@ __device__ __forceinline__ G1Affine dev_g1(const uint32_t* w, bool& ok) {
     ok = ok && g1_on_curve(p);
     return p;
 }
+// SUBGROUP = false stops at the twist equation (a client state's own proof, cg_show_commit_batch)
+template <bool SUBGROUP = true>
 __device__ __forceinline__ G2Affine dev_g2(const uint32_t* w, bool& ok) {
     const uint32_t f = w[31] >> 30;
     ok = ok && f != 3u;
@@ -237,7 +261,7 @@ __device__ __forceinline__ G2Affine dev_g2(const uint32_t* w, bool& ok) {
     p.y.c1 = dev_fq(w + 24, ok, 0xC0000000u);
     if (f == 1u) return G2Affine::inf();
     ok = ok && g2_on_twist(p);
-    if (ok) ok = g2_in_subgroup(p);
+    if (SUBGROUP && ok) ok = g2_in_subgroup(p);
     return p;
 }
 
@@ -414,6 +438,216 @@ __global__ __launch_bounds__(VBLOCK) void k_show_k(uint64_t n, ShowShape sh, con
     for (int l = 0; l < 8; ++l) k_out[8 * g + l] = o[l];
 }
 
+// ---- creating showings (ClientState::show_groth16, groth16rand.rs:100-187) ---------------------------------------------
+// One call's layout.  A showing's G1 partials are [n_fix fixed-base terms | r1^-1·A | r2·A]; the fixed-base terms are the
+// n_resp secrets times their bases in the order dlog.rs:60-67 meets them (x_i·gamma_abc[i+1], r_i·delta_g1 per committed
+// input, x_j·gamma_abc[j+1] per hidden input, z·delta_g1), then the n_resp nonces times the same bases, then
+// (Σ r_i + z)·G.  `desc` on the device is [table of term t | scalar of term t]: an index into the showing's inputs, or with
+// MK_RAND set into its rand.
+struct MkShape {
+    uint32_t n_io, n_com, n_resp, n_rand;     // n_rand = 3 + n_com + n_resp: r1, r2, the r_i, z, the nonces
+    uint32_t n_fix;                           // 2·n_resp + 1
+    uint32_t n_terms;                         // n_fix + 2
+    uint32_t n_out;                           // points written per showing: A', B', C'', com_hidden, n_com committed, n_com + 1 k
+};
+constexpr uint32_t MK_RAND = 0x80000000u;
+
+__device__ __forceinline__ G2Affine dev_g2_unchecked(const uint32_t* w) {
+    if ((w[31] >> 30) == 1u) return G2Affine::inf();
+    bool ignored = true;
+    G2Affine p;
+    p.x.c0 = dev_fq(w, ignored);
+    p.x.c1 = dev_fq(w + 8, ignored);
+    p.y.c0 = dev_fq(w + 16, ignored);
+    p.y.c1 = dev_fq(w + 24, ignored, 0xC0000000u);
+    return p;
+}
+__device__ __forceinline__ Fr dev_fr(const uint32_t* w) {
+    Fr a;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a.l[i] = w[i];
+    return a;
+}
+// k·y for a canonical k < r < 2^254, as k_show_terms' variable-base lanes walk it
+template <class F>
+__device__ __forceinline__ XYZZ<F> dev_mul_254(const Affine<F>& y, const uint32_t k[8]) {
+    XYZZ<F> acc = XYZZ<F>::inf();
+    for (int wi = 7; wi >= 0; --wi) {
+        const uint32_t kw = k[wi];
+        for (int b = wi == 7 ? 29 : 31; b >= 0; --b) {
+            acc = dbl(acc);
+            if ((kw >> b) & 1u) madd(acc, y);
+        }
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(VBLOCK) void k_mk_fixed(const uint32_t* __restrict__ inputs, const uint32_t* __restrict__ rand, uint64_t n,
+                                                    MkShape sh, const uint32_t* __restrict__ desc, const G1Affine* __restrict__ tab,
+                                                    G1XYZZ* __restrict__ part) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * sh.n_fix) return;
+    const uint64_t p = g / sh.n_fix;
+    const uint32_t t = (uint32_t)(g % sh.n_fix);
+    const uint32_t* rd = rand + 8 * p * sh.n_rand;
+    Fr x;
+    if (t + 1 == sh.n_fix) {                                      // acc_r + z (groth16rand.rs:136, :167), mod r
+        x = dev_fr(rd + 8 * 2);
+        for (uint32_t j = 1; j <= sh.n_com; ++j) x = add(x, dev_fr(rd + 8 * (2 + j)));
+    } else {
+        const uint32_t src = desc[sh.n_fix + t];
+        x = dev_fr(src & MK_RAND ? rd + 8 * (src & ~MK_RAND) : inputs + 8 * (p * sh.n_io + src));
+    }
+    const G1Affine* tb = tab + (uint64_t)desc[t] * NWIN * VWIN;
+    G1XYZZ acc = G1XYZZ::inf();
+    for (int w = 0; w < NWIN; ++w) {
+        const uint32_t d = (x.l[w >> 2] >> (8 * (w & 3))) & 0xFFu;
+        if (d) madd(acc, tb[w * VWIN + d]);
+    }
+    part[p * sh.n_terms + t] = acc;
+}
+
+// the chains of rerandomize_proof (prover.rs:239-253): lanes [0, n) r1^-1·A, lanes [n, 2n) r2·A, and from a workgroup of
+// their own the G2 lanes r1·(B + r2·delta_g2), one multiplication over Fq2 each and several times as long.  Nothing is
+// checked here: k_mk_check does that, and k_mk_out writes zeros for a showing that fails.
+__global__ __launch_bounds__(VBLOCK) void k_mk_var(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ rand, uint64_t n,
+                                                  MkShape sh, const G2Affine* __restrict__ tab_g2, G1XYZZ* __restrict__ part,
+                                                  G2XYZZ* __restrict__ part_g2) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < 2 * n) {
+        const uint32_t which = g >= n;
+        const uint64_t p = g - which * n;
+        const G1Affine a = dev_g1_unchecked(proofs + 64 * p);
+        Fr k = dev_fr(rand + 8 * (p * sh.n_rand + which));
+        if (!which) k = from_mont(inv(to_mont(k)));               // r1 = 0 stays 0; that showing is malformed
+        part[p * sh.n_terms + sh.n_fix + which] = dev_mul_254(a, k.l);
+        return;
+    }
+    const uint64_t g2_at = (2 * n + VBLOCK - 1) / VBLOCK * VBLOCK;
+    if (g < g2_at || g - g2_at >= n) return;
+    const uint64_t p = g - g2_at;
+    const uint32_t* r2 = rand + 8 * (p * sh.n_rand + 1);
+    G2XYZZ acc = G2XYZZ::inf();
+    for (int w = 0; w < NWIN; ++w) {
+        const uint32_t d = (r2[w >> 2] >> (8 * (w & 3))) & 0xFFu;
+        if (d) madd(acc, tab_g2[w * VWIN + d]);
+    }
+    madd(acc, dev_g2_unchecked(proofs + 64 * p + 16));
+    part_g2[p] = dev_mul_254(to_affine(acc), rand + 8 * p * sh.n_rand);
+}
+
+// one lane per showing: the checks of dev_g1 / dev_g2 on the proof without [r]B = O (a client state is the host's own
+// data, which the reference reads unchecked), every read input and every rand scalar < r, r1 and r2 non-zero
+__global__ __launch_bounds__(VBLOCK) void k_mk_check(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ inputs,
+                                                    const uint32_t* __restrict__ rand, uint64_t n, MkShape sh,
+                                                    const uint32_t* __restrict__ desc, uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t* w = proofs + 64 * p;
+    bool ok = true;
+    (void)dev_g1(w, ok);
+    (void)dev_g2<false>(w + 16, ok);
+    (void)dev_g1(w + 48, ok);
+    for (uint32_t t = 0; t < sh.n_resp; ++t) {
+        const uint32_t src = desc[sh.n_fix + t];
+        if (!(src & MK_RAND)) ok = ok && limbs_below(inputs + 8 * (p * sh.n_io + src), FrP::N);
+    }
+    const uint32_t* rd = rand + 8 * p * sh.n_rand;
+    for (uint32_t j = 0; j < sh.n_rand; ++j) ok = ok && limbs_below(rd + 8 * j, FrP::N);
+    ok = ok && !dev_fr(rd).is_zero() && !dev_fr(rd + 8).is_zero();          // the reference redraws these (prover.rs:234-237)
+    status[p] = ok ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+}
+
+// ark-serialize of an affine G1 point: uncompressed (16 words) or compressed (8 words), SWFlags in the top bits
+__device__ __forceinline__ void dev_put_g1(const G1Affine& a, uint32_t* out, bool compressed) {
+    Fq x = Fq::zero(), y = Fq::zero();
+    uint32_t flags = 0x40000000u;                                 // SWFlags::PointAtInfinity
+    if (!a.is_inf()) {
+        x = from_mont(a.x);
+        y = from_mont(a.y);
+        const Fq ny = from_mont(neg(a.y));
+        flags = limbs_below(ny.l, y.l) ? 0x80000000u : 0u;        // SWFlags::YIsNegative: y > -y
+    }
+    (compressed ? x : y).l[7] |= flags;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) out[l] = x.l[l];
+    if (!compressed) {
+#pragma unroll
+        for (int l = 0; l < 8; ++l) out[8 + l] = y.l[l];
+    }
+}
+__device__ __forceinline__ void dev_put_g2(const G2Affine& a, uint32_t* out) {
+    if (a.is_inf()) {
+        for (int l = 0; l < 32; ++l) out[l] = l == 31 ? 0x40000000u : 0u;
+        return;
+    }
+    const Fq2 ny = neg(a.y);
+    const Fq c[4] = {from_mont(a.x.c0), from_mont(a.x.c1), from_mont(a.y.c0), from_mont(a.y.c1)};
+    const Fq n0 = from_mont(ny.c0), n1 = from_mont(ny.c1);
+    for (int j = 0; j < 4; ++j)
+        for (int l = 0; l < 8; ++l) out[8 * j + l] = c[j].l[l];
+    // QuadExtField's ordering compares c1 first, then c0
+    const bool larger = c[3] == n1 ? limbs_below(n0.l, c[2].l) : limbs_below(n1.l, c[3].l);
+    if (larger) out[31] |= 0x80000000u;
+}
+
+// one lane per (showing, output point): the partials summed with the general `add` (two of them coincide or cancel for
+// chosen randomness), affine, written as ark-serialize writes them; zeros for a malformed showing
+__global__ __launch_bounds__(VBLOCK) void k_mk_out(const uint32_t* __restrict__ proofs, uint64_t n, MkShape sh,
+                                                  const G1XYZZ* __restrict__ part, const G2XYZZ* __restrict__ part_g2,
+                                                  const uint8_t* __restrict__ status, uint32_t* __restrict__ rand_proofs,
+                                                  uint32_t* __restrict__ com_hidden, uint32_t* __restrict__ committed,
+                                                  uint32_t* __restrict__ k_out) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * sh.n_out) return;
+    const uint64_t p = g / sh.n_out;
+    const uint32_t o = (uint32_t)(g % sh.n_out);
+    const bool made = status[p] == CG_SHOW_MADE;
+    const G1XYZZ* pt = part + p * sh.n_terms;
+    if (o == 1) {                                                 // B' = r1·(B + r2·delta_g2)
+        uint32_t* out = rand_proofs + 64 * p + 16;
+        if (made) dev_put_g2(to_affine(part_g2[p]), out);
+        else for (int l = 0; l < 32; ++l) out[l] = 0;
+        return;
+    }
+    uint32_t* out;
+    uint32_t lo, hi;                                              // the fixed-base partials [lo, hi) of this point
+    bool compressed = false;
+    G1XYZZ acc = G1XYZZ::inf();
+    if (o == 0) {                                                 // A' = r1^-1·A
+        out = rand_proofs + 64 * p;
+        lo = hi = 0;
+        acc = pt[sh.n_fix];
+    } else if (o == 2) {                                          // C'' = C + r2·A - (acc_r + z)·G
+        out = rand_proofs + 64 * p + 48;
+        lo = hi = 0;
+        if (made) {
+            acc = G1XYZZ::from_affine(dev_g1_unchecked(proofs + 64 * p + 48));
+            add(acc, pt[sh.n_fix + 1]);
+            add(acc, neg(pt[sh.n_fix - 1]));
+        }
+    } else if (o == 3) {                                          // Σ x_j·gamma_abc[j+1] + z·delta_g1 over the hidden inputs
+        out = com_hidden + 16 * p;
+        lo = 2 * sh.n_com, hi = sh.n_resp;
+    } else if (o < 4 + sh.n_com) {                                // x_i·gamma_abc[i+1] + r_i·delta_g1
+        const uint32_t i = o - 4;
+        out = committed + 16 * (p * sh.n_com + i);
+        lo = 2 * i, hi = 2 * i + 2;
+    } else {                                                      // k_i = Σ_j rho_ij·base_ij (dlog.rs:60-67)
+        const uint32_t i = o - 4 - sh.n_com;
+        out = k_out + 8 * (p * (sh.n_com + 1) + i);
+        compressed = true;
+        lo = sh.n_resp + (i < sh.n_com ? 2 * i : 2 * sh.n_com);
+        hi = i < sh.n_com ? lo + 2 : 2 * sh.n_resp;
+    }
+    if (!made) {
+        for (int l = 0; l < (compressed ? 8 : 16); ++l) out[l] = 0;
+        return;
+    }
+    for (uint32_t j = lo; j < hi; ++j) add(acc, pt[j]);
+    dev_put_g1(to_affine(acc), out, compressed);
+}
+
 }  // namespace
 
 struct cg_pvk {
@@ -435,6 +669,12 @@ struct cg_pvk {
     // cg_verify_show_batch's own: grown one by one, since their sizes follow the call's layout
     DevBuf<uint8_t> s_rev, s_comh, s_comm, s_c, s_s, s_k;
     DevBuf<uint32_t> s_tab_of;
+    // cg_show_commit_batch's own: the table of delta_g2, whether gamma_g2 is the generator, and its per-call buffers
+    bool gamma_is_one = false;
+    DevBuf<G2Affine> tab_g2;
+    DevBuf<uint8_t> m_rand, m_rproofs, m_comh, m_comm, m_k;
+    DevBuf<G2XYZZ> m_part_g2;
+    DevBuf<uint32_t> m_desc;
     ~cg_pvk() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
 };
 
@@ -447,7 +687,12 @@ extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len,
         if (hk.vk.gamma_abc.empty()) return fail(CG_ERR_MALFORMED_KEY, "gamma_abc_g1 is empty");
         std::vector<G1Affine> bases = hk.vk.gamma_abc, tab;
         bases.push_back(hk.vk.delta_g1);            // the Pedersen / DLogPoK base of a showing (groth16rand.rs:133, :274)
+        bases.push_back({Fq::one(), dbl(Fq::one())});   // G = (1, 2): the correction of C in a showing (groth16rand.rs:167)
         build_tables(bases, tab);
+        std::vector<G2Affine> tab_g2;                   // r2·delta_g2 of rerandomize_proof (prover.rs:247)
+        build_tables(std::vector<G2Affine>{G2Affine::inf(), hk.vk.delta_g2}, tab_g2);
+        const G2Affine g2_gen = {{to_mont(fq_const(G2_GEN[0])), to_mont(fq_const(G2_GEN[1]))},
+                                 {to_mont(fq_const(G2_GEN[2])), to_mont(fq_const(G2_GEN[3]))}};
         int dev = device;
         if (dev < 0) CG_HIP(hipGetDevice(&dev));
         CG_HIP(hipSetDevice(dev));
@@ -458,9 +703,12 @@ extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len,
         k->alpha_beta = hk.alpha_beta;
         k->gamma_live = hk.gamma_live;
         k->delta_live = hk.delta_live;
+        k->gamma_is_one = hk.vk.gamma_g2.x == g2_gen.x && hk.vk.gamma_g2.y == g2_gen.y;       // generator.rs:28
         CG_HIP(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
         k->tab.alloc(tab.size() ? tab.size() : 1);
         h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
+        k->tab_g2.alloc(tab_g2.size());
+        h2d_sync(k->tab_g2.p, tab_g2.data(), tab_g2.size() * sizeof(G2Affine), k->st);
         k->gamma_c.alloc(NC);
         k->delta_c.alloc(NC);
         if (hk.gamma_live) h2d_sync(k->gamma_c.p, hk.gamma_c.data(), NC * sizeof(EllCoeff), k->st);
@@ -630,6 +878,152 @@ extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
     } catch (...) {
         return translate_current_exception();
     }
+}
+
+// ---- creating showings: the layout of one call, shared by the three entries ---------------------------------------------
+namespace {
+struct MkLayout {
+    MkShape sh;
+    std::vector<uint32_t> desc;        // [table of term t | scalar of term t], as k_mk_fixed reads it
+};
+// 0, or the failure already recorded
+int mk_layout(const uint8_t* io_types, uint64_t n_io, MkLayout& L) {
+    if (n_io && !io_types) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_io >= MK_RAND / 4) return fail(CG_ERR_INVALID_ARGUMENT, "too many io types");
+    std::vector<uint32_t> com, hid;
+    for (uint64_t i = 0; i < n_io; ++i) {
+        switch (io_types[i]) {
+            case CG_IO_REVEALED: break;
+            case CG_IO_HIDDEN: hid.push_back((uint32_t)i); break;
+            case CG_IO_COMMITTED: com.push_back((uint32_t)i); break;
+            default: return fail(CG_ERR_INVALID_ARGUMENT, "io_types[%llu] = %u is no PublicIOType", (unsigned long long)i, io_types[i]);
+        }
+    }
+    MkShape& sh = L.sh;
+    sh.n_io = (uint32_t)n_io;
+    sh.n_com = (uint32_t)com.size();
+    sh.n_resp = 2 * sh.n_com + (uint32_t)hid.size() + 1;
+    sh.n_rand = 3 + sh.n_com + sh.n_resp;
+    sh.n_fix = 2 * sh.n_resp + 1;
+    sh.n_terms = sh.n_fix + 2;
+    sh.n_out = 2 * sh.n_com + 5;
+    std::vector<uint32_t> tab_of, src;
+    for (uint32_t c = 0; c < sh.n_com; ++c) {                     // (x_i, r_i) on (gamma_abc[i+1], delta_g1)
+        tab_of.push_back(com[c]); src.push_back(com[c]);
+        tab_of.push_back(sh.n_io); src.push_back(MK_RAND | (2 + c));
+    }
+    for (uint32_t j : hid) { tab_of.push_back(j); src.push_back(j); }
+    tab_of.push_back(sh.n_io); src.push_back(MK_RAND | (2 + sh.n_com));          // z on delta_g1
+    for (uint32_t t = 0; t < sh.n_resp; ++t) {                    // the nonces walk the same tables
+        tab_of.push_back(tab_of[t]); src.push_back(MK_RAND | (3 + sh.n_com + t));
+    }
+    tab_of.push_back(sh.n_io + 1); src.push_back(0);              // (acc_r + z)·G: the lane forms its own scalar
+    L.desc = tab_of;
+    L.desc.insert(L.desc.end(), src.begin(), src.end());
+    return CG_OK;
+}
+}  // namespace
+
+extern "C" int cg_show_rand_count(const uint8_t* io_types, uint64_t n_io, uint64_t* n_rand) {
+    if (!n_rand) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    MkLayout L;
+    if (int rc = mk_layout(io_types, n_io, L)) return rc;
+    *n_rand = L.sh.n_rand;
+    return CG_OK;
+}
+
+extern "C" int cg_show_commit_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, const uint8_t* proofs, const uint8_t* inputs,
+                                    const uint8_t* rand, uint64_t n, uint8_t* rand_proofs, uint8_t* com_hidden, uint8_t* committed,
+                                    uint8_t* k_out, uint8_t* status) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_io != k->n_inputs)
+        return fail(CG_ERR_MALFORMED_KEY, "%llu io types for a key with gamma_abc_g1.len() = %llu", (unsigned long long)n_io,
+                    (unsigned long long)(k->n_inputs + 1));
+    MkLayout L;
+    if (int rc = mk_layout(io_types, n_io, L)) return rc;
+    if (!k->gamma_is_one)
+        return fail(CG_ERR_MALFORMED_KEY, "gamma_g2 is not the G2 generator: C - (acc_r + z) G re-randomises gamma = 1 keys only");
+    if (n == 0) return CG_OK;
+    const MkShape sh = L.sh;
+    if (!proofs || !rand || !rand_proofs || !com_hidden || !k_out || !status || (sh.n_resp > 1 && !inputs) || (sh.n_com && !committed))
+        return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
+        const uint32_t n_stmt = sh.n_com + 1;
+        grow(k->d_proofs, chunk * 256);
+        grow(k->d_inputs, chunk * sh.n_io * 32 + 32);
+        grow(k->d_status, chunk);
+        grow(k->d_part, chunk * sh.n_terms + 1);
+        grow(k->m_rand, chunk * sh.n_rand * 32);
+        grow(k->m_part_g2, chunk);
+        grow(k->m_rproofs, chunk * 256);
+        grow(k->m_comh, chunk * 64);
+        grow(k->m_comm, chunk * sh.n_com * 64 + 64);
+        grow(k->m_k, chunk * n_stmt * 32);
+        grow(k->m_desc, L.desc.size());
+        h2d_sync(k->m_desc.p, L.desc.data(), L.desc.size() * sizeof(uint32_t), k->st);
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            CG_HIP(hipMemcpyAsync(k->d_proofs.p, proofs + off * 256, m * 256, hipMemcpyHostToDevice, k->st));
+            if (inputs && sh.n_io) CG_HIP(hipMemcpyAsync(k->d_inputs.p, inputs + off * sh.n_io * 32, m * sh.n_io * 32, hipMemcpyHostToDevice, k->st));
+            CG_HIP(hipMemcpyAsync(k->m_rand.p, rand + off * sh.n_rand * 32, m * sh.n_rand * 32, hipMemcpyHostToDevice, k->st));
+            const uint32_t *d_pr = (const uint32_t*)k->d_proofs.p, *d_in = (const uint32_t*)k->d_inputs.p, *d_rd = (const uint32_t*)k->m_rand.p;
+            k_mk_check<<<ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_in, d_rd, m, sh, k->m_desc.p, k->d_status.p);
+            CG_KERNEL_CHECK();
+            k_mk_fixed<<<ceil_div(m * sh.n_fix, VBLOCK), VBLOCK, 0, k->st>>>(d_in, d_rd, m, sh, k->m_desc.p, k->tab.p, k->d_part.p);
+            CG_KERNEL_CHECK();
+            k_mk_var<<<ceil_div(2 * m, VBLOCK) + ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_rd, m, sh, k->tab_g2.p, k->d_part.p,
+                                                                                         k->m_part_g2.p);
+            CG_KERNEL_CHECK();
+            k_mk_out<<<ceil_div(m * sh.n_out, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, k->d_part.p, k->m_part_g2.p, k->d_status.p,
+                                                                          (uint32_t*)k->m_rproofs.p, (uint32_t*)k->m_comh.p,
+                                                                          (uint32_t*)k->m_comm.p, (uint32_t*)k->m_k.p);
+            CG_KERNEL_CHECK();
+            CG_HIP(hipMemcpyAsync(rand_proofs + off * 256, k->m_rproofs.p, m * 256, hipMemcpyDeviceToHost, k->st));
+            CG_HIP(hipMemcpyAsync(com_hidden + off * 64, k->m_comh.p, m * 64, hipMemcpyDeviceToHost, k->st));
+            if (sh.n_com) CG_HIP(hipMemcpyAsync(committed + off * sh.n_com * 64, k->m_comm.p, m * sh.n_com * 64, hipMemcpyDeviceToHost, k->st));
+            CG_HIP(hipMemcpyAsync(k_out + off * n_stmt * 32, k->m_k.p, m * n_stmt * 32, hipMemcpyDeviceToHost, k->st));
+            CG_HIP(hipMemcpyAsync(status + off, k->d_status.p, m, hipMemcpyDeviceToHost, k->st));
+            CG_HIP(hipStreamSynchronize(k->st));
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+// DLogPoK::prove's responses (dlog.rs:101-109) once the host's transcript has produced c: plain host arithmetic
+extern "C" int cg_show_respond_batch(const uint8_t* io_types, uint64_t n_io, const uint8_t* inputs, const uint8_t* rand,
+                                     const uint8_t* pok_c, const uint8_t* status, uint64_t n, uint8_t* pok_s) {
+    MkLayout L;
+    if (int rc = mk_layout(io_types, n_io, L)) return rc;
+    if (n == 0) return CG_OK;
+    const MkShape sh = L.sh;
+    if (!rand || !pok_c || !pok_s || (sh.n_resp > 1 && !inputs)) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    const uint32_t* src = L.desc.data() + sh.n_fix;
+    auto secret = [&](uint64_t p, uint32_t t) {
+        return src[t] & MK_RAND ? rand + 32 * (p * sh.n_rand + (src[t] & ~MK_RAND)) : inputs + 32 * (p * sh.n_io + src[t]);
+    };
+    auto nonce = [&](uint64_t p, uint32_t t) { return rand + 32 * (p * sh.n_rand + 3 + sh.n_com + t); };
+    for (uint64_t p = 0; p < n; ++p) {                            // every value first: an error writes nothing
+        if (status && status[p] != CG_SHOW_MADE) continue;
+        bool ok = scalar_is_canonical(pok_c + 32 * p);
+        for (uint32_t t = 0; t < sh.n_resp; ++t) ok = ok && scalar_is_canonical(secret(p, t)) && scalar_is_canonical(nonce(p, t));
+        if (!ok) return fail(CG_ERR_INVALID_ARGUMENT, "showing %llu: an input, a rand scalar or c is not below the scalar modulus", (unsigned long long)p);
+    }
+    for (uint64_t p = 0; p < n; ++p) {
+        uint8_t* out = pok_s + 32 * p * sh.n_resp;
+        if (status && status[p] != CG_SHOW_MADE) {
+            memset(out, 0, 32 * (size_t)sh.n_resp);
+            continue;
+        }
+        const Fr c = to_mont(fp_from_bytes<Fr>(pok_c + 32 * p));             // c·R times a canonical x is c·x, canonical
+        for (uint32_t t = 0; t < sh.n_resp; ++t)
+            fp_to_bytes(sub(fp_from_bytes<Fr>(nonce(p, t)), mul(c, fp_from_bytes<Fr>(secret(p, t)))), out + 32 * t);
+    }
+    return CG_OK;
 }
 
 extern "C" void cg_pvk_free(cg_pvk* k) {

@@ -618,6 +618,48 @@ enum { CG_IO_REVEALED = 0, CG_IO_HIDDEN = 1, CG_IO_COMMITTED = 2 };
 int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, const uint8_t* revealed,
                          const uint8_t* rand_proofs, const uint8_t* com_hidden, const uint8_t* committed,
                          const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts, uint8_t* k_out);
+/* Creating showings: `ClientState::show_groth16` (creds/src/groth16rand.rs:100-187) for n client states under one key and
+ * ONE io_types layout, in two calls around the host's Merlin transcript.  The library draws no randomness and runs no
+ * transcript: every random scalar comes from the caller (as r, s of cg_prove do), and between the two calls the host
+ * absorbs the bases, k_out and the committed points / com_hidden into its own Merlin transcript and squeezes c
+ * (creds/src/dlog.rs:56-99; INTEGRATION.md, "Creating showings").
+ * A showing consumes n_rand = 3 + n_committed + n_resp scalars (n_resp = 2 * n_committed + n_hidden + 1), in this order:
+ *   r1, r2 (rerandomize_proof) | r_i per committed input, in input order | z (input_com_randomness) |
+ *   the n_resp nonces, statement-major as dlog.rs:60-67 draws them: per committed input (for gamma_abc[i+1], for
+ *   delta_g1), then one per hidden input, then one for delta_g1. */
+enum { CG_SHOW_MADE = 1, CG_SHOW_MALFORMED = 2 };
+/* The n_rand of a layout.  Host only. */
+int cg_show_rand_count(const uint8_t* io_types, uint64_t n_io, uint64_t* n_rand);
+/* Replaces: `rerandomize_proof` (forks/groth16/src/prover.rs:227-254), the Pedersen commitments and com_hidden_inputs of
+ * groth16rand.rs:120-160, the correction of C (:167-168) and the commitments k_i of `DLogPoK::prove` (dlog.rs:60-75), on
+ * the GPU.
+ * proofs: n x 256 B (cg_prove's layout);  inputs: n x n_io x 32 B canonical Fr (`ClientState.inputs`; only hidden and
+ * committed positions are read);  rand: n x n_rand x 32 B canonical Fr, as above.
+ * rand_proofs: n x 256 B, A' = r1^-1 A | B' = r1 (B + r2 delta_g2) | C'' = C + r2 A - (sum r_i + z) G
+ * com_hidden:  n x 64 B, sum x_j gamma_abc[j+1] + z delta_g1 over the hidden inputs
+ * committed:   n x n_committed x 64 B, x_i gamma_abc[i+1] + r_i delta_g1
+ *   (all ark-serialize uncompressed, the bytes cg_verify_show_batch takes back)
+ * k_out:       n x (n_committed + 1) x 32 B, k_i = sum_j rho_ij base_ij as ark-serialize COMPRESSED G1: what
+ *              `add_to_transcript(b"k", ..)` appends, the encoding cg_verify_show_batch's k_out has
+ * status:      n x CG_SHOW_*.  CG_SHOW_MALFORMED (that showing only, all of its outputs zero bytes): a proof coordinate
+ *              >= q, bad point flags, A or C off the curve, B off the twist (B's subgroup is NOT checked: a client state is
+ *              the host's own data, which the reference reads unchecked); a read input or a rand scalar >= r; r1 = 0 or
+ *              r2 = 0 (the reference redraws those, prover.rs:234-237).
+ * n_io != cg_pvk_num_inputs is CG_ERR_MALFORMED_KEY, a byte above 2 in io_types CG_ERR_INVALID_ARGUMENT; a key whose
+ * gamma_g2 is not the G2 generator is CG_ERR_MALFORMED_KEY (the correction of C holds for the fork's gamma = 1 keys only,
+ * forks/groth16/src/generator.rs:28).  Argument errors are reported before any HIP call; n = 0 is CG_OK. */
+int cg_show_commit_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, const uint8_t* proofs,
+                         const uint8_t* inputs, const uint8_t* rand, uint64_t n, uint8_t* rand_proofs,
+                         uint8_t* com_hidden, uint8_t* committed, uint8_t* k_out, uint8_t* status);
+/* Replaces: the responses of `DLogPoK::prove` (dlog.rs:101-109), s_ij = rho_ij - c * secret_ij mod r, once the host's
+ * Merlin transcript has produced c.  Host only, on the calling thread: no handle, no HIP call.
+ * inputs, rand: as given to cg_show_commit_batch;  pok_c: n x 32 B canonical Fr;  status: that call's status bytes, or
+ * NULL for "all made" - a showing whose byte is not CG_SHOW_MADE is not read and gets zero bytes.
+ * pok_s: n x n_resp x 32 B in the order cg_verify_show_batch reads them (secrets: x_i, r_i per committed input, then the
+ * hidden x_j, then z).  A value >= r in a showing that is read, its c included, is CG_ERR_INVALID_ARGUMENT naming the
+ * showing, and nothing is written. */
+int cg_show_respond_batch(const uint8_t* io_types, uint64_t n_io, const uint8_t* inputs, const uint8_t* rand,
+                          const uint8_t* pok_c, const uint8_t* status, uint64_t n, uint8_t* pok_s);
 void cg_pvk_free(cg_pvk* k);
 /* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
  * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the

@@ -745,6 +745,90 @@ impl GpuVerifyingKey {
     }
 }
 
+/// What `GpuVerifyingKey::show_commit_batch` returns: the flat arrays of `cg_show_commit_batch`, one row per client state.
+pub struct ShowCommitments {
+    /// n x 256 B: A' | B' | C'' ark-serialize uncompressed (`Proof::deserialize_uncompressed_unchecked` reads a row back)
+    pub rand_proofs: Vec<u8>,
+    /// n x 64 B: com_hidden_inputs
+    pub com_hidden: Vec<u8>,
+    /// n x n_committed x 64 B: commited_inputs
+    pub committed: Vec<u8>,
+    /// n x (n_committed + 1) x 32 B: the k_i as `add_to_transcript(&mut ts, b"k", &k_i)` appends them
+    pub k: Vec<u8>,
+    /// n x CG_SHOW_MADE / CG_SHOW_MALFORMED
+    pub status: Vec<u8>,
+}
+
+impl GpuVerifyingKey {
+    /// The GPU share of `ClientState::show_groth16` (groth16rand.rs:100-187) for `n` client states of one proof spec:
+    /// `rerandomize_proof`, the Pedersen commitments, com_hidden_inputs, the correction of C and the k_i of
+    /// `DLogPoK::prove`.  `inputs`: n x io_types.len() (`ClientState.inputs`); `rand`: n x `cg_show_rand_count` scalars
+    /// drawn by the caller in the header's order (r1, r2, the r_i, z, the nonces).  The Merlin transcript stays here on
+    /// the host: absorb the bases, `k` and y as dlog.rs:56-99 does, derive c, then call `show_respond_batch`, and keep
+    /// the r_i and z as `committed_input_openings` / `input_com_randomness` ("Creating showings").
+    pub fn show_commit_batch(&self, io_types: &[u8], proofs: &[Proof<Bn254>], inputs: &[Fr], rand: &[Fr]) -> Result<ShowCommitments, SynthesisError> {
+        let n = proofs.len();
+        let n_com = io_types.iter().filter(|t| **t == sys::CG_IO_COMMITTED).count();
+        let mut n_rand = 0u64;
+        let rc = unsafe { sys::cg_show_rand_count(io_types.as_ptr(), io_types.len() as u64, &mut n_rand) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        if inputs.len() != n * io_types.len() || rand.len() != n * n_rand as usize {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let mut pb = Vec::with_capacity(n * 256);
+        for p in proofs {
+            p.serialize_uncompressed(&mut pb).map_err(|_| SynthesisError::AssignmentMissing)?;
+        }
+        let (ib, rb) = (canonical_bytes(inputs), canonical_bytes(rand));
+        let mut out = ShowCommitments {
+            rand_proofs: vec![0u8; n * 256],
+            com_hidden: vec![0u8; n * 64],
+            committed: vec![0u8; n * n_com * 64 + 64],
+            k: vec![0u8; n * (n_com + 1) * 32],
+            status: vec![0u8; n],
+        };
+        let rc = unsafe {
+            sys::cg_show_commit_batch(self.h, io_types.as_ptr(), io_types.len() as u64, pb.as_ptr(), ib.as_ptr(), rb.as_ptr(), n as u64,
+                                      out.rand_proofs.as_mut_ptr(), out.com_hidden.as_mut_ptr(), out.committed.as_mut_ptr(),
+                                      out.k.as_mut_ptr(), out.status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        out.committed.truncate(n * n_com * 64);
+        Ok(out)
+    }
+
+    /// The responses of `DLogPoK::prove` (dlog.rs:101-109) for the challenges the host's transcript produced: n x n_resp
+    /// canonical 32-byte scalars in the order `pok_inputs.s` flattens to.  Host arithmetic only; `inputs`, `rand` and
+    /// `status` are those of `show_commit_batch` (a state that is not CG_SHOW_MADE gets zeros).
+    pub fn show_respond_batch(io_types: &[u8], inputs: &[Fr], rand: &[Fr], pok_c: &[Fr], status: &[u8]) -> Result<Vec<u8>, SynthesisError> {
+        let n = pok_c.len();
+        let n_com = io_types.iter().filter(|t| **t == sys::CG_IO_COMMITTED).count();
+        let mut n_rand = 0u64;
+        let rc = unsafe { sys::cg_show_rand_count(io_types.as_ptr(), io_types.len() as u64, &mut n_rand) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        if inputs.len() != n * io_types.len() || rand.len() != n * n_rand as usize || status.len() != n {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let n_resp = n_rand as usize - 3 - n_com;
+        let (ib, rb, cb) = (canonical_bytes(inputs), canonical_bytes(rand), canonical_bytes(pok_c));
+        let mut s = vec![0u8; n * n_resp * 32];
+        let rc = unsafe {
+            sys::cg_show_respond_batch(io_types.as_ptr(), io_types.len() as u64, ib.as_ptr(), rb.as_ptr(), cb.as_ptr(), status.as_ptr(),
+                                       n as u64, s.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(s)
+    }
+}
+
 impl Drop for GpuVerifyingKey {
     fn drop(&mut self) {
         unsafe { sys::cg_pvk_free(self.h) }

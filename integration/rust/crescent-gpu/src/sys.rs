@@ -22,6 +22,8 @@ pub const CG_VERIFY_MALFORMED: u8 = 2;
 pub const CG_IO_REVEALED: u8 = 0;
 pub const CG_IO_HIDDEN: u8 = 1;
 pub const CG_IO_COMMITTED: u8 = 2;
+pub const CG_SHOW_MADE: u8 = 1;
+pub const CG_SHOW_MALFORMED: u8 = 2;
 
 #[repr(C)]
 pub struct cg_proving_key {
@@ -337,6 +339,32 @@ extern "C" {
         n: u64,
         verdicts: *mut u8,
         k_out: *mut u8,
+    ) -> c_int;
+    // creating showings: two calls around the host's Merlin transcript
+    pub fn cg_show_rand_count(io_types: *const u8, n_io: u64, n_rand: *mut u64) -> c_int;
+    pub fn cg_show_commit_batch(
+        k: *mut cg_pvk,
+        io_types: *const u8,
+        n_io: u64,
+        proofs: *const u8,
+        inputs: *const u8,
+        rand: *const u8,
+        n: u64,
+        rand_proofs: *mut u8,
+        com_hidden: *mut u8,
+        committed: *mut u8,
+        k_out: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_show_respond_batch(
+        io_types: *const u8,
+        n_io: u64,
+        inputs: *const u8,
+        rand: *const u8,
+        pok_c: *const u8,
+        status: *const u8,
+        n: u64,
+        pok_s: *mut u8,
     ) -> c_int;
     pub fn cg_pvk_free(k: *mut cg_pvk);
 }
