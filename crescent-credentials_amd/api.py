@@ -28,6 +28,7 @@ CG_FLAG_LATENCY_MODE, CG_FLAG_THROUGHPUT_MODE, CG_FLAG_SPIN_WAIT, CG_FLAG_CONTIG
 CG_FLAG_STAGED_LOAD = 64
 CG_FLAG_NO_LONE_SLOT = 128
 CG_FLAG_CHECK_WITNESS = 256
+CG_FLAG_SCALARS_MONTGOMERY = 512
 CG_ERR_UNSATISFIED = -8
 CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
 CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED = 0, 1, 2      # PublicIOType, creds/src/structs.rs:33-37
@@ -200,6 +201,8 @@ _SIGNATURES = {
     "cg_qap_check_witness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_CgWitnessReport)]),
     "cg_domain_size": (C.c_uint64, [C.c_void_p]),
     "cg_qap_load": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(_CgCsr), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32]),
+    "cg_qap_load_form": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(_CgCsr), C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint32]),
+    "cg_scalars_convert": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64]),
     "cg_qap_witness_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "cg_qap_domain_size": (C.c_uint64, [C.c_void_p]),
     "cg_qap_free": (None, [C.c_void_p]),
@@ -308,6 +311,23 @@ def scalars_to_array(vals: Sequence[int]) -> np.ndarray:
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def scalars_convert(a, in_form: int, out_form: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """cg_scalars_convert: n x 32 B scalars from one form (CG_FORM_CANONICAL / CG_FORM_MONTGOMERY) to the other, on the
+    library's host threads; no GPU involved.  out: a writable uint8 array of the same size to convert into (`a` itself
+    converts in place); default a new array.  An element >= r raises CrescentGpuError naming its index; `out` is then
+    untouched."""
+    src = a if isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags.c_contiguous else _u8(a)
+    src = src.reshape(-1)
+    if src.size % 32:
+        raise ValueError("length is not a multiple of 32 bytes")
+    if out is None:
+        out = np.empty(src.size, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable or out.size != src.size:
+        raise ValueError("out must be a writable contiguous uint8 array of the input's size")
+    _check(lib().cg_scalars_convert(_ptr(src) if src.size else None, in_form, _ptr(out) if out.size else None, out_form, src.size // 32))
+    return out
 
 
 def show_rand_count(io_types) -> int:
@@ -513,8 +533,11 @@ class Prover:
                  shard_rank: int = 0, shard_count: int = 1, proof_slots: int = 1, h_coefficient_basis: bool = False,
                  mode: Optional[str] = None, spin_wait: bool = False, contiguous_h_shards: bool = False,
                  h_scalars_external: bool = False, flags: int = 0, staged_load: bool = False, shard_span: Optional[Tuple[int, int]] = None,
-                 lone_slot: bool = True, check_witness: bool = False):
-        """check_witness=True: CG_FLAG_CHECK_WITNESS - every proving / witness-map call on the context first checks that the
+                 lone_slot: bool = True, check_witness: bool = False, scalars_montgomery: bool = False):
+        """scalars_montgomery=True: CG_FLAG_SCALARS_MONTGOMERY - every assignment the context receives is x * 2^256 mod r per
+        element (arkworks' in-memory Fr) and witness_map returns its coefficients in that form; r, s, the witness report and
+        the vectors passed between shards stay canonical.
+        check_witness=True: CG_FLAG_CHECK_WITNESS - every proving / witness-map call on the context first checks that the
         witness satisfies the R1CS and raises UnsatisfiedWitness instead of returning a proof that cannot verify.
         lone_slot=False: CG_FLAG_NO_LONE_SLOT (a throughput context then holds no extra slot for proofs that arrive alone).
         h_coefficient_basis=True keeps the h query as loaded (seven transforms per proof, CG_FLAG_H_COEFFICIENT_BASIS).
@@ -531,7 +554,7 @@ class Prover:
                  (CG_FLAG_THROUGHPUT_MODE if mode == "throughput" else 0) | (CG_FLAG_SPIN_WAIT if spin_wait else 0) | \
                  (CG_FLAG_CONTIGUOUS_H_SHARDS if contiguous_h_shards else 0) | (CG_FLAG_H_SCALARS_EXTERNAL if h_scalars_external else 0) | \
                  (CG_FLAG_STAGED_LOAD if staged_load else 0) | (0 if lone_slot else CG_FLAG_NO_LONE_SLOT) | \
-                 (CG_FLAG_CHECK_WITNESS if check_witness else 0)
+                 (CG_FLAG_CHECK_WITNESS if check_witness else 0) | (CG_FLAG_SCALARS_MONTGOMERY if scalars_montgomery else 0)
         L = lib()
         self.num_inputs = matrices.num_instance_variables
         self.num_constraints = matrices.num_constraints
@@ -793,13 +816,16 @@ def host_unregister(a: np.ndarray) -> None:
 class QapContext:
     """Three constraint matrices resident on one GPU with their domain tables, no proving key (cg_qap_ctx)."""
 
-    def __init__(self, matrices: ConstraintMatrices, device: int = -1):
+    def __init__(self, matrices: ConstraintMatrices, device: int = -1, scalar_form: int = CG_FORM_CANONICAL):
+        """scalar_form: the form of the assignments witness_map / check_witness take and of the h witness_map returns
+        (cg_qap_load_form); CG_FORM_MONTGOMERY = arkworks' in-memory Fr"""
         self.num_inputs = matrices.num_instance_variables
         self.num_constraints = matrices.num_constraints
         self.num_variables = matrices.num_variables
         abc, _keep = matrices._c()
         self._h = C.c_void_p()
-        _check(lib().cg_qap_load(C.byref(self._h), abc, self.num_inputs, self.num_constraints, self.num_variables, device))
+        _check(lib().cg_qap_load_form(C.byref(self._h), abc, self.num_inputs, self.num_constraints, self.num_variables, device, scalar_form))
+        self.scalar_form = scalar_form
         self.domain_size = int(lib().cg_qap_domain_size(self._h))
         self._lease_lock = threading.Lock()
         self._leases = 0
@@ -1441,7 +1467,9 @@ class MsmContext:
     """A fixed set of G1 (group=1) or G2 (group=2) bases resident on the GPU with its window tables; `run` is
     msm_bigint against them (cg_msm_load_* / cg_msm_run)."""
 
-    def __init__(self, bases, group: int = 1, coord_form: int = CG_FORM_CANONICAL, window_bits: int = 0, device: int = -1):
+    def __init__(self, bases, group: int = 1, coord_form: int = CG_FORM_CANONICAL, window_bits: int = 0, device: int = -1,
+                 scalars_montgomery: bool = False):
+        """scalars_montgomery=True: CG_FLAG_SCALARS_MONTGOMERY - run / run_dev take x * 2^256 mod r per scalar"""
         if group not in (1, 2):
             raise ValueError("group must be 1 or 2")
         self.group = group
@@ -1450,7 +1478,7 @@ class MsmContext:
         if b.size % self.point_bytes:
             raise ValueError("bases length is not a multiple of %d bytes" % self.point_bytes)
         self.n = b.size // self.point_bytes
-        opt = _CgOptions(device=device, window_bits=window_bits)
+        opt = _CgOptions(device=device, window_bits=window_bits, flags=CG_FLAG_SCALARS_MONTGOMERY if scalars_montgomery else 0)
         self._h = C.c_void_p()
         load = lib().cg_msm_load_g1 if group == 1 else lib().cg_msm_load_g2
         _check(load(C.byref(self._h), _ptr(b) if b.size else None, coord_form, self.n, C.byref(opt)))
@@ -1460,7 +1488,7 @@ class MsmContext:
         return self._run(_ptr(s) if s.size else None, 0, s.size // 32, timings)
 
     def run_dev(self, d_ptr: int, n_scalars: int, timings: bool = False):
-        """scalars already on this context's GPU (device pointer, n_scalars x 32 B canonical)"""
+        """scalars already on this context's GPU (device pointer, n_scalars x 32 B in the handle's form; not written)"""
         return self._run(d_ptr, 1, n_scalars, timings)
 
     def _run(self, ptr, on_device, n, timings):

@@ -18,6 +18,7 @@
 
 #include "msm.hpp"
 #include "ntt.hpp"
+#include "scalar_form.hpp"
 #include "wmap29.hpp"
 
 namespace cg {
@@ -169,6 +170,9 @@ struct ProofSlot {
     // streams and the latency arrangement of the engines, as a latency context's only slot has them
     bool lone = false;
     hipEvent_t ev_t[2] = {nullptr, nullptr};
+    // CG_FLAG_SCALARS_MONTGOMERY: the verdict of the conversion pass that brought this proof's assignment into its upload
+    // buffer (Upload::bad; set by the call's frame, read with the slot's own input check - input_verdict)
+    const uint32_t* up_bad = nullptr;
     ~ProofSlot() {
         for (int i = 0; i < 5; ++i)
             if (st[i] && !st_borrowed[i] && (i == 0 || st[i] != st[0])) (void)hipStreamDestroy(st[i]);
@@ -189,7 +193,10 @@ struct Upload {
     hipStream_t st = nullptr;          // one of the context's few copy-only streams (cg_ctx::up_streams: owned there)
     hipEvent_t ev[2] = {nullptr, nullptr};
     hipEvent_t ev_done = nullptr;      // recorded behind the copy and polled (wait_sleeping)
+    PinnedBuf<uint32_t> bad;           // CG_FLAG_SCALARS_MONTGOMERY: host memory the conversion pass sets when it meets an element >= r
+    hipEvent_t ev_pass = nullptr;      // ... and the end of that pass (timed calls; it starts at ev[1])
     ~Upload() {
+        if (ev_pass) (void)hipEventDestroy(ev_pass);
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         if (ev_done) (void)hipEventDestroy(ev_done);
     }
@@ -341,6 +348,11 @@ struct cg_ctx {
     bool spin_wait = false;      // CG_FLAG_SPIN_WAIT
     bool external_q = false;     // CG_FLAG_H_SCALARS_EXTERNAL: no witness-map resources; the h scalars arrive with every proof
     bool check_witness = false;  // CG_FLAG_CHECK_WITNESS: every witness map also checks a·b = c row by row (wmap29.hpp SatCheck29)
+    // CG_FLAG_SCALARS_MONTGOMERY: assignments arrive as x·2^256 mod r (arkworks' Fr.0).  Every one of them - a device-resident
+    // one too, whose buffer is the caller's and stays as it is - goes through an upload buffer, where one pass makes it the
+    // plain integers everything downstream reads (scalar_form.hpp; CallFrame); cg_witness_map's coefficients go back out
+    // through the opposite pass
+    bool mont_scalars = false;
     // device bytes that stay resident (cg_ctx_get_info): window tables + validity flags | matrices and domain tables | one slot
     // (slot_bytes is the sum of slot_part: entry lists, segment pieces, bucket arrays and reduction buffers, the witness
     // map's vectors + the h MSM's scalars, one upload buffer - account_slot)
@@ -735,7 +747,7 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
         return fail(CG_ERR_INVALID_ARGUMENT, "shard_span needs a sharded context and 0 <= lo < hi <= 10000");
     constexpr int32_t KNOWN_FLAGS = CG_FLAG_H_COEFFICIENT_BASIS | CG_FLAG_LATENCY_MODE | CG_FLAG_THROUGHPUT_MODE | CG_FLAG_SPIN_WAIT |
                                     CG_FLAG_CONTIGUOUS_H_SHARDS | CG_FLAG_H_SCALARS_EXTERNAL | CG_FLAG_STAGED_LOAD | CG_FLAG_NO_LONE_SLOT |
-                                    CG_FLAG_CHECK_WITNESS;
+                                    CG_FLAG_CHECK_WITNESS | CG_FLAG_SCALARS_MONTGOMERY;
     if (opt && (opt->flags & ~KNOWN_FLAGS)) return fail(CG_ERR_INVALID_ARGUMENT, "unknown bits in flags");
     if (opt && (opt->flags & CG_FLAG_H_SCALARS_EXTERNAL) && ((opt->flags & CG_FLAG_H_COEFFICIENT_BASIS) || shard_count <= 1))
         return fail(CG_ERR_INVALID_ARGUMENT, "flags: CG_FLAG_H_SCALARS_EXTERNAL needs a sharded context over the folded key");
@@ -778,6 +790,7 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
         c->folded = !(opt && (opt->flags & CG_FLAG_H_COEFFICIENT_BASIS));
         c->external_q = opt && (opt->flags & CG_FLAG_H_SCALARS_EXTERNAL);
         c->check_witness = opt && (opt->flags & CG_FLAG_CHECK_WITNESS);
+        c->mont_scalars = opt && (opt->flags & CG_FLAG_SCALARS_MONTGOMERY);
         // a staged load proves in the reference's arrangement first (see CG_FLAG_STAGED_LOAD); sharded contexts and contexts
         // that keep that arrangement for good load synchronously
         const bool staged = opt && (opt->flags & CG_FLAG_STAGED_LOAD) && c->folded && shard_count == 1;
@@ -949,6 +962,10 @@ extern "C" int cg_circuit_load(cg_ctx** out, const cg_proving_key* pk, const cg_
             u->st = c->up_streams[(size_t)k % c->up_streams.size()];
             for (auto& e : u->ev) CG_HIP(hipEventCreate(&e));
             CG_HIP(hipEventCreateWithFlags(&u->ev_done, hipEventDisableTiming));
+            if (c->mont_scalars) {
+                u->bad.alloc(1);
+                CG_HIP(hipEventCreate(&u->ev_pass));
+            }
             c->uploads.push_back(std::move(u));
         }
         // two of them: with two proofs in flight both still gain (145 against 123-131 proofs/s at 2^21); a third buys nothing
@@ -1034,7 +1051,7 @@ static int unsatisfied(const cg_ctx* c, const ProofSlot* S) {
 // What the slot's input check, and the witness check if this call's witness map queued one (`checked`), found; read after
 // the call's own synchronisation.  with_slice: caller-supplied h scalars were checked with the assignment.
 static int input_verdict(const cg_ctx* c, const ProofSlot* S, bool with_slice, bool checked) {
-    if (S->wm.h_bad_input.p[0])
+    if (S->wm.h_bad_input.p[0] || (S->up_bad && *S->up_bad))
         return fail(CG_ERR_INVALID_ARGUMENT, with_slice ? "full_assignment or the h-scalar slice holds a value >= the scalar field modulus"
                                                         : "full_assignment holds a value >= the scalar field modulus");
     return checked ? unsatisfied(c, S) : CG_OK;
@@ -1160,17 +1177,28 @@ static void wait_for_slot(const cg_ctx* c, ProofSlot* S) {
 // several streams share and stalls kernels of OTHER proofs behind it: 171 proofs/s against 184-187 with the wait here
 // (profiles/r03_a_host_witness.txt).  Page-locked source (cg_host_alloc / cg_host_register): one DMA at PCIe speed;
 // pageable source: staged by the runtime through its own pinned buffers, inside the call.  Returns the copy's ms (timed).
-static float upload_assignment(cg_ctx* c, Upload* u, const void* host_assignment, bool timed) {
-    if (timed) CG_HIP(hipEventRecord(u->ev[0], u->st));
-    CG_HIP(hipMemcpyAsync(u->w.p, host_assignment, c->M * 32, hipMemcpyHostToDevice, u->st));
+// CG_FLAG_SCALARS_MONTGOMERY: the pass that makes the assignment plain integers is queued behind the copy, in place, and
+// waited for with it, so every stream that reads u->w afterwards sees what it sees on any other context (the pass is in
+// cg_timings.total_ms and on its own in reserved_ms, not in upload_ms: *pass_ms).  An assignment that is ALREADY on the
+// device (on_device; such a context only) is the caller's and is not written: the pass reads it there and writes u->w - no
+// copy, upload_ms = 0.
+static float upload_assignment(cg_ctx* c, Upload* u, const void* assignment, bool timed, bool on_device, float* pass_ms) {
+    if (timed && !on_device) CG_HIP(hipEventRecord(u->ev[0], u->st));
+    if (!on_device) CG_HIP(hipMemcpyAsync(u->w.p, assignment, c->M * 32, hipMemcpyHostToDevice, u->st));
     if (timed) CG_HIP(hipEventRecord(u->ev[1], u->st));
+    if (c->mont_scalars) {
+        u->bad.p[0] = 0;
+        scalars_from_mont(on_device ? (const Fr*)assignment : u->w.p, u->w.p, c->M, u->bad.dev(), u->st);
+        if (timed) CG_HIP(hipEventRecord(u->ev_pass, u->st));
+    }
     if (c->spin_wait || c->latency) {
         CG_HIP(hipStreamSynchronize(u->st));
     } else {
         CG_HIP(hipEventRecord(u->ev_done, u->st));
         wait_sleeping(u->ev_done, 50);             // a 48 MB copy takes ~1 ms
     }
-    return timed ? ev_ms(u->ev[0], u->ev[1]) : 0.f;
+    if (timed && c->mont_scalars) *pass_ms = ev_ms(u->ev[1], u->ev_pass);
+    return timed && !on_device ? ev_ms(u->ev[0], u->ev[1]) : 0.f;
 }
 
 static const char* const BROKEN_CONTEXT = "a window re-tune ran out of device memory while re-sizing the proof slots: free this context and load the circuit again";
@@ -1187,6 +1215,7 @@ struct CallFrame {
     const Fr* w_dev = nullptr;         // the assignment in device memory: the caller's own buffer, or the upload's
     ProofSlot* S = nullptr;
     float upload_ms = 0.f;             // (timed)
+    float convert_ms = 0.f;            // (timed) CG_FLAG_SCALARS_MONTGOMERY: the pass that made the assignment plain integers
     CallFrame(cg_ctx* ctx, const void* assignment, bool on_device, bool may_run_alone, bool timed = false, bool handle = false)
         : inside(ctx), c(ctx), in_handle(handle), exceptions(std::uncaught_exceptions()) {
         try {
@@ -1201,12 +1230,13 @@ struct CallFrame {
             // have failed half-way: the engines of the slots are then cut for the old window against the rebuilt table
             if (c->broken) throw HipError(CG_ERR_OUT_OF_MEMORY, BROKEN_CONTEXT);
             w_dev = (const Fr*)assignment;
-            if (!on_device) {          // before the slot: an upload never holds a working set
+            if (!on_device || c->mont_scalars) {          // before the slot: an upload never holds a working set
                 up = c->acquire_upload();
-                upload_ms = upload_assignment(c, up, assignment, timed);
+                upload_ms = upload_assignment(c, up, assignment, timed, on_device, &convert_ms);
                 w_dev = up->w.p;
             }
             S = c->acquire(may_run_alone);
+            S->up_bad = c->mont_scalars ? up->bad.p : nullptr;
         } catch (...) {
             release();
             throw;
@@ -1221,6 +1251,7 @@ struct CallFrame {
             // cg_prove_partial_q_abort and a failed _finish: drain them before the working set is handed to the next proof
             if (in_handle || std::uncaught_exceptions() > exceptions)
                 for (auto st : S->st) if (st) (void)hipStreamSynchronize(st);
+            S->up_bad = nullptr;
             c->release(S);
             S = nullptr;
         }
@@ -1546,7 +1577,7 @@ static int prove_on_slot(cg_ctx* ctx, const void* assignment, bool on_device, co
         const std::function<void()> overlap = [&]() { pre = delta_multiples(ctx, r, s); };
         CallFrame f(ctx, assignment, on_device, tm == nullptr, tm != nullptr);
         if (int e = prove_partial_impl(ctx, f.S, f.w_dev, scalar_is_zero(r), P, tm, ts, s ? &overlap : nullptr, supplied)) return e;
-        if (tm) { tm->upload_ms = f.upload_ms; tm->total_ms += f.upload_ms; }
+        if (tm) { tm->upload_ms = f.upload_ms; tm->reserved_ms = f.convert_ms; tm->total_ms += f.upload_ms + f.convert_ms; }
         f.release();
         maybe_retune(ctx, ts);
         if (!s) {
@@ -1772,6 +1803,7 @@ extern "C" int cg_witness_map(cg_ctx* ctx, const uint8_t* full_assignment, uint8
         CallFrame f(ctx, full_assignment, false, false);
         hipStream_t s0 = f.S->st[0];
         run_witness_map(ctx, f.S, f.w_dev, s0, false);   // the reference's result: coefficients
+        if (ctx->mont_scalars) scalars_to_mont(f.S->h_canon.p, f.S->h_canon.p, ctx->D, s0);      // ... in the form the assignment came in
         CG_HIP(hipMemcpyAsync(h_out, f.S->h_canon.p, ctx->D * 32, hipMemcpyDeviceToHost, s0));
         CG_HIP(hipStreamSynchronize(s0));
         return input_verdict(ctx, f.S, false, ctx->check_witness);

@@ -10,7 +10,9 @@
 #include <mutex>
 #include <thread>
 
+#include "host_parallel.hpp"
 #include "msm.hpp"
+#include "scalar_form.hpp"
 #include "wmap29.hpp"
 
 using namespace cg;
@@ -22,6 +24,7 @@ struct cg_msm_ctx {
     int device = 0;
     int group = 1;
     uint64_t n = 0;
+    bool mont_scalars = false;     // CG_FLAG_SCALARS_MONTGOMERY: cg_msm_run's scalars are x·2^256 mod r
     MsmBases<Fq> b1;
     MsmBases<Fq2> b2;
     MsmEngine<Fq> e1;
@@ -60,6 +63,7 @@ static int msm_load(cg_msm_ctx** out, int group, const uint8_t* bases, uint32_t 
         c->device = dev;
         c->group = group;
         c->n = n;
+        c->mont_scalars = opt && (opt->flags & CG_FLAG_SCALARS_MONTGOMERY);
         CG_HIP(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
         int wb = opt ? opt->window_bits : 0;
         if (wb < 0 || wb == 1 || wb > 22) return fail(CG_ERR_INVALID_ARGUMENT, "window_bits must be 0 or in [2, 22]");
@@ -135,8 +139,15 @@ extern "C" int cg_msm_run(cg_msm_ctx* ctx, const void* scalars, int scalars_on_d
             sc = ctx->scalars.p;
         }
         CG_HIP(hipMemsetAsync(ctx->bad.p, 0, 4, st));
-        k_check_canonical<<<ceil_div(n, 256), 256, 0, st>>>(sc, n, ctx->bad.p);
-        CG_KERNEL_CHECK();
+        if (ctx->mont_scalars) {
+            // one pass converts the pairs the MSM uses and checks them (scalar_form.hpp): in place behind the copy, or out
+            // of the caller's device buffer, which is not written
+            scalars_from_mont(sc, ctx->scalars.p, n, ctx->bad.p, st);
+            sc = ctx->scalars.p;
+        } else {
+            k_check_canonical<<<ceil_div(n, 256), 256, 0, st>>>(sc, n, ctx->bad.p);
+            CG_KERNEL_CHECK();
+        }
         CG_HIP(hipMemcpyAsync(ctx->h_bad.p, ctx->bad.p, 4, hipMemcpyDeviceToHost, st));
         if (ctx->group == 1) {
             ctx->e1.digits(sc, n, st);
@@ -233,6 +244,11 @@ struct cg_qap_ctx {
     Wm29Domain wdom;
     Wm29Buffers wm;
     DevBuf<Fr> w_canon, h_canon;
+    // cg_qap_load_form(CG_FORM_MONTGOMERY): assignments arrive, and h goes back, as x·2^256 mod r.  The pass that makes an
+    // assignment plain integers in w_canon reports an element >= r here (host memory: the witness map's own flag is
+    // cleared when the map is queued, which may be after the pass has run)
+    bool mont_scalars = false;
+    PinnedBuf<uint32_t> form_bad;
     hipStream_t st = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};     // cg_qap_check_witness: check_ms
     std::mutex mu;
@@ -253,8 +269,14 @@ const char* csr_view_problem(const cg_csr& m) {
 
 extern "C" int cg_qap_load(cg_qap_ctx** out, const cg_csr abc[3], uint64_t num_inputs, uint64_t num_constraints,
                            uint64_t num_variables, int32_t device) {
+    return cg_qap_load_form(out, abc, num_inputs, num_constraints, num_variables, device, CG_FORM_CANONICAL);
+}
+
+extern "C" int cg_qap_load_form(cg_qap_ctx** out, const cg_csr abc[3], uint64_t num_inputs, uint64_t num_constraints,
+                                uint64_t num_variables, int32_t device, uint32_t scalar_form) {
     if (!out || !abc) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
+    if (!scalar_form_known(scalar_form)) return fail(CG_ERR_INVALID_ARGUMENT, "bad scalar_form (CG_FORM_CANONICAL or CG_FORM_MONTGOMERY)");
     if (num_inputs == 0 || num_inputs > num_variables) return fail(CG_ERR_INVALID_ARGUMENT, "need 1 <= num_inputs <= num_variables");
     for (int k = 0; k < 3; ++k)
         if (const char* why = csr_view_problem(abc[k])) return fail(CG_ERR_INVALID_ARGUMENT, "matrix %d: %s", k, why);
@@ -285,6 +307,8 @@ extern "C" int cg_qap_load(cg_qap_ctx** out, const cg_csr abc[3], uint64_t num_i
         c->wm.alloc(c->M, c->D, std::max(c->A.sell_scratch, std::max(c->B.sell_scratch, c->C.sell_scratch)));
         c->w_canon.alloc(c->M);
         c->h_canon.alloc(c->D);
+        c->mont_scalars = scalar_form == CG_FORM_MONTGOMERY;
+        if (c->mont_scalars) c->form_bad.alloc(1);
         *out = c.release();
         return CG_OK;
     } catch (...) {
@@ -294,23 +318,42 @@ extern "C" int cg_qap_load(cg_qap_ctx** out, const cg_csr abc[3], uint64_t num_i
 
 extern "C" uint64_t cg_qap_domain_size(const cg_qap_ctx* ctx) { return ctx ? ctx->D : 0; }
 
+static const char* const BAD_ASSIGNMENT = "full_assignment holds a value >= the scalar field modulus";
+
+// The assignment as plain integers in device memory, queued on the handle's stream: the caller's device buffer as it is,
+// or w_canon after the copy from the host; a Montgomery handle converts into w_canon either way (in place behind the
+// copy, or out of the caller's buffer, which is not written)
+static const Fr* qap_assignment(cg_qap_ctx* ctx, const void* full_assignment, int on_device) {
+    const Fr* w = (const Fr*)full_assignment;
+    if (!on_device) {
+        CG_HIP(hipMemcpyAsync(ctx->w_canon.p, full_assignment, ctx->M * 32, hipMemcpyHostToDevice, ctx->st));
+        w = ctx->w_canon.p;
+    }
+    if (ctx->mont_scalars) {
+        ctx->form_bad.p[0] = 0;
+        scalars_from_mont(w, ctx->w_canon.p, ctx->M, ctx->form_bad.dev(), ctx->st);
+        w = ctx->w_canon.p;
+    }
+    return w;
+}
+static bool qap_bad_input(const cg_qap_ctx* ctx) { return ctx->wm.h_bad_input.p[0] || (ctx->mont_scalars && ctx->form_bad.p[0]); }
+
 extern "C" int cg_qap_witness_map(cg_qap_ctx* ctx, const void* full_assignment, int assignment_on_device, void* h_out,
                                   int h_on_device) {
     if (!ctx || !full_assignment || !h_out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     try {
         std::lock_guard<std::mutex> lk(ctx->mu);
         CG_HIP(hipSetDevice(ctx->device));
-        const Fr* w = (const Fr*)full_assignment;
-        if (!assignment_on_device) {
-            CG_HIP(hipMemcpyAsync(ctx->w_canon.p, full_assignment, ctx->M * 32, hipMemcpyHostToDevice, ctx->st));
-            w = ctx->w_canon.p;
-        }
-        Fr* h = h_on_device ? (Fr*)h_out : ctx->h_canon.p;
+        const Fr* w = qap_assignment(ctx, full_assignment, assignment_on_device);
+        // a Montgomery handle computes into h_canon and converts on the way out: in place before the download, or into
+        // the caller's device buffer
+        Fr* h = h_on_device && !ctx->mont_scalars ? (Fr*)h_out : ctx->h_canon.p;
         wm29_run(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, ctx->wm, w, ctx->M, ctx->m, ctx->l, h, ctx->st,
                  false);
+        if (ctx->mont_scalars) scalars_to_mont(ctx->h_canon.p, h_on_device ? (Fr*)h_out : ctx->h_canon.p, ctx->D, ctx->st);
         if (!h_on_device) CG_HIP(hipMemcpyAsync(h_out, ctx->h_canon.p, ctx->D * 32, hipMemcpyDeviceToHost, ctx->st));
         CG_HIP(hipStreamSynchronize(ctx->st));
-        if (ctx->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+        if (qap_bad_input(ctx)) return fail(CG_ERR_INVALID_ARGUMENT, BAD_ASSIGNMENT);
         return CG_OK;
     } catch (...) {
         return translate_current_exception();
@@ -323,16 +366,12 @@ extern "C" int cg_qap_check_witness(cg_qap_ctx* ctx, const void* full_assignment
     try {
         std::lock_guard<std::mutex> lk(ctx->mu);
         CG_HIP(hipSetDevice(ctx->device));
-        const Fr* w = (const Fr*)full_assignment;
-        if (!assignment_on_device) {
-            CG_HIP(hipMemcpyAsync(ctx->w_canon.p, full_assignment, ctx->M * 32, hipMemcpyHostToDevice, ctx->st));
-            w = ctx->w_canon.p;
-        }
+        const Fr* w = qap_assignment(ctx, full_assignment, assignment_on_device);
         CG_HIP(hipEventRecord(ctx->ev[0], ctx->st));
         wm29_check(ctx->wdom, ctx->A, ctx->B, ctx->C, ctx->dA, ctx->dB, ctx->dC, ctx->wm, w, ctx->M, ctx->m, ctx->l, ctx->st);
         CG_HIP(hipEventRecord(ctx->ev[1], ctx->st));
         CG_HIP(hipStreamSynchronize(ctx->st));
-        if (ctx->wm.h_bad_input.p[0]) return fail(CG_ERR_INVALID_ARGUMENT, "full_assignment holds a value >= the scalar field modulus");
+        if (qap_bad_input(ctx)) return fail(CG_ERR_INVALID_ARGUMENT, BAD_ASSIGNMENT);
         const unsigned long long n = ctx->wm.sat.h_rec.p[0], first = ctx->wm.sat.h_rec.p[1];
         if (report) {
             memset(report, 0, sizeof(*report));
@@ -355,6 +394,41 @@ extern "C" void cg_qap_free(cg_qap_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     delete ctx;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fr vectors between the two forms on the host (no HIP call): for hosts that hold one form and need the other
+// ---------------------------------------------------------------------------------------------
+extern "C" int cg_scalars_convert(const uint8_t* in, uint32_t in_form, uint8_t* out, uint32_t out_form, uint64_t n) {
+    if (!scalar_form_known(in_form) || !scalar_form_known(out_form)) return fail(CG_ERR_INVALID_ARGUMENT, "bad form (CG_FORM_CANONICAL or CG_FORM_MONTGOMERY)");
+    if (n == 0) return CG_OK;
+    if (!in || !out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (n > (~(uint64_t)0) / 32) return fail(CG_ERR_INVALID_ARGUMENT, "n x 32 bytes exceeds the address space");
+    try {
+        // every element is looked at before the first is written (in == out included): a refused vector is left as it was.
+        // parallel_ranges rethrows the LOWEST range's exception, and a range stops at its first bad element
+        parallel_ranges(n, 256, [&](uint64_t lo, uint64_t hi) {
+            for (uint64_t i = lo; i < hi; ++i)
+                if (!scalar_is_canonical(in + 32 * i)) {
+                    char b[128];
+                    snprintf(b, sizeof(b), "element %llu is not a field element (>= the scalar field modulus)", (unsigned long long)i);
+                    throw HipError(CG_ERR_INVALID_ARGUMENT, b);
+                }
+        });
+        parallel_ranges(n, 256, [&](uint64_t lo, uint64_t hi) {
+            if (in_form == out_form) {
+                if (in != out) memmove(out + 32 * lo, in + 32 * lo, 32 * (hi - lo));
+                return;
+            }
+            for (uint64_t i = lo; i < hi; ++i) {
+                const Fr x = fp_from_bytes<Fr>(in + 32 * i);
+                fp_to_bytes(out_form == CG_FORM_MONTGOMERY ? to_mont(x) : from_mont(x), out + 32 * i);
+            }
+        });
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

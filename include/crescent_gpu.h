@@ -18,7 +18,18 @@
  *   - G1 affine point  = x ‖ y                  (64 bytes);   identity = 64 zero bytes
  *   - G2 affine point  = x.c0 ‖ x.c1 ‖ y.c0 ‖ y.c1 (128 bytes); identity = 128 zero bytes
  *     (same component order as snarkjs/arkworks, zkey.rs:421-431)
- *   - Scalars (witness, r, s) are always CG_FORM_CANONICAL.
+ *   - Scalars are CG_FORM_CANONICAL, with ONE exception a host opts into: on a handle loaded with
+ *     CG_FLAG_SCALARS_MONTGOMERY (cg_circuit_load, cg_msm_load_g1/g2) or cg_qap_load_form(.., CG_FORM_MONTGOMERY) every
+ *     ASSIGNMENT a call receives - full_assignment / d_full_assignment of cg_prove, cg_prove_dev, cg_check_witness,
+ *     cg_prove_partial, cg_prove_partial_q, cg_prove_partial_q_begin, cg_witness_map, cg_witness_map_coset,
+ *     cg_witness_map_coset_half, cg_qap_witness_map, cg_qap_check_witness; `scalars` of cg_msm_run - is
+ *     CG_FORM_MONTGOMERY, i.e. a `Vec<Fr>` as it lies in memory, and the coefficients cg_witness_map /
+ *     cg_qap_witness_map return are in the same form.  The GPU converts (one pass over the vector; a device-resident
+ *     assignment is read, never written).  A Montgomery element >= r is not a field element: CG_ERR_INVALID_ARGUMENT,
+ *     nothing written, exactly as for a non-canonical element.  Canonical on every handle: the single scalars r, s;
+ *     the a/b/c of cg_witness_report; the vectors no host computes with and only passes from shard to shard (q_out,
+ *     q_slice, a_slice, b_slice, the _half outputs); proofs and partial records.  cg_scalars_convert changes a vector's
+ *     form on the host.
  *   - Every function returns CG_OK (0) or a negative cg_status; cg_last_error() returns a
  *     thread-local human-readable message for the last failure on the calling thread.
  *   - The caller owns every host buffer; the library copies what it keeps.
@@ -170,7 +181,16 @@ enum {
      * read after the synchronisation the call makes anyway.  NOT checked: the _q forms (cg_prove_partial_q, _q_finish,
      * _q_finish2), whose h scalars come from outside, and the _half forms, which see one matrix only.
      * With CG_FLAG_H_SCALARS_EXTERNAL (no matrices on the context) the load is CG_ERR_INVALID_ARGUMENT. */
-    CG_FLAG_CHECK_WITNESS = 256
+    CG_FLAG_CHECK_WITNESS = 256,
+    /* Assignments in arkworks' in-memory form (Conventions): every assignment a call on this context receives is
+     * x·2^256 mod r, 32 little-endian bytes per element - `Fr.0`, so a Rust host copies its `Vec<Fr>` as it is instead of
+     * running `into_bigint()` over it - and cg_witness_map returns its coefficients in that form.  The context converts on
+     * the GPU: a host assignment in place in its upload buffer, behind the copy; a device-resident one (cg_prove_dev, ..)
+     * from the caller's buffer, which is not written, into an upload buffer.  An element >= r is refused as a
+     * non-canonical one is on other contexts.  Combines with every other flag; also honoured by cg_msm_load_g1/g2 (the
+     * `scalars` of cg_msm_run).  cg_timings of such a context: upload_ms stays the copy alone; the pass is part of
+     * total_ms and is reported on its own in reserved_ms (0 on every other context). */
+    CG_FLAG_SCALARS_MONTGOMERY = 512
 };
 
 /* Per-phase wall/GPU times of one cg_prove call, mirroring the reference's `print-trace` phases
@@ -193,7 +213,7 @@ typedef struct cg_timings {
     float accum_g1_ms;     /* bucket-accumulation kernel (k_accum_affine<Fq>), the four G1 MSMs */
     float accum_g2_ms;     /* same kernel over Fq2 (the G2 MSM) */
     float sort_ms;         /* grouping the digit entries by bucket (counting partition), all five MSMs */
-    float reserved_ms;
+    float reserved_ms;     /* CG_FLAG_SCALARS_MONTGOMERY contexts: the Montgomery -> canonical pass over the assignment; else 0 */
     uint64_t entries_g1;   /* non-zero signed digits (= mixed additions) accumulated, G1 */
     uint64_t entries_g2;
     uint32_t accum_g1_launches;
@@ -230,7 +250,8 @@ void cg_circuit_free(cg_ctx* ctx);
  * Replaces: `Groth16::<E,QAP>::create_proof_with_reduction_and_matrices`,
  *           forks/groth16/src/prover.rs:26-51 (and through it :54-136, :256-274 and
  *           r1cs_to_qap.rs:150-213).
- * full_assignment: num_variables x 32 B canonical (instance ‖ witness, full_assignment[0] = 1).
+ * full_assignment: num_variables x 32 B canonical - Montgomery on a CG_FLAG_SCALARS_MONTGOMERY context, here and in every
+ *       entry point below that takes one - (instance ‖ witness, full_assignment[0] = 1).
  * r, s: 32 B canonical each (prover.rs:150-151 samples them; r = s = 0 gives the no-zk proof,
  *       prover.rs:160-173).
  * proof_out: 256 B = ark-serialize uncompressed a ‖ b ‖ c (data_structures.rs:7-14).
@@ -429,6 +450,13 @@ int cg_qap_witness_map(cg_qap_ctx* ctx, const void* full_assignment, int assignm
 /* cg_check_witness on the key-less handle: where the reference's own check sits (the circom builder, before any key). */
 int cg_qap_check_witness(cg_qap_ctx* ctx, const void* full_assignment, int assignment_on_device, cg_witness_report* report);
 uint64_t cg_qap_domain_size(const cg_qap_ctx* ctx);
+/* cg_qap_load with the form of the scalars that cross this handle: of the assignment cg_qap_witness_map and
+ * cg_qap_check_witness take, and of the h_out cg_qap_witness_map writes (host or device memory alike; a device-resident
+ * assignment is not written).  scalar_form = CG_FORM_MONTGOMERY is what an `impl R1CSToQAP` holds: `&[F]` in, `Vec<F>`
+ * out, no `into_bigint` / `from_bigint` on either side.  cg_witness_report's a/b/c stay canonical.  A form above
+ * CG_FORM_MONTGOMERY is CG_ERR_INVALID_ARGUMENT, reported before any HIP call.  cg_qap_load is this with CG_FORM_CANONICAL. */
+int cg_qap_load_form(cg_qap_ctx** out, const cg_csr abc[3], uint64_t num_inputs, uint64_t num_constraints,
+                     uint64_t num_variables, int32_t device /* -1 = current */, uint32_t scalar_form);
 void cg_qap_free(cg_qap_ctx* ctx);
 
 /* Unit level: Σ scalars[i]·bases[i] over BN254 G1 / G2 for caller-supplied bases.
@@ -441,6 +469,12 @@ int cg_msm_g1(const uint8_t* bases, uint32_t coord_form, uint64_t n_bases, const
 int cg_msm_g2(const uint8_t* bases, uint32_t coord_form, uint64_t n_bases, const uint8_t* scalars,
               uint64_t n_scalars, int32_t window_bits, uint8_t out[128]);
 
+/* n scalars from one form to the other (or copied, when the forms are equal), on the library's host threads.  Host only: no
+ * HIP call, works in a process without a GPU.  in == out is allowed (other overlaps are not).  An input element >= r, in
+ * either form, is CG_ERR_INVALID_ARGUMENT - cg_last_error names the index of the first one - and nothing is written.
+ * For hosts that hold one form and need the other (a C host feeding a CG_FLAG_SCALARS_MONTGOMERY context, tests). */
+int cg_scalars_convert(const uint8_t* in, uint32_t in_form, uint8_t* out, uint32_t out_form, uint64_t n);
+
 /* Unit level: in-place radix-2 NTT over Fr, natural order in and out, 2^log_n x 32 B canonical.
  * Replaces: `EvaluationDomain::{fft,ifft}_in_place` and the coset variants obtained through
  *           `get_coset(F::GENERATOR)` (ark-poly; call sites r1cs_to_qap.rs:179-185,198-199,210).
@@ -451,8 +485,10 @@ int cg_ntt(uint8_t* data, uint32_t log_n, int inverse, int coset);
  * of bases (a query of the key, a commitment key) or a domain keeps the expanded window tables / twiddle tables
  * in HBM and may pass scalars / data that already live on the device; these run exactly the kernels cg_prove
  * runs and are what `tools/sweep.py` times (SURVEY 8d "unit sweeps").
- *   cg_msm_load_g1/g2 : opt may be NULL; opt->device and opt->window_bits are honoured (0 = size-based default).
- *   cg_msm_run        : Σ scalars[i]·bases[i] over min(n_scalars, n_bases) pairs; scalars canonical, host or
+ *   cg_msm_load_g1/g2 : opt may be NULL; opt->device and opt->window_bits are honoured (0 = size-based default), and of
+ *                       opt->flags CG_FLAG_SCALARS_MONTGOMERY.
+ *   cg_msm_run        : Σ scalars[i]·bases[i] over min(n_scalars, n_bases) pairs; scalars canonical (Montgomery on a
+ *                       handle loaded with that flag: those pairs are converted, a device buffer is not written), host or
  *                       device memory; out = 64 B (G1) / 128 B (G2) affine canonical, zeros = identity.
  *                       timings (optional): the h (G1) or b2 (G2) MSM fields, accum_*, sort_ms, entries_*.
  *   cg_ntt_load/run   : in-place transform of 2^log_n canonical scalars in host or device memory, natural

@@ -3,7 +3,7 @@
  * torch, nothing in the process but libcrescent_gpu.so (and the build's own synthetic-circuit generator, libcg_synth.so,
  * which stands in for the circuit and witness a Crescent cache directory would supply: creds/src/lib.rs:255-283).
  *
- *   crescent_throughput [--shape l m M] [--bits f] [--slots T] [--proofs N] [--warmup W] [--pageable]
+ *   crescent_throughput [--shape l m M] [--bits f] [--slots T] [--proofs N] [--warmup W] [--pageable] [--montgomery]
  *
  * What it does, in the reference's terms: one-time `zksetup` (cg_setup: forks/groth16/src/generator.rs:50-228) and circuit
  * load, then T + 2 host threads that each call `Groth16::prove` (cg_prove: forks/groth16/src/prover.rs:26-51) in a loop
@@ -12,6 +12,10 @@
  * credential).  It reports the steady-state rate between the W-th and the (W + N)-th completion and the CPU time the
  * process spent meanwhile.  bench.py measures the same thing from Python; this program is the check that neither the
  * rate nor the host cost is an artefact of that harness.
+ *
+ * --montgomery: the host an arkworks prover is - its witnesses are `Vec<Fr>`, x * 2^256 mod r in memory.  The generated
+ * witness goes through cg_scalars_convert once (timed: the work `into_bigint()` over the assignment would cost such a host
+ * per proof, on this library's host threads), the context is loaded with CG_FLAG_SCALARS_MONTGOMERY and converts on the GPU.
  */
 #define _GNU_SOURCE
 #include <crescent_gpu.h>
@@ -104,7 +108,7 @@ static int cmp_double(const void* a, const void* b) {
 int main(int argc, char** argv) {
     uint64_t l = 26, m = 1480000, M = 1500000;          /* rs256-sd shape */
     double bits = 0.9;
-    int slots = 16, pageable = 0;
+    int slots = 16, pageable = 0, montgomery = 0;
     long proofs = 1200, warmup = 64;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--shape") && i + 3 < argc) { l = strtoull(argv[i + 1], NULL, 10); m = strtoull(argv[i + 2], NULL, 10); M = strtoull(argv[i + 3], NULL, 10); i += 3; }
@@ -113,7 +117,8 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--proofs") && i + 1 < argc) proofs = atol(argv[++i]);
         else if (!strcmp(argv[i], "--warmup") && i + 1 < argc) warmup = atol(argv[++i]);
         else if (!strcmp(argv[i], "--pageable")) pageable = 1;
-        else { fprintf(stderr, "usage: %s [--shape l m M] [--bits f] [--slots T] [--proofs N] [--warmup W] [--pageable]\n", argv[0]); return 2; }
+        else if (!strcmp(argv[i], "--montgomery")) montgomery = 1;
+        else { fprintf(stderr, "usage: %s [--shape l m M] [--bits f] [--slots T] [--proofs N] [--warmup W] [--pageable] [--montgomery]\n", argv[0]); return 2; }
     }
     if (slots < 1 || slots > 16 || proofs < 1 || warmup < 0) { fprintf(stderr, "bad arguments\n"); return 2; }
     if (cg_init(0, NULL) != CG_OK) { fprintf(stderr, "cg_init: %s\n", cg_last_error()); return 1; }
@@ -150,6 +155,7 @@ int main(int argc, char** argv) {
     memset(&opt, 0, sizeof opt);
     opt.device = -1;
     opt.proof_slots = slots;
+    opt.flags = montgomery ? CG_FLAG_SCALARS_MONTGOMERY : 0;
     cg_ctx* ctx = NULL;
     if (cg_circuit_load(&ctx, &pk, abc, l, m, M, &opt) != CG_OK) { fprintf(stderr, "cg_circuit_load: %s\n", cg_last_error()); return 1; }
     double t2 = now_s();
@@ -167,6 +173,14 @@ int main(int argc, char** argv) {
         if (!S.witness[k]) { fprintf(stderr, "witness buffer: %s\n", cg_last_error()); return 1; }
         memcpy(S.witness[k], wit, M * 32);
     }
+    double convert_ms = 0.0;
+    if (montgomery)             /* each copy on its own, in place: the best of them is the host's cost for one assignment */
+        for (int k = 0; k < S.n_witness; ++k) {
+            const double c_t0 = now_s();
+            if (cg_scalars_convert(S.witness[k], CG_FORM_CANONICAL, S.witness[k], CG_FORM_MONTGOMERY, M) != CG_OK) { fprintf(stderr, "cg_scalars_convert: %s\n", cg_last_error()); return 1; }
+            const double ms = (now_s() - c_t0) * 1e3;
+            if (k == 0 || ms < convert_ms) convert_ms = ms;
+        }
     /* the first proof re-tunes the windows of the assignment-driven MSMs: circuit loading, not proving */
     {
         uint64_t seed = 1;
@@ -190,8 +204,9 @@ int main(int argc, char** argv) {
     cg_ctx_info info;
     if (cg_ctx_get_info(ctx, &info) != CG_OK) { fprintf(stderr, "cg_ctx_get_info: %s\n", cg_last_error()); return 1; }
     printf("{\"proofs_per_s\": %.3f, \"proofs\": %ld, \"warmup\": %ld, \"proof_slots\": %d, \"caller_threads\": %d, \"witness\": \"%s host memory\", "
-           "\"host_cpus_busy\": %.2f, \"resident_GB\": %.2f, \"window_bits\": [%d, %d, %d, %d, %d], \"tuned\": %d}\n",
-           (double)proofs / (t_b - t_a), proofs, warmup, slots, callers, pageable ? "pageable" : "page-locked", (c1 - c0) / (w1 - w0),
+           "\"scalars\": \"%s\", \"host_scalars_convert_ms\": %.3f, \"host_cpus_busy\": %.2f, \"resident_GB\": %.2f, \"window_bits\": [%d, %d, %d, %d, %d], \"tuned\": %d}\n",
+           (double)proofs / (t_b - t_a), proofs, warmup, slots, callers, pageable ? "pageable" : "page-locked", montgomery ? "montgomery" : "canonical", convert_ms,
+           (c1 - c0) / (w1 - w0),
            (double)info.total_bytes / 1e9, (int)info.window_bits[0], (int)info.window_bits[1], (int)info.window_bits[2], (int)info.window_bits[3],
            (int)info.window_bits[4], (int)info.tuned);
     for (int k = 0; k < S.n_witness; ++k) { if (pageable) free(S.witness[k]); else cg_host_free(S.witness[k]); }

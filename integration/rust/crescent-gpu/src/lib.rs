@@ -6,7 +6,7 @@
 pub mod sys;
 
 use ark_bn254::{Bn254, Fq, Fq2, Fr, G1Affine, G2Affine};
-use ark_ff::{BigInteger, PrimeField};
+use ark_ff::{BigInt, BigInteger, PrimeField};
 use ark_groth16::r1cs_to_qap::{LibsnarkReduction, R1CSToQAP};
 use ark_groth16::{Proof, ProvingKey};
 use ark_poly::EvaluationDomain;
@@ -23,6 +23,23 @@ fn put_fq(out: &mut [u8], x: &Fq) {
     for (k, limb) in x.0 .0.iter().enumerate() {
         out[k * 8..k * 8 + 8].copy_from_slice(&limb.to_le_bytes());
     }
+}
+// The same for scalars: every context this crate loads carries `CG_FLAG_SCALARS_MONTGOMERY` (and `GpuReduction`'s handle
+// `CG_FORM_MONTGOMERY`), so an assignment crosses as the limbs of `Fr.0` - a copy, where `into_bigint()` was a Montgomery
+// reduction per element on one host thread - and the GPU converts.  32 bytes per element is what the library reads:
+const _: () = assert!(std::mem::size_of::<Fr>() == 32);
+fn put_fr(out: &mut [u8], x: &Fr) {
+    for (k, limb) in x.0 .0.iter().enumerate() {
+        out[k * 8..k * 8 + 8].copy_from_slice(&limb.to_le_bytes());
+    }
+}
+/// An assignment as the library takes it on this crate's contexts: `Fr.0`, limb by limb (no arithmetic).
+fn montgomery_bytes(xs: &[Fr]) -> Vec<u8> {
+    let mut out = vec![0u8; xs.len() * 32];
+    for (i, x) in xs.iter().enumerate() {
+        put_fr(&mut out[i * 32..i * 32 + 32], x);
+    }
+    out
 }
 fn put_fq2(out: &mut [u8], x: &Fq2) {
     put_fq(&mut out[..32], &x.c0);
@@ -162,7 +179,9 @@ impl GpuCircuit {
         Self::load_opt(pk, m, sys::cg_options { device, proof_slots, shard_rank, shard_count, flags, shard_span, ..Default::default() })
     }
 
-    fn load_opt(pk: &ProvingKey<Bn254>, m: &ConstraintMatrices<Fr>, opt: sys::cg_options) -> Result<Self, SynthesisError> {
+    fn load_opt(pk: &ProvingKey<Bn254>, m: &ConstraintMatrices<Fr>, mut opt: sys::cg_options) -> Result<Self, SynthesisError> {
+        // every wrapper below hands the library `Fr.0` as it lies in memory (put_fr): the context converts on the GPU
+        opt.flags |= sys::CG_FLAG_SCALARS_MONTGOMERY;
         let proof_slots = opt.proof_slots;
         let rc = unsafe { sys::cg_init(0, std::ptr::null()) };
         if rc != 0 {
@@ -210,7 +229,7 @@ impl GpuCircuit {
         if full_assignment.len() != self.num_variables {
             return Err(SynthesisError::AssignmentMissing);
         }
-        // the canonical bytes are written straight into page-locked memory from the circuit's pool: cg_prove's upload is
+        // the limbs of `Fr.0` are copied straight into page-locked memory from the circuit's pool: cg_prove's upload is
         // then one asynchronous DMA at PCIe speed that overlaps the other proofs in flight.  Should page-locking fail
         // (locked-memory limit of the host), a pageable Vec does the same job a little slower - never an error.
         let len = full_assignment.len() * 32;
@@ -224,7 +243,7 @@ impl GpuCircuit {
             }
         };
         for (i, x) in full_assignment.iter().enumerate() {
-            buf[i * 32..i * 32 + 32].copy_from_slice(&x.into_bigint().to_bytes_le()); // prover.rs:64,71,86 take the same form
+            put_fr(&mut buf[i * 32..i * 32 + 32], x); // CG_FLAG_SCALARS_MONTGOMERY: the `into_bigint` of prover.rs:64,71,86 runs on the GPU
         }
         let (rb, sb) = (r.into_bigint().to_bytes_le(), s.into_bigint().to_bytes_le());
         let mut out = [0u8; 256];
@@ -267,6 +286,7 @@ fn print_trace(tm: &sys::cg_timings) {
     line(0, "Groth16::Prover", tm.total_ms);                                               // :48
 }
 
+/// Canonical bytes (`into_bigint`): what stays canonical on every context - r, s, the showings' small vectors (pok_*, inputs, rand).
 fn canonical_bytes(xs: &[Fr]) -> Vec<u8> {
     let mut out = vec![0u8; xs.len() * 32];
     for (i, x) in xs.iter().enumerate() {
@@ -283,7 +303,7 @@ impl GpuCircuit {
         if full_assignment.len() != self.num_variables {
             return Err(SynthesisError::AssignmentMissing);
         }
-        let (w, rb) = (canonical_bytes(full_assignment), r.into_bigint().to_bytes_le());
+        let (w, rb) = (montgomery_bytes(full_assignment), r.into_bigint().to_bytes_le());
         let mut out = [0u8; 384];
         let rc = unsafe { sys::cg_prove_partial(self.ctx, w.as_ptr() as *const _, 0, rb.as_ptr(), out.as_mut_ptr(), std::ptr::null_mut()) };
         if rc != 0 { Err(map_err(rc)) } else { Ok(out) }
@@ -308,7 +328,7 @@ impl GpuCircuit {
         if full_assignment.len() != self.num_variables {
             return Err(SynthesisError::AssignmentMissing);
         }
-        let w = canonical_bytes(full_assignment);
+        let w = montgomery_bytes(full_assignment);
         let mut q = vec![0u8; unsafe { sys::cg_domain_size(self.ctx) } as usize * 32];
         let rc = unsafe { sys::cg_witness_map_coset(self.ctx, w.as_ptr() as *const _, 0, q.as_mut_ptr() as *mut _, 0) };
         if rc != 0 { Err(map_err(rc)) } else { Ok(q) }
@@ -327,7 +347,7 @@ impl GpuCircuit {
         if full_assignment.len() != self.num_variables {
             return Err(SynthesisError::AssignmentMissing);
         }
-        let (w, rb) = (canonical_bytes(full_assignment), r.into_bigint().to_bytes_le());
+        let (w, rb) = (montgomery_bytes(full_assignment), r.into_bigint().to_bytes_le());
         let mut out = [0u8; 384];
         let rc = unsafe {
             sys::cg_prove_partial_q(self.ctx, w.as_ptr() as *const _, 0, q_slice.as_ptr() as *const _, 0, rb.as_ptr(), out.as_mut_ptr(),
@@ -351,7 +371,7 @@ impl GpuCircuit {
         if full_assignment.len() != self.num_variables {
             return Err(SynthesisError::AssignmentMissing);
         }
-        let (w, rb) = (canonical_bytes(full_assignment), r.into_bigint().to_bytes_le());
+        let (w, rb) = (montgomery_bytes(full_assignment), r.into_bigint().to_bytes_le());
         let mut p: *mut sys::cg_partial = std::ptr::null_mut();
         // (the library has copied the assignment to the GPU before it returns: `w` may go)
         let rc = unsafe { sys::cg_prove_partial_q_begin(self.ctx, w.as_ptr() as *const _, 0, rb.as_ptr(), &mut p) };
@@ -425,7 +445,7 @@ impl GpuCircuit {
         if full_assignment.len() != self.num_variables {
             return Err(SynthesisError::AssignmentMissing);
         }
-        let w = canonical_bytes(full_assignment);
+        let w = montgomery_bytes(full_assignment);
         let mut rep = sys::cg_witness_report::default();
         match unsafe { sys::cg_check_witness(self.ctx, w.as_ptr() as *const _, 0, &mut rep) } {
             0 => Ok(None),
@@ -523,8 +543,9 @@ fn qap_for<F: PrimeField>(m: &ConstraintMatrices<F>) -> Result<Arc<QapHandle>, S
     let abc = [ca.view(), cb.view(), cc.view()];
     let mut ctx: *mut sys::cg_qap_ctx = std::ptr::null_mut();
     let rc = unsafe {
-        sys::cg_qap_load(&mut ctx, abc.as_ptr(), m.num_instance_variables as u64, m.num_constraints as u64,
-                         (m.num_instance_variables + m.num_witness_variables) as u64, -1)
+        // the handle takes `&[Fr]` and returns `Vec<Fr>` as they lie in memory (witness_map_from_matrices below)
+        sys::cg_qap_load_form(&mut ctx, abc.as_ptr(), m.num_instance_variables as u64, m.num_constraints as u64,
+                              (m.num_instance_variables + m.num_witness_variables) as u64, -1, sys::CG_FORM_MONTGOMERY)
     };
     if rc != 0 {
         return Err(map_err(rc));
@@ -556,11 +577,12 @@ impl R1CSToQAP for GpuReduction {
         num_constraints: usize,
         full_assignment: &[F],
     ) -> Result<Vec<F>, SynthesisError> {
-        // The library computes over BN254's scalar field only; any other field keeps the CPU path.
-        if F::MODULUS.to_bytes_le() != <Fr as PrimeField>::MODULUS.to_bytes_le() {
+        // The library computes over BN254's scalar field only; any other field keeps the CPU path.  The limbs cross the
+        // boundary as they lie in memory, so F must BE ark_bn254::Fr (same type, hence same backend and layout), not only
+        // share its modulus.
+        if std::any::TypeId::of::<F>() != std::any::TypeId::of::<Fr>() {
             return LibsnarkReduction::witness_map_from_matrices::<F, D>(matrices, num_inputs, num_constraints, full_assignment);
         }
-        // F is BN254's Fr (checked by modulus); everything crosses the boundary as canonical bytes, so no cast is needed
         let m = matrices;
         if num_inputs != m.num_instance_variables || num_constraints != m.num_constraints
             || full_assignment.len() != m.num_instance_variables + m.num_witness_variables
@@ -568,17 +590,30 @@ impl R1CSToQAP for GpuReduction {
             return Err(SynthesisError::AssignmentMissing);
         }
         let h = qap_for(m)?;
-        let mut w = Vec::with_capacity(full_assignment.len() * 32);
-        for x in full_assignment {
-            w.extend_from_slice(&x.into_bigint().to_bytes_le());
-        }
+        // SAFETY: F is Fr (TypeId above), so this is the same slice under its own name
+        let assignment: &[Fr] = unsafe { std::slice::from_raw_parts(full_assignment.as_ptr() as *const Fr, full_assignment.len()) };
+        let w = montgomery_bytes(assignment);
         let d = unsafe { sys::cg_qap_domain_size(h.0) } as usize;
         let mut out = vec![0u8; d * 32];
         let rc = unsafe { sys::cg_qap_witness_map(h.0, w.as_ptr() as *const _, 0, out.as_mut_ptr() as *mut _, 0) };
         if rc != 0 {
             return Err(map_err(rc));
         }
-        Ok(out.chunks_exact(32).map(F::from_le_bytes_mod_order).collect()) // domain_size coefficients (r1cs_to_qap.rs:212)
+        // domain_size coefficients (r1cs_to_qap.rs:212), already x·2^256 mod r and < r (the library's own results): the limbs
+        // ARE the field element, no `from_bigint` (a Montgomery product each) on the way back
+        let coeffs: Vec<Fr> = out
+            .chunks_exact(32)
+            .map(|c| {
+                let mut limbs = [0u64; 4];
+                for (k, l) in limbs.iter_mut().enumerate() {
+                    *l = u64::from_le_bytes(c[k * 8..k * 8 + 8].try_into().unwrap());
+                }
+                Fr::new_unchecked(BigInt(limbs))
+            })
+            .collect();
+        // SAFETY: F is Fr; the Vec is rebuilt from its own parts under the caller's name for the type
+        let mut coeffs = std::mem::ManuallyDrop::new(coeffs);
+        Ok(unsafe { Vec::from_raw_parts(coeffs.as_mut_ptr() as *mut F, coeffs.len(), coeffs.capacity()) })
     }
 
     fn h_query_scalars<F: PrimeField, D: EvaluationDomain<F>>(

@@ -13,6 +13,7 @@ pub const CG_FLAG_H_SCALARS_EXTERNAL: i32 = 32;
 pub const CG_FLAG_STAGED_LOAD: i32 = 64;
 pub const CG_FLAG_NO_LONE_SLOT: i32 = 128;
 pub const CG_FLAG_CHECK_WITNESS: i32 = 256;
+pub const CG_FLAG_SCALARS_MONTGOMERY: i32 = 512;
 pub const CG_ERR_POLY_DEGREE_TOO_LARGE: c_int = -5;
 pub const CG_ERR_MALFORMED_KEY: c_int = -6;
 pub const CG_ERR_UNSATISFIED: c_int = -8;
@@ -273,6 +274,16 @@ extern "C" {
         num_variables: u64,
         device: i32,
     ) -> c_int;
+    pub fn cg_qap_load_form(
+        out: *mut *mut cg_qap_ctx,
+        abc: *const cg_csr,
+        num_inputs: u64,
+        num_constraints: u64,
+        num_variables: u64,
+        device: i32,
+        scalar_form: u32,
+    ) -> c_int;
+    pub fn cg_scalars_convert(input: *const u8, in_form: u32, out: *mut u8, out_form: u32, n: u64) -> c_int;
     pub fn cg_qap_witness_map(
         ctx: *mut cg_qap_ctx,
         full_assignment: *const c_void,
