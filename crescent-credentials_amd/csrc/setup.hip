@@ -9,6 +9,7 @@
 // (generator.rs:140,162,168,174,185,194) become one fixed-base kernel over an 8-bit window table.
 #include <memory>
 
+#include "fixed_base.hpp"
 #include "msm.hpp"
 #include "ntt.hpp"
 
@@ -17,40 +18,12 @@ int translate_current_exception();
 }
 using namespace cg;
 
-// The G2 generator is parsed from its decimal strings at start-up instead of trusting hand-copied limbs.
-static Fq fq_from_decimal(const char* s) {
-    // acc = acc*10 + digit, in Montgomery form
-    Fq acc = Fq::zero();
-    Fq ten = Fq::zero();
-    ten.l[0] = 10;
-    ten = to_mont(ten);
-    for (const char* p = s; *p; ++p) {
-        Fq d = Fq::zero();
-        d.l[0] = (uint32_t)(*p - '0');
-        acc = add(mul(acc, ten), to_mont(d));
-    }
-    return acc;
-}
-static G1Affine g1_generator() {
-    Fq x = Fq::one();
-    Fq y = add(Fq::one(), Fq::one());
-    return {x, y};
-}
-static G2Affine g2_generator() {
-    return {{fq_from_decimal("10857046999023057135944570762232829481370756359578518086990519993285655852781"),
-             fq_from_decimal("11559732032986387107991004021392285783925812861821192530917403151452391805634")},
-            {fq_from_decimal("8495653923123431417604973247489272438418190587263600148770280649306958101930"),
-             fq_from_decimal("4082367875863433681332203403145435568316851327593401208105741076214120093531")}};
-}
-
-static constexpr int FB_NWIN = 32;   // 32 windows of 8 bits
-
-// table[j*256 + d] = d * 2^(8j) * gen
+// table[j*FB_WIN + d] = d * 2^(8j) * gen: one base's table in fixed_base.hpp's layout, built on the device
 template <class F>
-__global__ void __launch_bounds__(256) k_fb_table(Affine<F> gen, Affine<F>* __restrict__ table) {
+__global__ void __launch_bounds__(FB_WIN) k_fb_table(Affine<F> gen, Affine<F>* __restrict__ table) {
     uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= FB_NWIN * 256) return;
-    uint32_t j = t >> 8, d = t & 255u;
+    if (t >= FB_NWIN * FB_WIN) return;
+    uint32_t j = t / FB_WIN, d = t % FB_WIN;
     if (d == 0) {
         table[t] = Affine<F>::inf();
         return;
@@ -82,15 +55,7 @@ __global__ void __launch_bounds__(256) k_fixed_base(const Affine<F>* __restrict_
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fr s = from_mont(scalars[i]);
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (int j = 0; j < FB_NWIN; ++j) {
-        uint32_t d = 0;   // byte j of the scalar, selected without a dynamic register index
-#pragma unroll
-        for (int w = 0; w < 8; ++w) d = ((j >> 2) == w) ? s.l[w] : d;
-        d = (d >> ((j & 3) * 8)) & 255u;
-        if (d) madd(acc, table[j * 256 + d]);
-    }
-    Affine<F> p = to_affine(acc);
+    Affine<F> p = to_affine(fixed_base_mul(table, s.l));
     CoordsOf<F>::to_canonical(p);
     out[i] = p;
 }
@@ -185,11 +150,11 @@ extern "C" int cg_setup(const cg_csr abc[3], uint64_t num_inputs, uint64_t num_c
         DevBuf<Fr> hs(D);
         fr_pow_table(hs.p, tau, mul(zt, dinv), D - 1, false, 0, st);
         // fixed-base tables
-        DevBuf<G1Affine> t1(FB_NWIN * 256);
-        DevBuf<G2Affine> t2(FB_NWIN * 256);
-        k_fb_table<Fq><<<FB_NWIN, 256, 0, st>>>(g1_generator(), t1.p);
+        DevBuf<G1Affine> t1(FB_NWIN * FB_WIN);
+        DevBuf<G2Affine> t2(FB_NWIN * FB_WIN);
+        k_fb_table<Fq><<<FB_NWIN, FB_WIN, 0, st>>>(g1_generator(), t1.p);
         CG_KERNEL_CHECK();
-        k_fb_table<Fq2><<<FB_NWIN, 256, 0, st>>>(g2_generator(), t2.p);
+        k_fb_table<Fq2><<<FB_NWIN, FB_WIN, 0, st>>>(g2_generator(), t2.p);
         CG_KERNEL_CHECK();
         fixed_base_to_host<Fq>(t1.p, qa.p, M, a_query, st);               // generator.rs:162
         fixed_base_to_host<Fq>(t1.p, qb.p, M, b_g1_query, st);            // :168
@@ -229,8 +194,8 @@ static int fixed_base_export(const Affine<F>& gen, const uint8_t* scalars, uint6
         }
         DevBuf<Fr> sc(n);
         CG_HIP(hipMemcpyAsync(sc.p, host.data(), n * sizeof(Fr), hipMemcpyHostToDevice, st));
-        DevBuf<Affine<F>> table(FB_NWIN * 256);
-        k_fb_table<F><<<FB_NWIN, 256, 0, st>>>(gen, table.p);
+        DevBuf<Affine<F>> table(FB_NWIN * FB_WIN);
+        k_fb_table<F><<<FB_NWIN, FB_WIN, 0, st>>>(gen, table.p);
         CG_KERNEL_CHECK();
         fixed_base_to_host<F>(table.p, sc.p, n, out, st);
         return CG_OK;

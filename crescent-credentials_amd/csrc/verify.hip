@@ -4,7 +4,8 @@
 //
 // A cg_pvk holds one parsed key on a device: alpha_g1_beta_g2, the 91 line coefficients of gamma_g2_neg_pc and of
 // delta_g2_neg_pc, gamma_abc_g1[0] and, for every other gamma_abc_g1 entry, a fixed-base table of 32 windows x 256
-// multiples (8-bit windows: x_i·G_i is 32 mixed additions).  cg_verify_batch runs four kernels per chunk of proofs on the
+// multiples (8-bit windows: x_i·G_i is 32 mixed additions; fixed_base.hpp has the geometry, build_tables and the walk,
+// fixed_base_mul, that every fixed-base lane below takes).  cg_verify_batch runs four kernels per chunk of proofs on the
 // handle's own non-blocking stream:
 //   k_vfy_inputs  one lane per (proof, input): x_i·gamma_abc[i+1] from the table                      -> XYZZ partials
 //   k_vfy_check   one lane per proof: ark's checked deserialisation of A, B, C (coordinates < q, flags, curve, [r]B = O)
@@ -37,9 +38,14 @@
 //   k_mk_out      one lane per (state, output point): A', B', C'' = C + r2·A - (Σ r_i + z)·G, com_hidden, the committed
 //                 points and the k_i of DLogPoK::prove (creds/src/dlog.rs:60-75), affine, as ark-serialize writes them
 // cg_show_respond_batch, the responses once the host's transcript has produced c, is host arithmetic.
+//
+// Shared by the three entries: the double-and-add chains are fixed_base.hpp's scalar_mul_254_mixed; the section "ark-serialize
+// points" below reads and writes every point on the device; io_layout parses a call's io_types once, for the verifier's and
+// the creator's shapes alike; and the handle has one set of per-call buffers, named by what they hold.
 #include <memory>
 
 #include "common.hpp"
+#include "fixed_base.hpp"
 #include "pairing.hpp"
 
 namespace cg {
@@ -49,9 +55,6 @@ using namespace cg;
 
 namespace {
 
-constexpr int VWIN_BITS = 8;
-constexpr int VWIN = 1 << VWIN_BITS;       // entries per window (entry 0 = O)
-constexpr int NWIN = 256 / VWIN_BITS;      // windows per 256-bit scalar
 constexpr uint64_t VCHUNK = 1u << 15;      // proofs per launch set
 constexpr int VBLOCK = 64;
 constexpr int NC = PairingConsts::N_COEFFS;
@@ -123,13 +126,6 @@ struct KeyRd {
     }
 };
 
-// the G2 generator, canonical limbs x.c0, x.c1, y.c0, y.c1 (ark-bn254 g2.rs; zkey.rs:442-460)
-constexpr uint32_t G2_GEN[4][8] = {
-    {0xd992f6edu, 0x46debd5cu, 0xf75edaddu, 0x674322d4u, 0x5e5c4479u, 0x426a0066u, 0x121f1e76u, 0x1800deefu},
-    {0xaef312c2u, 0x97e485b7u, 0x35a9e712u, 0xf1aa4933u, 0x31fb5d25u, 0x7260bfb7u, 0x920d483au, 0x198e9393u},
-    {0x66fa7daau, 0x4ce6cc01u, 0x0c43d37bu, 0xe3d1e769u, 0x8dcb408fu, 0x4aab7180u, 0xdb8c6debu, 0x12c85ea5u},
-    {0xd122975bu, 0x55acdadcu, 0x70b38ef3u, 0xbc4b3133u, 0x690c3395u, 0xec9e99adu, 0x585ff075u, 0x090689d0u}};
-
 struct HostVk {
     G1Affine alpha_g1, delta_g1;
     G2Affine beta_g2, gamma_g2, delta_g2;
@@ -178,47 +174,7 @@ static void parse_pvk(const uint8_t* data, uint64_t len, HostPvk& k) {   // data
     if (r.off != len) throw HipError(CG_ERR_PARSE, "trailing bytes after PreparedVerifyingKey");
 }
 
-// fixed-base tables of gabc[1..]: tab[(i·NWIN + w)·VWIN + d] = d·2^(8w)·gabc[i+1], affine (one batch inversion).  The key
-// passes gamma_abc_g1 followed by delta_g1 and the G1 generator, so table n_inputs is delta_g1's and table n_inputs + 1 the
-// generator's; over Fq2 the same walk makes the one table of delta_g2.
-template <class F>
-static void build_tables(const std::vector<Affine<F>>& gabc, std::vector<Affine<F>>& tab) {
-    const uint64_t ell = gabc.size() - 1;
-    const uint64_t total = ell * NWIN * VWIN;
-    std::vector<XYZZ<F>> pts(total);
-    for (uint64_t i = 0; i < ell; ++i) {
-        XYZZ<F> step = XYZZ<F>::from_affine(gabc[i + 1]);
-        for (int w = 0; w < NWIN; ++w) {
-            XYZZ<F>* row = &pts[(i * NWIN + w) * VWIN];
-            row[0] = XYZZ<F>::inf();
-            for (int d = 1; d < VWIN; ++d) {
-                row[d] = row[d - 1];
-                add(row[d], step);
-            }
-            XYZZ<F> next = row[VWIN - 1];
-            add(next, step);
-            step = next;
-        }
-    }
-    // batch affine: t_j = zz_j·zzz_j, one inversion of their product
-    std::vector<F> pref(total);
-    F acc = F::one();
-    for (uint64_t j = 0; j < total; ++j) {
-        pref[j] = acc;
-        if (!pts[j].is_inf()) acc = mul(acc, mul(pts[j].zz, pts[j].zzz));
-    }
-    F ia = inv(acc);
-    tab.resize(total);
-    for (uint64_t j = total; j-- > 0;) {
-        if (pts[j].is_inf()) { tab[j] = Affine<F>::inf(); continue; }
-        const F t = mul(pts[j].zz, pts[j].zzz);
-        const F it = mul(ia, pref[j]);          // 1 / t_j
-        ia = mul(ia, t);
-        tab[j] = {mul(pts[j].x, mul(it, pts[j].zzz)), mul(pts[j].y, mul(it, pts[j].zz))};
-    }
-}
-
-// ---- device side ----------------------------------------------------------------------------------------------------
+// ---- device side: ark-serialize points, read (checked, or unchecked for the chains) and written ---------------------------
 __device__ __forceinline__ bool limbs_below(const uint32_t a[8], const uint32_t n[8]) {
     for (int i = 7; i >= 0; --i) {
         if (a[i] < n[i]) return true;
@@ -265,19 +221,66 @@ __device__ __forceinline__ G2Affine dev_g2(const uint32_t* w, bool& ok) {
     return p;
 }
 
+// the same points as the chains use them: no checks (k_show_check / k_mk_check make them, and an item that fails them has
+// its output zeroed), flags stripped
+__device__ __forceinline__ G1Affine dev_g1_unchecked(const uint32_t* w) {
+    if ((w[15] >> 30) == 1u) return G1Affine::inf();
+    bool ignored = true;
+    G1Affine p;
+    p.x = dev_fq(w, ignored);
+    p.y = dev_fq(w + 8, ignored, 0xC0000000u);
+    return p;
+}
+__device__ __forceinline__ G2Affine dev_g2_unchecked(const uint32_t* w) {
+    if ((w[31] >> 30) == 1u) return G2Affine::inf();
+    bool ignored = true;
+    G2Affine p;
+    p.x.c0 = dev_fq(w, ignored);
+    p.x.c1 = dev_fq(w + 8, ignored);
+    p.y.c0 = dev_fq(w + 16, ignored);
+    p.y.c1 = dev_fq(w + 24, ignored, 0xC0000000u);
+    return p;
+}
+// ark-serialize of an affine G1 point: uncompressed (16 words) or compressed (8 words), SWFlags in the top bits
+__device__ __forceinline__ void dev_put_g1(const G1Affine& a, uint32_t* out, bool compressed) {
+    Fq x = Fq::zero(), y = Fq::zero();
+    uint32_t flags = 0x40000000u;                                 // SWFlags::PointAtInfinity
+    if (!a.is_inf()) {
+        x = from_mont(a.x);
+        y = from_mont(a.y);
+        const Fq ny = from_mont(neg(a.y));
+        flags = limbs_below(ny.l, y.l) ? 0x80000000u : 0u;        // SWFlags::YIsNegative: y > -y
+    }
+    (compressed ? x : y).l[7] |= flags;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) out[l] = x.l[l];
+    if (!compressed) {
+#pragma unroll
+        for (int l = 0; l < 8; ++l) out[8 + l] = y.l[l];
+    }
+}
+__device__ __forceinline__ void dev_put_g2(const G2Affine& a, uint32_t* out) {
+    if (a.is_inf()) {
+        for (int l = 0; l < 32; ++l) out[l] = l == 31 ? 0x40000000u : 0u;
+        return;
+    }
+    const Fq2 ny = neg(a.y);
+    const Fq c[4] = {from_mont(a.x.c0), from_mont(a.x.c1), from_mont(a.y.c0), from_mont(a.y.c1)};
+    const Fq n0 = from_mont(ny.c0), n1 = from_mont(ny.c1);
+    for (int j = 0; j < 4; ++j)
+        for (int l = 0; l < 8; ++l) out[8 * j + l] = c[j].l[l];
+    // QuadExtField's ordering compares c1 first, then c0
+    const bool larger = c[3] == n1 ? limbs_below(n0.l, c[2].l) : limbs_below(n1.l, c[3].l);
+    if (larger) out[31] |= 0x80000000u;
+}
+
 __global__ __launch_bounds__(VBLOCK) void k_vfy_inputs(const uint32_t* __restrict__ inputs, uint64_t n, uint32_t ell,
                                                       const G1Affine* __restrict__ tab, G1XYZZ* __restrict__ part) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n * ell) return;
     const uint32_t i = (uint32_t)(t % ell);
     const uint32_t* x = inputs + 8 * t;
-    const G1Affine* tb = tab + (uint64_t)i * NWIN * VWIN;
-    G1XYZZ acc = G1XYZZ::inf();
-    for (int w = 0; w < NWIN; ++w) {
-        const uint32_t d = (x[w >> 2] >> (8 * (w & 3))) & 0xFFu;
-        if (d) madd(acc, tb[w * VWIN + d]);
-    }
-    part[t] = acc;
+    part[t] = fixed_base_mul(tab + (uint64_t)i * FB_NWIN * FB_WIN, x);
 }
 
 __global__ __launch_bounds__(VBLOCK) void k_vfy_check(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ inputs,
@@ -336,17 +339,6 @@ struct ShowShape {
     uint32_t n_terms;                  // n_fixed + n_var
 };
 
-// an uncompressed G1 point as the variable-base lanes use it: no checks (k_show_check makes them, and a showing that fails
-// them has its k bytes zeroed), flags stripped
-__device__ __forceinline__ G1Affine dev_g1_unchecked(const uint32_t* w) {
-    if ((w[15] >> 30) == 1u) return G1Affine::inf();
-    bool ignored = true;
-    G1Affine p;
-    p.x = dev_fq(w, ignored);
-    p.y = dev_fq(w + 8, ignored, 0xC0000000u);
-    return p;
-}
-
 __global__ __launch_bounds__(VBLOCK) void k_show_terms(const uint32_t* __restrict__ revealed, const uint32_t* __restrict__ pok_s,
                                                       const uint32_t* __restrict__ pok_c, const uint32_t* __restrict__ com_hidden,
                                                       const uint32_t* __restrict__ committed, uint64_t n, ShowShape sh,
@@ -358,13 +350,7 @@ __global__ __launch_bounds__(VBLOCK) void k_show_terms(const uint32_t* __restric
         const uint64_t p = g / sh.n_fixed;
         const uint32_t t = (uint32_t)(g % sh.n_fixed);
         const uint32_t* x = t < sh.n_rev ? revealed + 8 * (p * sh.n_rev + t) : pok_s + 8 * (p * sh.n_resp + (t - sh.n_rev));
-        const G1Affine* tb = tab + (uint64_t)tab_of[t] * NWIN * VWIN;
-        G1XYZZ acc = G1XYZZ::inf();
-        for (int w = 0; w < NWIN; ++w) {
-            const uint32_t d = (x[w >> 2] >> (8 * (w & 3))) & 0xFFu;
-            if (d) madd(acc, tb[w * VWIN + d]);
-        }
-        part[p * sh.n_terms + t] = acc;
+        part[p * sh.n_terms + t] = fixed_base_mul(tab + (uint64_t)tab_of[t] * FB_NWIN * FB_WIN, x);
         return;
     }
     // the variable-base lanes (a chain ~10x as long) start at a workgroup of their own
@@ -374,17 +360,8 @@ __global__ __launch_bounds__(VBLOCK) void k_show_terms(const uint32_t* __restric
     const uint64_t p = v / sh.n_var;
     const uint32_t i = (uint32_t)(v % sh.n_var);
     const G1Affine y = dev_g1_unchecked(i < sh.n_com ? committed + 16 * (p * sh.n_com + i) : com_hidden + 16 * p);
-    const uint32_t* c = pok_c + 8 * p;
-    // c < r < 2^254 (a challenge is 248 bits, dlog.rs:97-99); the doublings before the first set bit return at once
-    G1XYZZ acc = G1XYZZ::inf();
-    for (int wi = 7; wi >= 0; --wi) {
-        const uint32_t cw = c[wi];
-        for (int b = wi == 7 ? 29 : 31; b >= 0; --b) {
-            acc = dbl(acc);
-            if ((cw >> b) & 1u) madd(acc, y);
-        }
-    }
-    part[p * sh.n_terms + sh.n_fixed + i] = acc;
+    // c < r < 2^254 (a challenge is 248 bits, dlog.rs:97-99)
+    part[p * sh.n_terms + sh.n_fixed + i] = scalar_mul_254_mixed(y, pok_c + 8 * p);
 }
 
 __global__ __launch_bounds__(VBLOCK) void k_show_check(const uint32_t* __restrict__ revealed, const uint32_t* __restrict__ pok_s,
@@ -416,26 +393,18 @@ __global__ __launch_bounds__(VBLOCK) void k_show_k(uint64_t n, ShowShape sh, con
     if (g >= n * sh.n_var) return;
     const uint64_t p = g / sh.n_var;
     const uint32_t i = (uint32_t)(g % sh.n_var);
-    uint32_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (status[p] == ST_OK) {
-        // statement i < n_com: (gamma_abc[.], delta_g1); the last one: the hidden inputs' bases, then delta_g1
-        const uint32_t lo = i < sh.n_com ? 2 * i : 2 * sh.n_com;
-        const uint32_t hi = i < sh.n_com ? 2 * i + 2 : sh.n_resp;
-        const G1XYZZ* pt = part + p * sh.n_terms;
-        G1XYZZ acc = pt[sh.n_fixed + i];
-        for (uint32_t j = lo; j < hi; ++j) add(acc, pt[sh.n_rev + j]);
-        const G1Affine a = to_affine(acc);
-        if (a.is_inf()) {
-            o[7] = 0x40000000u;                                   // SWFlags::PointAtInfinity
-        } else {
-            const Fq x = from_mont(a.x), y = from_mont(a.y), ny = from_mont(neg(a.y));
-#pragma unroll
-            for (int l = 0; l < 8; ++l) o[l] = x.l[l];
-            if (limbs_below(ny.l, y.l)) o[7] |= 0x80000000u;      // SWFlags::YIsNegative: y > -y
-        }
+    uint32_t* out = k_out + 8 * g;
+    if (status[p] != ST_OK) {
+        for (int l = 0; l < 8; ++l) out[l] = 0;
+        return;
     }
-#pragma unroll
-    for (int l = 0; l < 8; ++l) k_out[8 * g + l] = o[l];
+    // statement i < n_com: (gamma_abc[.], delta_g1); the last one: the hidden inputs' bases, then delta_g1
+    const uint32_t lo = i < sh.n_com ? 2 * i : 2 * sh.n_com;
+    const uint32_t hi = i < sh.n_com ? 2 * i + 2 : sh.n_resp;
+    const G1XYZZ* pt = part + p * sh.n_terms;
+    G1XYZZ acc = pt[sh.n_fixed + i];
+    for (uint32_t j = lo; j < hi; ++j) add(acc, pt[sh.n_rev + j]);
+    dev_put_g1(to_affine(acc), out, true);
 }
 
 // ---- creating showings (ClientState::show_groth16, groth16rand.rs:100-187) ---------------------------------------------
@@ -452,36 +421,12 @@ struct MkShape {
 };
 constexpr uint32_t MK_RAND = 0x80000000u;
 
-__device__ __forceinline__ G2Affine dev_g2_unchecked(const uint32_t* w) {
-    if ((w[31] >> 30) == 1u) return G2Affine::inf();
-    bool ignored = true;
-    G2Affine p;
-    p.x.c0 = dev_fq(w, ignored);
-    p.x.c1 = dev_fq(w + 8, ignored);
-    p.y.c0 = dev_fq(w + 16, ignored);
-    p.y.c1 = dev_fq(w + 24, ignored, 0xC0000000u);
-    return p;
-}
 __device__ __forceinline__ Fr dev_fr(const uint32_t* w) {
     Fr a;
 #pragma unroll
     for (int i = 0; i < 8; ++i) a.l[i] = w[i];
     return a;
 }
-// k·y for a canonical k < r < 2^254, as k_show_terms' variable-base lanes walk it
-template <class F>
-__device__ __forceinline__ XYZZ<F> dev_mul_254(const Affine<F>& y, const uint32_t k[8]) {
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (int wi = 7; wi >= 0; --wi) {
-        const uint32_t kw = k[wi];
-        for (int b = wi == 7 ? 29 : 31; b >= 0; --b) {
-            acc = dbl(acc);
-            if ((kw >> b) & 1u) madd(acc, y);
-        }
-    }
-    return acc;
-}
-
 __global__ __launch_bounds__(VBLOCK) void k_mk_fixed(const uint32_t* __restrict__ inputs, const uint32_t* __restrict__ rand, uint64_t n,
                                                     MkShape sh, const uint32_t* __restrict__ desc, const G1Affine* __restrict__ tab,
                                                     G1XYZZ* __restrict__ part) {
@@ -498,13 +443,7 @@ __global__ __launch_bounds__(VBLOCK) void k_mk_fixed(const uint32_t* __restrict_
         const uint32_t src = desc[sh.n_fix + t];
         x = dev_fr(src & MK_RAND ? rd + 8 * (src & ~MK_RAND) : inputs + 8 * (p * sh.n_io + src));
     }
-    const G1Affine* tb = tab + (uint64_t)desc[t] * NWIN * VWIN;
-    G1XYZZ acc = G1XYZZ::inf();
-    for (int w = 0; w < NWIN; ++w) {
-        const uint32_t d = (x.l[w >> 2] >> (8 * (w & 3))) & 0xFFu;
-        if (d) madd(acc, tb[w * VWIN + d]);
-    }
-    part[p * sh.n_terms + t] = acc;
+    part[p * sh.n_terms + t] = fixed_base_mul(tab + (uint64_t)desc[t] * FB_NWIN * FB_WIN, x.l);
 }
 
 // the chains of rerandomize_proof (prover.rs:239-253): lanes [0, n) r1^-1·A, lanes [n, 2n) r2·A, and from a workgroup of
@@ -520,20 +459,15 @@ __global__ __launch_bounds__(VBLOCK) void k_mk_var(const uint32_t* __restrict__ 
         const G1Affine a = dev_g1_unchecked(proofs + 64 * p);
         Fr k = dev_fr(rand + 8 * (p * sh.n_rand + which));
         if (!which) k = from_mont(inv(to_mont(k)));               // r1 = 0 stays 0; that showing is malformed
-        part[p * sh.n_terms + sh.n_fix + which] = dev_mul_254(a, k.l);
+        part[p * sh.n_terms + sh.n_fix + which] = scalar_mul_254_mixed(a, k.l);
         return;
     }
     const uint64_t g2_at = (2 * n + VBLOCK - 1) / VBLOCK * VBLOCK;
     if (g < g2_at || g - g2_at >= n) return;
     const uint64_t p = g - g2_at;
-    const uint32_t* r2 = rand + 8 * (p * sh.n_rand + 1);
-    G2XYZZ acc = G2XYZZ::inf();
-    for (int w = 0; w < NWIN; ++w) {
-        const uint32_t d = (r2[w >> 2] >> (8 * (w & 3))) & 0xFFu;
-        if (d) madd(acc, tab_g2[w * VWIN + d]);
-    }
+    G2XYZZ acc = fixed_base_mul(tab_g2, rand + 8 * (p * sh.n_rand + 1));         // r2·delta_g2
     madd(acc, dev_g2_unchecked(proofs + 64 * p + 16));
-    part_g2[p] = dev_mul_254(to_affine(acc), rand + 8 * p * sh.n_rand);
+    part_g2[p] = scalar_mul_254_mixed(to_affine(acc), rand + 8 * p * sh.n_rand);
 }
 
 // one lane per showing: the checks of dev_g1 / dev_g2 on the proof without [r]B = O (a client state is the host's own
@@ -556,39 +490,6 @@ __global__ __launch_bounds__(VBLOCK) void k_mk_check(const uint32_t* __restrict_
     for (uint32_t j = 0; j < sh.n_rand; ++j) ok = ok && limbs_below(rd + 8 * j, FrP::N);
     ok = ok && !dev_fr(rd).is_zero() && !dev_fr(rd + 8).is_zero();          // the reference redraws these (prover.rs:234-237)
     status[p] = ok ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
-}
-
-// ark-serialize of an affine G1 point: uncompressed (16 words) or compressed (8 words), SWFlags in the top bits
-__device__ __forceinline__ void dev_put_g1(const G1Affine& a, uint32_t* out, bool compressed) {
-    Fq x = Fq::zero(), y = Fq::zero();
-    uint32_t flags = 0x40000000u;                                 // SWFlags::PointAtInfinity
-    if (!a.is_inf()) {
-        x = from_mont(a.x);
-        y = from_mont(a.y);
-        const Fq ny = from_mont(neg(a.y));
-        flags = limbs_below(ny.l, y.l) ? 0x80000000u : 0u;        // SWFlags::YIsNegative: y > -y
-    }
-    (compressed ? x : y).l[7] |= flags;
-#pragma unroll
-    for (int l = 0; l < 8; ++l) out[l] = x.l[l];
-    if (!compressed) {
-#pragma unroll
-        for (int l = 0; l < 8; ++l) out[8 + l] = y.l[l];
-    }
-}
-__device__ __forceinline__ void dev_put_g2(const G2Affine& a, uint32_t* out) {
-    if (a.is_inf()) {
-        for (int l = 0; l < 32; ++l) out[l] = l == 31 ? 0x40000000u : 0u;
-        return;
-    }
-    const Fq2 ny = neg(a.y);
-    const Fq c[4] = {from_mont(a.x.c0), from_mont(a.x.c1), from_mont(a.y.c0), from_mont(a.y.c1)};
-    const Fq n0 = from_mont(ny.c0), n1 = from_mont(ny.c1);
-    for (int j = 0; j < 4; ++j)
-        for (int l = 0; l < 8; ++l) out[8 * j + l] = c[j].l[l];
-    // QuadExtField's ordering compares c1 first, then c0
-    const bool larger = c[3] == n1 ? limbs_below(n0.l, c[2].l) : limbs_below(n1.l, c[3].l);
-    if (larger) out[31] |= 0x80000000u;
 }
 
 // one lane per (showing, output point): the partials summed with the general `add` (two of them coincide or cancel for
@@ -658,25 +559,39 @@ struct cg_pvk {
     G1Affine g0;
     Fq12 alpha_beta;
     int gamma_live = 0, delta_live = 0;
-    DevBuf<G1Affine> tab;
+    bool gamma_is_one = false;             // gamma_g2 is the G2 generator: what cg_show_commit_batch's correction of C assumes
+    DevBuf<G1Affine> tab;                  // gamma_abc_g1[1..], delta_g1, the G1 generator
+    DevBuf<G2Affine> tab_g2;               // delta_g2
     DevBuf<EllCoeff> gamma_c, delta_c;
-    // per-call buffers, grown to the largest chunk seen
-    uint64_t cap = 0;
-    DevBuf<uint8_t> d_inputs, d_proofs, d_status, d_verdict;
-    DevBuf<G1XYZZ> d_part;
-    DevBuf<ParsedProof> d_parsed;
-    DevBuf<Fq12> d_f;
-    // cg_verify_show_batch's own: grown one by one, since their sizes follow the call's layout
-    DevBuf<uint8_t> s_rev, s_comh, s_comm, s_c, s_s, s_k;
-    DevBuf<uint32_t> s_tab_of;
-    // cg_show_commit_batch's own: the table of delta_g2, whether gamma_g2 is the generator, and its per-call buffers
-    bool gamma_is_one = false;
-    DevBuf<G2Affine> tab_g2;
-    DevBuf<uint8_t> m_rand, m_rproofs, m_comh, m_comm, m_k;
-    DevBuf<G2XYZZ> m_part_g2;
-    DevBuf<uint32_t> m_desc;
+    // per-call buffers, named by what they hold and shared by the three entries: each is grown, never shrunk, to the largest
+    // chunk and layout seen.  Bytes are ark-serialize's, as the caller passes and receives them.
+    DevBuf<uint8_t> b_proofs;              // proofs in: 256 B per item
+    DevBuf<uint8_t> b_inputs;              // scalars per (item, input): public inputs, revealed inputs, a client state's inputs
+    DevBuf<uint8_t> b_rows;                // scalars per (item, row): the responses of a showing, or a client state's rand
+    DevBuf<uint8_t> b_chal;                // the challenge c per item
+    DevBuf<uint8_t> b_comh, b_comm, b_k;   // com_hidden, the committed points and the k points per item, read or written
+    DevBuf<uint8_t> b_rproofs;             // re-randomised proofs out
+    DevBuf<uint8_t> b_status, b_verdict;
+    DevBuf<G1XYZZ> b_part;
+    DevBuf<G2XYZZ> b_part_g2;
+    DevBuf<ParsedProof> b_parsed;
+    DevBuf<Fq12> b_miller;
+    DevBuf<uint32_t> b_desc;               // the call's term descriptor: tab_of of k_show_terms, desc of k_mk_*
     ~cg_pvk() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
 };
+
+template <class T>
+static void grow(DevBuf<T>& b, uint64_t count) {
+    if (b.n < count) b.alloc(count);
+}
+// rows [off, off + m) of a caller's array, `stride` bytes each, to the start of a device buffer and back, on the handle's
+// stream; nothing for an array the layout leaves empty (stride 0) or the caller may leave out (null)
+static void rows_up(cg_pvk* k, DevBuf<uint8_t>& d, const uint8_t* h, uint64_t off, uint64_t m, uint64_t stride) {
+    if (h && stride) CG_HIP(hipMemcpyAsync(d.p, h + off * stride, m * stride, hipMemcpyHostToDevice, k->st));
+}
+static void rows_down(cg_pvk* k, uint8_t* h, const DevBuf<uint8_t>& d, uint64_t off, uint64_t m, uint64_t stride) {
+    if (h && stride) CG_HIP(hipMemcpyAsync(h + off * stride, d.p, m * stride, hipMemcpyDeviceToHost, k->st));
+}
 
 extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len, int32_t device) {
     if (!out || !pvk_bytes) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
@@ -685,14 +600,15 @@ extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len,
         HostPvk hk;
         parse_pvk(pvk_bytes, len, hk);           // host only: a parse error is reported before any HIP call
         if (hk.vk.gamma_abc.empty()) return fail(CG_ERR_MALFORMED_KEY, "gamma_abc_g1 is empty");
+        // the tables: build_tables skips gamma_abc[0], so table i is gamma_abc[i+1]'s, table n_inputs delta_g1's and table
+        // n_inputs + 1 the generator's
         std::vector<G1Affine> bases = hk.vk.gamma_abc, tab;
         bases.push_back(hk.vk.delta_g1);            // the Pedersen / DLogPoK base of a showing (groth16rand.rs:133, :274)
-        bases.push_back({Fq::one(), dbl(Fq::one())});   // G = (1, 2): the correction of C in a showing (groth16rand.rs:167)
+        bases.push_back(g1_generator());            // G: the correction of C in a showing (groth16rand.rs:167)
         build_tables(bases, tab);
         std::vector<G2Affine> tab_g2;                   // r2·delta_g2 of rerandomize_proof (prover.rs:247)
         build_tables(std::vector<G2Affine>{G2Affine::inf(), hk.vk.delta_g2}, tab_g2);
-        const G2Affine g2_gen = {{to_mont(fq_const(G2_GEN[0])), to_mont(fq_const(G2_GEN[1]))},
-                                 {to_mont(fq_const(G2_GEN[2])), to_mont(fq_const(G2_GEN[3]))}};
+        const G2Affine g2_gen = g2_generator();
         int dev = device;
         if (dev < 0) CG_HIP(hipGetDevice(&dev));
         CG_HIP(hipSetDevice(dev));
@@ -739,35 +655,32 @@ extern "C" int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inpu
         CG_HIP(hipSetDevice(k->device));
         const uint64_t ell = n_inputs;
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
-        if (chunk > k->cap) {
-            k->d_inputs.alloc(chunk * ell * 32 + 32);
-            k->d_proofs.alloc(chunk * 256);
-            k->d_status.alloc(chunk);
-            k->d_verdict.alloc(chunk);
-            k->d_part.alloc(chunk * ell + 1);
-            k->d_parsed.alloc(chunk);
-            k->d_f.alloc(chunk);
-            k->cap = chunk;
-        }
+        grow(k->b_inputs, chunk * ell * 32 + 32);
+        grow(k->b_proofs, chunk * 256);
+        grow(k->b_status, chunk);
+        grow(k->b_verdict, chunk);
+        grow(k->b_part, chunk * ell + 1);
+        grow(k->b_parsed, chunk);
+        grow(k->b_miller, chunk);
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            if (ell) CG_HIP(hipMemcpyAsync(k->d_inputs.p, inputs + off * ell * 32, m * ell * 32, hipMemcpyHostToDevice, k->st));
-            CG_HIP(hipMemcpyAsync(k->d_proofs.p, proofs + off * 256, m * 256, hipMemcpyHostToDevice, k->st));
+            rows_up(k, k->b_inputs, inputs, off, m, ell * 32);
+            rows_up(k, k->b_proofs, proofs, off, m, 256);
             if (ell) {
-                k_vfy_inputs<<<ceil_div(m * ell, VBLOCK), VBLOCK, 0, k->st>>>((const uint32_t*)k->d_inputs.p, m, (uint32_t)ell,
-                                                                             k->tab.p, k->d_part.p);
+                k_vfy_inputs<<<ceil_div(m * ell, VBLOCK), VBLOCK, 0, k->st>>>((const uint32_t*)k->b_inputs.p, m, (uint32_t)ell,
+                                                                             k->tab.p, k->b_part.p);
                 CG_KERNEL_CHECK();
             }
             const uint32_t grid = ceil_div(m, VBLOCK);
-            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->d_proofs.p, (const uint32_t*)k->d_inputs.p, m, (uint32_t)ell,
-                                                    k->d_part.p, k->g0, k->d_parsed.p, k->d_status.p);
+            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->b_proofs.p, (const uint32_t*)k->b_inputs.p, m, (uint32_t)ell,
+                                                    k->b_part.p, k->g0, k->b_parsed.p, k->b_status.p);
             CG_KERNEL_CHECK();
-            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->d_parsed.p, k->d_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
-                                                     k->delta_live, k->d_f.p);
+            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
+                                                     k->delta_live, k->b_miller.p);
             CG_KERNEL_CHECK();
-            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->d_f.p, k->d_status.p, m, k->alpha_beta, k->d_verdict.p);
+            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.p, m, k->alpha_beta, k->b_verdict.p);
             CG_KERNEL_CHECK();
-            CG_HIP(hipMemcpyAsync(verdicts + off, k->d_verdict.p, m, hipMemcpyDeviceToHost, k->st));
+            rows_down(k, verdicts, k->b_verdict, off, m, 1);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -776,102 +689,151 @@ extern "C" int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inpu
     }
 }
 
-template <class T>
-static void grow(DevBuf<T>& b, uint64_t count) {
-    if (b.n < count) b.alloc(count);
+// ---- one call's io_types layout, shared by the verifier and the creator of showings -------------------------------------
+namespace {
+struct IoLayout {
+    std::vector<uint32_t> rev, com, hid;     // the inputs of each PublicIOType, ascending
+    // the table each DLogPoK response walks, in the order dlog.rs:60-67 and :135-145 meet the bases: (gamma_abc[i+1], delta_g1)
+    // per committed input, then the hidden inputs, then delta_g1 (table n_io is delta_g1's)
+    std::vector<uint32_t> resp_tab;
+};
+// 0, or the failure already recorded.  This is the part that needs no key (cg_show_rand_count, cg_show_respond_batch).
+int io_layout(const uint8_t* io_types, uint64_t n_io, IoLayout& L) {
+    if (n_io && !io_types) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_io >= MK_RAND / 4) return fail(CG_ERR_INVALID_ARGUMENT, "too many io types");
+    for (uint64_t i = 0; i < n_io; ++i) {
+        switch (io_types[i]) {
+            case CG_IO_REVEALED: L.rev.push_back((uint32_t)i); break;
+            case CG_IO_HIDDEN: L.hid.push_back((uint32_t)i); break;
+            case CG_IO_COMMITTED: L.com.push_back((uint32_t)i); break;
+            default: return fail(CG_ERR_INVALID_ARGUMENT, "io_types[%llu] = %u is no PublicIOType", (unsigned long long)i, io_types[i]);
+        }
+    }
+    for (uint32_t i : L.com) {
+        L.resp_tab.push_back(i);
+        L.resp_tab.push_back((uint32_t)n_io);
+    }
+    L.resp_tab.insert(L.resp_tab.end(), L.hid.begin(), L.hid.end());
+    L.resp_tab.push_back((uint32_t)n_io);
+    return CG_OK;
 }
+// under a key: the length first, then the types
+int io_layout(const cg_pvk* k, const uint8_t* io_types, uint64_t n_io, IoLayout& L) {
+    if (n_io != k->n_inputs)
+        return fail(CG_ERR_MALFORMED_KEY, "%llu io types for a key with gamma_abc_g1.len() = %llu", (unsigned long long)n_io,
+                    (unsigned long long)(k->n_inputs + 1));
+    return io_layout(io_types, n_io, L);
+}
+
+// the verifier's shape and tab_of: the revealed inputs, then (with a DLogPoK) the responses
+ShowShape show_shape(const IoLayout& L, bool pok, std::vector<uint32_t>& tab_of) {
+    ShowShape sh;
+    sh.n_rev = (uint32_t)L.rev.size();
+    sh.n_com = (uint32_t)L.com.size();
+    sh.n_resp = (uint32_t)L.resp_tab.size();
+    sh.n_fixed = sh.n_rev + (pok ? sh.n_resp : 0);
+    sh.n_var = pok ? sh.n_com + 1 : 0;
+    sh.n_terms = sh.n_fixed + sh.n_var;
+    tab_of = L.rev;
+    if (pok) tab_of.insert(tab_of.end(), L.resp_tab.begin(), L.resp_tab.end());
+    return sh;
+}
+
+MkShape mk_shape(const IoLayout& L, uint64_t n_io) {
+    MkShape sh;
+    sh.n_io = (uint32_t)n_io;
+    sh.n_com = (uint32_t)L.com.size();
+    sh.n_resp = (uint32_t)L.resp_tab.size();
+    sh.n_rand = 3 + sh.n_com + sh.n_resp;
+    sh.n_fix = 2 * sh.n_resp + 1;
+    sh.n_terms = sh.n_fix + 2;
+    sh.n_out = 2 * sh.n_com + 5;
+    return sh;
+}
+// the creator's desc: [table of term t | scalar of term t], as k_mk_fixed reads it
+std::vector<uint32_t> mk_desc(const IoLayout& L, const MkShape& sh) {
+    std::vector<uint32_t> desc = L.resp_tab, src;
+    desc.insert(desc.end(), L.resp_tab.begin(), L.resp_tab.end());               // the nonces walk the same tables
+    desc.push_back(sh.n_io + 1);                                                 // (acc_r + z)·G
+    for (uint32_t c = 0; c < sh.n_com; ++c) {                     // (x_i, r_i) on (gamma_abc[i+1], delta_g1)
+        src.push_back(L.com[c]);
+        src.push_back(MK_RAND | (2 + c));
+    }
+    src.insert(src.end(), L.hid.begin(), L.hid.end());
+    src.push_back(MK_RAND | (2 + sh.n_com));                                     // z on delta_g1
+    for (uint32_t t = 0; t < sh.n_resp; ++t) src.push_back(MK_RAND | (3 + sh.n_com + t));
+    src.push_back(0);                                                            // the last lane forms its own scalar
+    desc.insert(desc.end(), src.begin(), src.end());
+    return desc;
+}
+}  // namespace
 
 extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, const uint8_t* revealed,
                                     const uint8_t* rand_proofs, const uint8_t* com_hidden, const uint8_t* committed,
                                     const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    if (n_io != k->n_inputs)
-        return fail(CG_ERR_MALFORMED_KEY, "%llu io types for a key with gamma_abc_g1.len() = %llu", (unsigned long long)n_io,
-                    (unsigned long long)(k->n_inputs + 1));
-    if (n_io && !io_types) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    // the layout: which table each fixed-base term walks (table n_inputs is delta_g1's)
-    std::vector<uint32_t> rev_tab, hid_tab, resp_tab;
-    for (uint64_t i = 0; i < n_io; ++i) {
-        switch (io_types[i]) {
-            case CG_IO_REVEALED: rev_tab.push_back((uint32_t)i); break;
-            case CG_IO_HIDDEN: hid_tab.push_back((uint32_t)i); break;
-            case CG_IO_COMMITTED:
-                resp_tab.push_back((uint32_t)i);
-                resp_tab.push_back((uint32_t)n_io);
-                break;
-            default: return fail(CG_ERR_INVALID_ARGUMENT, "io_types[%llu] = %u is no PublicIOType", (unsigned long long)i, io_types[i]);
-        }
-    }
+    IoLayout L;
+    if (int rc = io_layout(k, io_types, n_io, L)) return rc;
     if (n == 0) return CG_OK;
     const bool pok = pok_c != nullptr;
-    ShowShape sh;
-    sh.n_rev = (uint32_t)rev_tab.size();
-    sh.n_com = (uint32_t)(resp_tab.size() / 2);
-    resp_tab.insert(resp_tab.end(), hid_tab.begin(), hid_tab.end());
-    resp_tab.push_back((uint32_t)n_io);
-    sh.n_resp = (uint32_t)resp_tab.size();
-    sh.n_fixed = sh.n_rev + (pok ? sh.n_resp : 0);
-    sh.n_var = pok ? sh.n_com + 1 : 0;
-    sh.n_terms = sh.n_fixed + sh.n_var;
+    std::vector<uint32_t> tab_of;            // which table each fixed-base term walks
+    const ShowShape sh = show_shape(L, pok, tab_of);
     if (!rand_proofs || !com_hidden || !verdicts || (sh.n_rev && !revealed) || (sh.n_com && !committed) || (pok && (!pok_s || !k_out)))
         return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    std::vector<uint32_t> tab_of = rev_tab;
-    if (pok) tab_of.insert(tab_of.end(), resp_tab.begin(), resp_tab.end());
     try {
         std::lock_guard<std::mutex> lk(k->mu);
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
-        grow(k->d_proofs, chunk * 256);
-        grow(k->d_status, chunk);
-        grow(k->d_verdict, chunk);
-        grow(k->d_parsed, chunk);
-        grow(k->d_f, chunk);
-        grow(k->d_part, chunk * sh.n_terms + 1);
-        grow(k->s_rev, chunk * sh.n_rev * 32 + 32);
-        grow(k->s_comh, chunk * 64);
-        grow(k->s_comm, chunk * sh.n_com * 64 + 64);
-        grow(k->s_c, chunk * 32);
-        grow(k->s_s, chunk * sh.n_resp * 32);
-        grow(k->s_k, chunk * (sh.n_com + 1) * 32);
-        grow(k->s_tab_of, tab_of.size() + 1);
-        h2d_sync(k->s_tab_of.p, tab_of.data(), tab_of.size() * sizeof(uint32_t), k->st);
         const uint32_t n_stmt = sh.n_com + 1;
+        grow(k->b_proofs, chunk * 256);
+        grow(k->b_status, chunk);
+        grow(k->b_verdict, chunk);
+        grow(k->b_parsed, chunk);
+        grow(k->b_miller, chunk);
+        grow(k->b_part, chunk * sh.n_terms + 1);
+        grow(k->b_inputs, chunk * sh.n_rev * 32 + 32);
+        grow(k->b_comh, chunk * 64);
+        grow(k->b_comm, chunk * sh.n_com * 64 + 64);
+        grow(k->b_chal, chunk * 32);
+        grow(k->b_rows, chunk * sh.n_resp * 32);
+        grow(k->b_k, chunk * n_stmt * 32);
+        grow(k->b_desc, tab_of.size() + 1);
+        h2d_sync(k->b_desc.p, tab_of.data(), tab_of.size() * sizeof(uint32_t), k->st);
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            CG_HIP(hipMemcpyAsync(k->d_proofs.p, rand_proofs + off * 256, m * 256, hipMemcpyHostToDevice, k->st));
-            CG_HIP(hipMemcpyAsync(k->s_comh.p, com_hidden + off * 64, m * 64, hipMemcpyHostToDevice, k->st));
-            if (sh.n_rev) CG_HIP(hipMemcpyAsync(k->s_rev.p, revealed + off * sh.n_rev * 32, m * sh.n_rev * 32, hipMemcpyHostToDevice, k->st));
-            if (sh.n_com) CG_HIP(hipMemcpyAsync(k->s_comm.p, committed + off * sh.n_com * 64, m * sh.n_com * 64, hipMemcpyHostToDevice, k->st));
+            rows_up(k, k->b_proofs, rand_proofs, off, m, 256);
+            rows_up(k, k->b_comh, com_hidden, off, m, 64);
+            rows_up(k, k->b_inputs, revealed, off, m, sh.n_rev * 32);
+            rows_up(k, k->b_comm, committed, off, m, sh.n_com * 64);
             if (pok) {
-                CG_HIP(hipMemcpyAsync(k->s_c.p, pok_c + off * 32, m * 32, hipMemcpyHostToDevice, k->st));
-                CG_HIP(hipMemcpyAsync(k->s_s.p, pok_s + off * sh.n_resp * 32, m * sh.n_resp * 32, hipMemcpyHostToDevice, k->st));
+                rows_up(k, k->b_chal, pok_c, off, m, 32);
+                rows_up(k, k->b_rows, pok_s, off, m, sh.n_resp * 32);
             }
-            const uint32_t *d_rev = (const uint32_t*)k->s_rev.p, *d_s = (const uint32_t*)k->s_s.p, *d_c = (const uint32_t*)k->s_c.p,
-                           *d_comh = (const uint32_t*)k->s_comh.p, *d_comm = (const uint32_t*)k->s_comm.p;
+            const uint32_t *d_rev = (const uint32_t*)k->b_inputs.p, *d_s = (const uint32_t*)k->b_rows.p, *d_c = (const uint32_t*)k->b_chal.p,
+                           *d_comh = (const uint32_t*)k->b_comh.p, *d_comm = (const uint32_t*)k->b_comm.p;
             if (sh.n_terms) {
                 const uint32_t blocks = ceil_div(m * sh.n_fixed, VBLOCK) + ceil_div(m * sh.n_var, VBLOCK);
-                k_show_terms<<<blocks, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->s_tab_of.p,
-                                                                           k->tab.p, k->d_part.p);
+                k_show_terms<<<blocks, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_desc.p, k->tab.p, k->b_part.p);
                 CG_KERNEL_CHECK();
             }
             const uint32_t grid = ceil_div(m, VBLOCK);
-            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->d_proofs.p, d_rev, m, 0u, k->d_part.p, k->g0, k->d_parsed.p,
-                                                    k->d_status.p);
+            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->b_proofs.p, d_rev, m, 0u, k->b_part.p, k->g0, k->b_parsed.p,
+                                                    k->b_status.p);
             CG_KERNEL_CHECK();
-            k_show_check<<<grid, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->d_part.p, k->g0, k->d_parsed.p,
-                                                     k->d_status.p);
+            k_show_check<<<grid, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_part.p, k->g0, k->b_parsed.p,
+                                                     k->b_status.p);
             CG_KERNEL_CHECK();
             if (pok) {
-                k_show_k<<<ceil_div(m * n_stmt, VBLOCK), VBLOCK, 0, k->st>>>(m, sh, k->d_part.p, k->d_status.p, (uint32_t*)k->s_k.p);
+                k_show_k<<<ceil_div(m * n_stmt, VBLOCK), VBLOCK, 0, k->st>>>(m, sh, k->b_part.p, k->b_status.p, (uint32_t*)k->b_k.p);
                 CG_KERNEL_CHECK();
             }
-            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->d_parsed.p, k->d_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
-                                                     k->delta_live, k->d_f.p);
+            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
+                                                     k->delta_live, k->b_miller.p);
             CG_KERNEL_CHECK();
-            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->d_f.p, k->d_status.p, m, k->alpha_beta, k->d_verdict.p);
+            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.p, m, k->alpha_beta, k->b_verdict.p);
             CG_KERNEL_CHECK();
-            CG_HIP(hipMemcpyAsync(verdicts + off, k->d_verdict.p, m, hipMemcpyDeviceToHost, k->st));
-            if (pok) CG_HIP(hipMemcpyAsync(k_out + off * n_stmt * 32, k->s_k.p, m * n_stmt * 32, hipMemcpyDeviceToHost, k->st));
+            rows_down(k, verdicts, k->b_verdict, off, m, 1);
+            if (pok) rows_down(k, k_out, k->b_k, off, m, n_stmt * 32);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -880,55 +842,11 @@ extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
     }
 }
 
-// ---- creating showings: the layout of one call, shared by the three entries ---------------------------------------------
-namespace {
-struct MkLayout {
-    MkShape sh;
-    std::vector<uint32_t> desc;        // [table of term t | scalar of term t], as k_mk_fixed reads it
-};
-// 0, or the failure already recorded
-int mk_layout(const uint8_t* io_types, uint64_t n_io, MkLayout& L) {
-    if (n_io && !io_types) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    if (n_io >= MK_RAND / 4) return fail(CG_ERR_INVALID_ARGUMENT, "too many io types");
-    std::vector<uint32_t> com, hid;
-    for (uint64_t i = 0; i < n_io; ++i) {
-        switch (io_types[i]) {
-            case CG_IO_REVEALED: break;
-            case CG_IO_HIDDEN: hid.push_back((uint32_t)i); break;
-            case CG_IO_COMMITTED: com.push_back((uint32_t)i); break;
-            default: return fail(CG_ERR_INVALID_ARGUMENT, "io_types[%llu] = %u is no PublicIOType", (unsigned long long)i, io_types[i]);
-        }
-    }
-    MkShape& sh = L.sh;
-    sh.n_io = (uint32_t)n_io;
-    sh.n_com = (uint32_t)com.size();
-    sh.n_resp = 2 * sh.n_com + (uint32_t)hid.size() + 1;
-    sh.n_rand = 3 + sh.n_com + sh.n_resp;
-    sh.n_fix = 2 * sh.n_resp + 1;
-    sh.n_terms = sh.n_fix + 2;
-    sh.n_out = 2 * sh.n_com + 5;
-    std::vector<uint32_t> tab_of, src;
-    for (uint32_t c = 0; c < sh.n_com; ++c) {                     // (x_i, r_i) on (gamma_abc[i+1], delta_g1)
-        tab_of.push_back(com[c]); src.push_back(com[c]);
-        tab_of.push_back(sh.n_io); src.push_back(MK_RAND | (2 + c));
-    }
-    for (uint32_t j : hid) { tab_of.push_back(j); src.push_back(j); }
-    tab_of.push_back(sh.n_io); src.push_back(MK_RAND | (2 + sh.n_com));          // z on delta_g1
-    for (uint32_t t = 0; t < sh.n_resp; ++t) {                    // the nonces walk the same tables
-        tab_of.push_back(tab_of[t]); src.push_back(MK_RAND | (3 + sh.n_com + t));
-    }
-    tab_of.push_back(sh.n_io + 1); src.push_back(0);              // (acc_r + z)·G: the lane forms its own scalar
-    L.desc = tab_of;
-    L.desc.insert(L.desc.end(), src.begin(), src.end());
-    return CG_OK;
-}
-}  // namespace
-
 extern "C" int cg_show_rand_count(const uint8_t* io_types, uint64_t n_io, uint64_t* n_rand) {
     if (!n_rand) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    MkLayout L;
-    if (int rc = mk_layout(io_types, n_io, L)) return rc;
-    *n_rand = L.sh.n_rand;
+    IoLayout L;
+    if (int rc = io_layout(io_types, n_io, L)) return rc;
+    *n_rand = mk_shape(L, n_io).n_rand;
     return CG_OK;
 }
 
@@ -936,56 +854,54 @@ extern "C" int cg_show_commit_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
                                     const uint8_t* rand, uint64_t n, uint8_t* rand_proofs, uint8_t* com_hidden, uint8_t* committed,
                                     uint8_t* k_out, uint8_t* status) {
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    if (n_io != k->n_inputs)
-        return fail(CG_ERR_MALFORMED_KEY, "%llu io types for a key with gamma_abc_g1.len() = %llu", (unsigned long long)n_io,
-                    (unsigned long long)(k->n_inputs + 1));
-    MkLayout L;
-    if (int rc = mk_layout(io_types, n_io, L)) return rc;
+    IoLayout L;
+    if (int rc = io_layout(k, io_types, n_io, L)) return rc;
     if (!k->gamma_is_one)
         return fail(CG_ERR_MALFORMED_KEY, "gamma_g2 is not the G2 generator: C - (acc_r + z) G re-randomises gamma = 1 keys only");
     if (n == 0) return CG_OK;
-    const MkShape sh = L.sh;
+    const MkShape sh = mk_shape(L, n_io);
     if (!proofs || !rand || !rand_proofs || !com_hidden || !k_out || !status || (sh.n_resp > 1 && !inputs) || (sh.n_com && !committed))
         return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    const std::vector<uint32_t> desc = mk_desc(L, sh);
     try {
         std::lock_guard<std::mutex> lk(k->mu);
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
         const uint32_t n_stmt = sh.n_com + 1;
-        grow(k->d_proofs, chunk * 256);
-        grow(k->d_inputs, chunk * sh.n_io * 32 + 32);
-        grow(k->d_status, chunk);
-        grow(k->d_part, chunk * sh.n_terms + 1);
-        grow(k->m_rand, chunk * sh.n_rand * 32);
-        grow(k->m_part_g2, chunk);
-        grow(k->m_rproofs, chunk * 256);
-        grow(k->m_comh, chunk * 64);
-        grow(k->m_comm, chunk * sh.n_com * 64 + 64);
-        grow(k->m_k, chunk * n_stmt * 32);
-        grow(k->m_desc, L.desc.size());
-        h2d_sync(k->m_desc.p, L.desc.data(), L.desc.size() * sizeof(uint32_t), k->st);
+        grow(k->b_proofs, chunk * 256);
+        grow(k->b_inputs, chunk * sh.n_io * 32 + 32);
+        grow(k->b_status, chunk);
+        grow(k->b_part, chunk * sh.n_terms + 1);
+        grow(k->b_rows, chunk * sh.n_rand * 32);
+        grow(k->b_part_g2, chunk);
+        grow(k->b_rproofs, chunk * 256);
+        grow(k->b_comh, chunk * 64);
+        grow(k->b_comm, chunk * sh.n_com * 64 + 64);
+        grow(k->b_k, chunk * n_stmt * 32);
+        grow(k->b_desc, desc.size());
+        h2d_sync(k->b_desc.p, desc.data(), desc.size() * sizeof(uint32_t), k->st);
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            CG_HIP(hipMemcpyAsync(k->d_proofs.p, proofs + off * 256, m * 256, hipMemcpyHostToDevice, k->st));
-            if (inputs && sh.n_io) CG_HIP(hipMemcpyAsync(k->d_inputs.p, inputs + off * sh.n_io * 32, m * sh.n_io * 32, hipMemcpyHostToDevice, k->st));
-            CG_HIP(hipMemcpyAsync(k->m_rand.p, rand + off * sh.n_rand * 32, m * sh.n_rand * 32, hipMemcpyHostToDevice, k->st));
-            const uint32_t *d_pr = (const uint32_t*)k->d_proofs.p, *d_in = (const uint32_t*)k->d_inputs.p, *d_rd = (const uint32_t*)k->m_rand.p;
-            k_mk_check<<<ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_in, d_rd, m, sh, k->m_desc.p, k->d_status.p);
+            rows_up(k, k->b_proofs, proofs, off, m, 256);
+            rows_up(k, k->b_inputs, inputs, off, m, sh.n_io * 32);
+            rows_up(k, k->b_rows, rand, off, m, sh.n_rand * 32);
+            const uint32_t *d_pr = (const uint32_t*)k->b_proofs.p, *d_in = (const uint32_t*)k->b_inputs.p, *d_rd = (const uint32_t*)k->b_rows.p;
+            k_mk_check<<<ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_in, d_rd, m, sh, k->b_desc.p, k->b_status.p);
             CG_KERNEL_CHECK();
-            k_mk_fixed<<<ceil_div(m * sh.n_fix, VBLOCK), VBLOCK, 0, k->st>>>(d_in, d_rd, m, sh, k->m_desc.p, k->tab.p, k->d_part.p);
+            k_mk_fixed<<<ceil_div(m * sh.n_fix, VBLOCK), VBLOCK, 0, k->st>>>(d_in, d_rd, m, sh, k->b_desc.p, k->tab.p, k->b_part.p);
             CG_KERNEL_CHECK();
-            k_mk_var<<<ceil_div(2 * m, VBLOCK) + ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_rd, m, sh, k->tab_g2.p, k->d_part.p,
-                                                                                         k->m_part_g2.p);
+            k_mk_var<<<ceil_div(2 * m, VBLOCK) + ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_rd, m, sh, k->tab_g2.p, k->b_part.p,
+                                                                                         k->b_part_g2.p);
             CG_KERNEL_CHECK();
-            k_mk_out<<<ceil_div(m * sh.n_out, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, k->d_part.p, k->m_part_g2.p, k->d_status.p,
-                                                                          (uint32_t*)k->m_rproofs.p, (uint32_t*)k->m_comh.p,
-                                                                          (uint32_t*)k->m_comm.p, (uint32_t*)k->m_k.p);
+            k_mk_out<<<ceil_div(m * sh.n_out, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, k->b_part.p, k->b_part_g2.p, k->b_status.p,
+                                                                          (uint32_t*)k->b_rproofs.p, (uint32_t*)k->b_comh.p,
+                                                                          (uint32_t*)k->b_comm.p, (uint32_t*)k->b_k.p);
             CG_KERNEL_CHECK();
-            CG_HIP(hipMemcpyAsync(rand_proofs + off * 256, k->m_rproofs.p, m * 256, hipMemcpyDeviceToHost, k->st));
-            CG_HIP(hipMemcpyAsync(com_hidden + off * 64, k->m_comh.p, m * 64, hipMemcpyDeviceToHost, k->st));
-            if (sh.n_com) CG_HIP(hipMemcpyAsync(committed + off * sh.n_com * 64, k->m_comm.p, m * sh.n_com * 64, hipMemcpyDeviceToHost, k->st));
-            CG_HIP(hipMemcpyAsync(k_out + off * n_stmt * 32, k->m_k.p, m * n_stmt * 32, hipMemcpyDeviceToHost, k->st));
-            CG_HIP(hipMemcpyAsync(status + off, k->d_status.p, m, hipMemcpyDeviceToHost, k->st));
+            rows_down(k, rand_proofs, k->b_rproofs, off, m, 256);
+            rows_down(k, com_hidden, k->b_comh, off, m, 64);
+            rows_down(k, committed, k->b_comm, off, m, sh.n_com * 64);
+            rows_down(k, k_out, k->b_k, off, m, n_stmt * 32);
+            rows_down(k, status, k->b_status, off, m, 1);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -997,12 +913,13 @@ extern "C" int cg_show_commit_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
 // DLogPoK::prove's responses (dlog.rs:101-109) once the host's transcript has produced c: plain host arithmetic
 extern "C" int cg_show_respond_batch(const uint8_t* io_types, uint64_t n_io, const uint8_t* inputs, const uint8_t* rand,
                                      const uint8_t* pok_c, const uint8_t* status, uint64_t n, uint8_t* pok_s) {
-    MkLayout L;
-    if (int rc = mk_layout(io_types, n_io, L)) return rc;
+    IoLayout L;
+    if (int rc = io_layout(io_types, n_io, L)) return rc;
     if (n == 0) return CG_OK;
-    const MkShape sh = L.sh;
+    const MkShape sh = mk_shape(L, n_io);
     if (!rand || !pok_c || !pok_s || (sh.n_resp > 1 && !inputs)) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    const uint32_t* src = L.desc.data() + sh.n_fix;
+    const std::vector<uint32_t> desc = mk_desc(L, sh);
+    const uint32_t* src = desc.data() + sh.n_fix;
     auto secret = [&](uint64_t p, uint32_t t) {
         return src[t] & MK_RAND ? rand + 32 * (p * sh.n_rand + (src[t] & ~MK_RAND)) : inputs + 32 * (p * sh.n_io + src[t]);
     };

@@ -1,4 +1,4 @@
-// Host build of csrc/pairing.hpp (plain g++), driven by tests/test_pairing_host.py: one command per input line, every
+// Host build of csrc/pairing.hpp and csrc/fixed_base.hpp (plain g++), driven by tests/test_pairing_host.py: one command per input line, every
 // operand and result as hex of canonical little-endian bytes in ark-serialize order (Fq12: 384 B, G1: x ‖ y, G2:
 // x.c0 ‖ x.c1 ‖ y.c0 ‖ y.c1, identity = zeros).  The Python side computes the same values with the oracle.
 //
@@ -8,6 +8,8 @@
 //   fexp F                  final exponentiation                              -> Fq12, or NONE for F = 0
 //   check P|Q KIND          KIND in g1 (on curve), g2 (on twist), sub (in G2)  -> 0 / 1
 //   inputs N G0..GN X1..XN  prepare_inputs                                    -> G1
+//   fb g1|g2 BASE K         csrc/fixed_base.hpp: build_tables of one base, then fixed_base_mul (K: any 32 bytes)  -> G1 / G2
+//   mul254 g1|g2 BASE K     its scalar_mul_254_mixed, K < 2^254              -> G1 / G2
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -17,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "../../crescent-credentials_amd/csrc/fixed_base.hpp"
 #include "../../crescent-credentials_amd/csrc/pairing.hpp"
 
 using namespace cg;
@@ -59,6 +62,13 @@ static bool zeros(const std::vector<uint8_t>& b) {
 static G1Affine g1_in(const std::vector<uint8_t>& b) { return zeros(b) ? G1Affine::inf() : G1Affine{fq_in(b.data()), fq_in(b.data() + 32)}; }
 static G2Affine g2_in(const std::vector<uint8_t>& b) {
     return zeros(b) ? G2Affine::inf() : G2Affine{fq2_in(b.data()), fq2_in(b.data() + 64)};
+}
+// the table of one base as a key builds it (the first base of build_tables takes no table), walked once
+template <class F>
+static XYZZ<F> fb_mul(const Affine<F>& base, const uint32_t k[8]) {
+    std::vector<Affine<F>> tab;
+    build_tables(std::vector<Affine<F>>{Affine<F>::inf(), base}, tab);
+    return fixed_base_mul(tab.data(), k);
 }
 
 int main() {
@@ -130,6 +140,20 @@ int main() {
             G1Affine r = to_affine(prepare_inputs(g.data(), x.data(), n));
             std::vector<uint8_t> o;
             if (!r.is_inf()) { fq_out(r.x, o); fq_out(r.y, o); } else o.assign(64, 0);
+            printf("%s\n", hex(o).c_str());
+        } else if (cmd == "fb" || cmd == "mul254") {
+            std::string grp, base, ks;
+            in >> grp >> base >> ks;
+            std::vector<uint8_t> kb = unhex(ks), o;
+            uint32_t k[8];
+            memcpy(k, kb.data(), 32);
+            if (grp == "g1") {
+                G1Affine r = to_affine(cmd == "fb" ? fb_mul(g1_in(unhex(base)), k) : scalar_mul_254_mixed(g1_in(unhex(base)), k));
+                if (!r.is_inf()) { fq_out(r.x, o); fq_out(r.y, o); } else o.assign(64, 0);
+            } else {
+                G2Affine r = to_affine(cmd == "fb" ? fb_mul(g2_in(unhex(base)), k) : scalar_mul_254_mixed(g2_in(unhex(base)), k));
+                if (!r.is_inf()) { fq2_out(r.x, o); fq2_out(r.y, o); } else o.assign(128, 0);
+            }
             printf("%s\n", hex(o).c_str());
         } else if (!cmd.empty()) {
             printf("ERR\n");

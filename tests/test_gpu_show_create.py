@@ -261,3 +261,58 @@ def test_the_verifiers_are_undisturbed(cc):
         s1, k1 = cc.Groth16.verify_show_batch(gpu, io, shows)
     assert list(v0) == [1, 0, 1] and list(s0) == [1, 1, 0]
     assert np.array_equal(v0, v1) and np.array_equal(s0, s1) and np.array_equal(k0, k1)
+
+
+def test_entries_share_the_buffers_of_one_handle(cc):
+    """the three entries on one handle in growing and in shrinking order, so that each in turn is the one that last grew a
+    buffer the others read (proofs, scalars, com_hidden, committed, k, the term descriptor): every call returns what the same
+    call returns on a handle of its own.  The sizes cross one 64-lane workgroup; every call has one tampered or malformed
+    item."""
+    rng, sc, vk, xs, abc = M.synthetic(6, 0x5AFE)
+    io = M.layout("mixed", 6)
+    proof = M.proof_of(abc)
+    made = [M.make(vk, proof, xs, io, rng) for _ in range(2)]
+    tampered = S.clone(made[1].show, revealed=[(made[1].show.revealed[0] + 1) % R] + made[1].show.revealed[1:])
+    shows = [S.api_show(cc, made[0].show), S.api_show(cc, tampered), S.api_show(cc, made[1].show)]
+    flipped = list(xs)
+    flipped[0] = (flipped[0] + 1) % R
+    row = list(made[0].rand)
+    row[1] = 0                                                    # r2 = 0
+    bad = M.Made(proof, list(xs), row, None)
+
+    def one_bad(n, at, good, other):
+        return [other if i == at else good(i) for i in range(n)]
+
+    def verify_show(gpu):
+        v, k = cc.Groth16.verify_show_batch(gpu, io, shows)
+        assert list(v) == [1, 0, 1]
+        return [v.copy(), k.copy()]
+
+    def verify(n, at):
+        def call(gpu):
+            v = cc.Groth16.verify_batch(gpu, one_bad(n, at, lambda i: xs, flipped), [o.proof_uncompressed(proof)] * n)
+            assert list(v) == one_bad(n, at, lambda i: 1, 0)
+            return [v.copy()]
+        return call
+
+    def commit(n, at):
+        def call(gpu):
+            got = _commit(cc, gpu, io, one_bad(n, at, lambda i: made[i % 2], bad))
+            assert list(got[4]) == one_bad(n, at, lambda i: M.MADE, M.MALFORMED)
+            return [a.copy() for a in got]
+        return call
+
+    calls = [verify_show, verify(130, 64), commit(70, 64), verify_show, verify(2, 1), commit(1, 0)]
+    with _gpu_key(cc, vk) as gpu:
+        shared = [call(gpu) for call in calls]
+    for i, call in enumerate(calls):
+        if i == 0:                                                # the handle was fresh then
+            continue
+        if i == 3:                                                # the same call as the first
+            alone = shared[0]
+        else:
+            with _gpu_key(cc, vk) as gpu:
+                alone = call(gpu)
+        assert len(alone) == len(shared[i])
+        for a, b in zip(alone, shared[i]):
+            assert np.array_equal(a, b), i

@@ -136,3 +136,17 @@ def test_prepare_inputs(tool):
     line = "inputs 3 " + " ".join(V.g1_hex(p) for p in vk["gamma_abc_g1"]) + " " + \
         " ".join(int(x).to_bytes(32, "little").hex() for x in xs)
     assert tool(line) == V.g1_hex(want)
+
+
+@pytest.mark.parametrize("group", ["g1", "g2"])
+def test_fixed_base_walk_and_254_step_chain(tool, group):
+    """csrc/fixed_base.hpp's build_tables + fixed_base_mul and its scalar_mul_254_mixed against the oracle's k·P:
+    the edges of a window (0, 1, 255, 256), the top byte empty, r - 1, every digit 0xFF (an unreduced scalar for the walk,
+    2^254 - 1 for the chain, both >= r) and two seeded values"""
+    rng = V.rng(6)
+    curve, P, hx = (o.G1, V.g1(0xC0FFEE), V.g1_hex) if group == "g1" else (o.G2, V.g2(0xC0FFEE), V.g2_hex)
+    common = [0, 1, 255, 256, 2 ** 248 - 1, R - 1, rng.randrange(R), rng.randrange(R)]
+    for cmd, ks in (("fb", common + [2 ** 256 - 1]), ("mul254", common + [2 ** 254 - 1])):
+        for k in ks:
+            want = curve.to_affine(curve.mul_affine(P, k))
+            assert tool("%s %s %s %s" % (cmd, group, hx(P), k.to_bytes(32, "little").hex())) == hx(want), (cmd, hex(k))
