@@ -306,6 +306,34 @@ CG_HD Fp<typename P::P256> to_canonical_bytes(const F29<P>& a) {     // x·R' ->
 using Fq29 = F29<Fq29P>;
 using Fr29 = F29<Fr29P>;
 
+// ---- the transforms' lazy steps (wmap29.hip k_ntt29_pass; tools/bounds29.py replays their bounds) -------------------------
+// v (normalised, value < 2^261) -> r ≡ v (mod N), normalised, r < 3N < 2^256: a one-word quotient estimate instead of
+// a full Montgomery product; used where a value only has to fit the packed 32-byte form again.
+CG_HD Fr29 weak_reduce(const Fr29& v) {
+    // q = floor(l[8] * MU / 2^48) with MU = floor(2^280 / N) and l[8] = floor(v / 2^232): never above v / N,
+    // short of it by less than 2
+    constexpr uint32_t MU = 88753990u;   // floor(2^280 / r), r = BN254 scalar modulus
+    const uint32_t q = (uint32_t)(((uint64_t)v.l[8] * MU) >> 48);
+    const int32_t nq = -(int32_t)q;
+    Fr29 r;
+    int64_t c = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        c += (int64_t)v.l[i];
+        c += (int64_t)nq * (int64_t)(int32_t)Fr29P::N[i];
+        if (i < 8) { r.l[i] = (uint32_t)c & M29; c >>= 29; }
+        else r.l[i] = (uint32_t)c;
+    }
+    return r;
+}
+
+// DIT butterfly on lazy values: t = v·w;  (u, v) <- (u + t, u - t + 3N).  Limbs are NOT renormalised here.
+CG_HD void bfly(Fr29& u, Fr29& v, const Fr29& w) {
+    Fr29 t = mul(v, w);
+    v = sub<3, 1>(u, t);
+    u = add(u, t);
+}
+
 // ---- SIGNED 29-bit limbs: the G1 bucket accumulation's inner arithmetic (curve29.hpp madd29s) ----------------------------
 // value(a) = Σ a.l[i]·2^(29 i) with SIGNED limbs; "s-normalised" = limbs 0..7 in [0, 2^29), limb 8 signed (it carries the
 // sign of the value).  Products are chains of v_mad_i64_i32 into one signed 64-bit column sum, carries are arithmetic

@@ -92,26 +92,6 @@ __device__ __forceinline__ Fr29 load_tw(const uint32_t* __restrict__ tw, uint64_
     return r;
 }
 
-// v (normalised, value < 2^261) -> r ≡ v (mod N), normalised, r < 3N < 2^256: a one-word quotient estimate instead of
-// a full Montgomery product; used where a value only has to fit the packed 32-byte form again.
-__device__ __forceinline__ Fr29 weak_reduce(const Fr29& v) {
-    // q = floor(l[8] * MU / 2^48) with MU = floor(2^280 / N) and l[8] = floor(v / 2^232): never above v / N,
-    // short of it by less than 2
-    constexpr uint32_t MU = 88753990u;   // floor(2^280 / r), r = BN254 scalar modulus
-    const uint32_t q = (uint32_t)(((uint64_t)v.l[8] * MU) >> 48);
-    const int32_t nq = -(int32_t)q;
-    Fr29 r;
-    int64_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        c += (int64_t)v.l[i];
-        c += (int64_t)nq * (int64_t)(int32_t)Fr29P::N[i];
-        if (i < 8) { r.l[i] = (uint32_t)c & M29; c >>= 29; }
-        else r.l[i] = (uint32_t)c;
-    }
-    return r;
-}
-
 void Wm29Domain::build(const NttDomain& d, hipStream_t st) {
     logn = d.logn;
     n = d.n;
@@ -151,7 +131,9 @@ void Wm29Strided::build(const NttDomain& big, int logs_, int rank, hipStream_t s
 }
 
 // out[rev_d(i)] = Σ_t a[i + t·d]·T[i + t·d], i < d, t < 2^logs (Wm29Strided): a the unscaled output of the inverse
-// transform (packed, < 2^256), T canonical.  A product is below 1.04 N; limbs are renormalised every fourth term.
+// transform (packed, < 2^256), T canonical.  A product is below 1.04 N; limbs are renormalised every fourth term and the
+// value is brought back below 3N every 64th, so that a sum stays below 69N (of the 169N limbs hold) for ANY number of
+// terms: the loader admits 2^logs of them up to logD - 4, and 256 products already pass 2^261 (tools/bounds29.py check_fold).
 __global__ void __launch_bounds__(256) k_fold29(const uint32_t* __restrict__ a, const uint32_t* __restrict__ T, uint32_t* __restrict__ out,
                                                 uint32_t d, int logd, uint32_t terms) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,6 +143,7 @@ __global__ void __launch_bounds__(256) k_fold29(const uint32_t* __restrict__ a, 
         const uint64_t e = (uint64_t)i + (uint64_t)t * d;
         acc = add(acc, mul(load_packed29(a, e), load_packed29(T, e)));
         if ((t & 3u) == 3u) acc = normalize(acc);
+        if ((t & 63u) == 63u) acc = weak_reduce(acc);
     }
     store_packed29(out, brev(i, logd), weak_reduce(normalize(acc)));
 }
@@ -313,13 +296,6 @@ __device__ __forceinline__ void lds_put(uint32_t* s, uint32_t e, const Fr29& x) 
 
 struct Packed8 { uint32_t w[8]; };
 
-// DIT butterfly on lazy values: t = v·w;  (u, v) <- (u + t, u - t + 3N).  Limbs are NOT renormalised here.
-__device__ __forceinline__ void bfly(Fr29& u, Fr29& v, const Fr29& w) {
-    Fr29 t = mul(v, w);
-    v = sub<3, 1>(u, t);
-    u = add(u, t);
-}
-
 // LOAD: 0 = one input vector; 1 = (a∘b - c)·vinv from three vectors (r1cs_to_qap.rs:187,201-208)
 // STORE: 0 = value reduced just enough to pack; 1 = multiplied by scale[natural index] and made canonical
 //        (coset factor, or the exit from Montgomery form); 2 = multiplied by the constant passed in `vinv_p`
@@ -329,9 +305,12 @@ __device__ __forceinline__ void bfly(Fr29& u, Fr29& v, const Fr29& w) {
 //        201-208; c's part is folded into the l query at load, msm.hpp)
 // Stages are taken two at a time as radix-4 groups held in registers (three twiddle loads and ONE carry
 // propagation per element for two stages, half the barriers); an odd last stage runs radix-2.
-// Lazy-value bounds: a pass starts below 6N (packed inputs are < 2^256 = 5.3N), every stage adds at most 3N — the
-// product-free first group of a transform ends below 22.6N instead — so after ten stages values stay under 47N
-// (representable: 2^261 = 169N) and limbs, renormalised every second stage, under 2^32.
+// Lazy-value bounds (replayed by tools/bounds29.py check_ntt_pass over every plan dit29 makes, logn 0..28, both tiles):
+// a pass starts below 5.3N (packed inputs are < 2^256; a strided pass starts from weak_reduce's output, below 3N), every
+// stage adds at most 3N — the product-free first group of a transform ends below 22.6N instead — so the ten stages of a
+// small tile's first pass stay under 46.6N, the ELEVEN of the big tile's under 49.6N (the largest of any plan), a strided
+// pass of ten stages under 33N (representable: 2^261 = 169N); every butterfly's product is below 1.3N, inside the 2N that
+// sub<3,1> and the stores' cond_sub_n ask for; and limbs, renormalised every second stage, stay at or below 5·2^29 < 2^32.
 template <int LOAD, int STORE, int TSL>
 __global__ void __launch_bounds__(256 << (TSL - 10)) k_ntt29_pass(const uint32_t* __restrict__ in_a, const uint32_t* __restrict__ in_b,
                                                     const uint32_t* __restrict__ in_c, uint32_t* __restrict__ out,

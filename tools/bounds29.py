@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bound checker for the lazy 29-bit-limb formulas of csrc/curve29.hpp.
+"""Bound checker for the lazy 29-bit-limb formulas of csrc/curve29.hpp and the lazy transforms of csrc/wmap29.hip.
 
 Every field value is tracked as (V, L): V = upper bound of the value in units of the modulus N,
 L = upper bound of limbs 0..7 in units of 2^29.  The script replays the exact operation sequence of
@@ -337,9 +337,196 @@ def check_sat_row():
     print("Fr   sat_row    packed < %.2f N, a·b < %.2f N, difference < %.2f N, before cond_sub_n < %.3f N  ok" % (packed, p.V, d.V, r.V))
 
 
+# ---- the lazy transforms of csrc/wmap29.hip: k_ntt29_pass, k_fold29, k_sell29's accumulation, weak_reduce -------------------
+# Fr only.  PACKED = 2^256 / N: the most the 32-byte form can hold, and what a pass's loads are bounded by.  Twiddles, the
+# scale tables, the constants of STORE 2 and STORE 3's second operand are CANONICAL (k_to_limbs12 / k_to_packed29 / cond_sub_n
+# made them): value < N, normalised.
+N_FR = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+PACKED = 2.0 ** 256 / N_FR
+WEAK_OUT = 3.0       # weak_reduce's contract, derived in check_weak_reduce()
+TS_SMALL, TS_BIG = 10, 11
+
+
+def _limbs_fit(x, what):
+    assert x.L * 2 ** 29 < 2 ** 32, "%s: limbs %.1f·2^29 before normalize" % (what, x.L)
+
+
+def _bfly(u, v):
+    """field29.hpp bfly: t = v·w; (u, v) <- (u + t, u - t + 3N), w canonical"""
+    t = Fq.mul(v, B(1.0, 1.0))
+    assert t.V < 2.0, "bfly: product %.3f N does not fit sub<3,1>" % t.V
+    return Fq.add(u, t), Fq.sub(u, t, 3, 1)
+
+
+def ntt_first_group(x):
+    """the q == 0 branch: stages 0 and 1 with three of the four products skipped; four inputs at x"""
+    x0 = x1 = x2 = x3 = x
+    t = x1; x1 = Fq.sub(x0, t, 7, 1); x0 = Fq.add(x0, t)
+    t = x3; x3 = Fq.sub(x2, t, 7, 1); x2 = Fq.add(x2, t)
+    t = x2; x2 = Fq.sub(x0, t, 12, 2); x0 = Fq.add(x0, t)
+    x1, x3 = _bfly(x1, x3)
+    out = (x0, x1, x2, x3)
+    for o in out:
+        _limbs_fit(o, "first group")
+    return Fq.norm(B(max(o.V for o in out), max(o.L for o in out)))
+
+
+def ntt_radix4(x):
+    x0 = x1 = x2 = x3 = x
+    x0, x1 = _bfly(x0, x1)
+    x2, x3 = _bfly(x2, x3)
+    x0, x2 = _bfly(x0, x2)
+    x1, x3 = _bfly(x1, x3)
+    out = (x0, x1, x2, x3)
+    for o in out:
+        _limbs_fit(o, "radix-4 group")
+    return Fq.norm(B(max(o.V for o in out), max(o.L for o in out)))
+
+
+def ntt_radix2(x):
+    u, v = _bfly(x, x)
+    _limbs_fit(u, "radix-2 stage"); _limbs_fit(v, "radix-2 stage")
+    return Fq.norm(B(max(u.V, v.V), max(u.L, v.L)))
+
+
+def ntt_stages(x, S, first):
+    """S stages of one pass from the bound x: radix-4 groups, an odd last stage radix-2; `first`: the pass starts at stage 0"""
+    j = 0
+    while j + 1 < S:
+        x = ntt_first_group(x) if (first and j == 0) else ntt_radix4(x)
+        j += 2
+    if j < S:
+        x = ntt_radix2(x)
+    return x
+
+
+def ntt_load1():
+    """LOAD == 1: mul(normalize(sub<7,1>(mul(a, b), c)), vinv), three packed operands"""
+    a = B(PACKED, 1.0)
+    d = Fq.norm(Fq.sub(Fq.mul(a, a), a, 7, 1))
+    x = Fq.mul(d, B(1.0, 1.0))
+    assert x.V < PACKED
+    return x
+
+
+def ntt_stores(x):
+    """every STORE form from the last stage's bound x (normalised)"""
+    assert x.L <= 1.0
+    y = Fq.mul(x, B(1.0, 1.0))          # STORE 1, 2, 3: by a canonical factor, then cond_sub_n
+    assert y.V < 2.0, "cond_sub_n after the store's product sees %.3f N" % y.V
+    assert x.V * N_FR < 2.0 ** 261      # STORE 0: weak_reduce
+    return y.V
+
+
+def check_weak_reduce():
+    """q = floor(l8·MU / 2^48), l8 = floor(v / 2^232), MU = floor(2^280 / N): r = v - q·N for a normalised v < 2^261"""
+    from fractions import Fraction as Fr_
+    MU = 2 ** 280 // N_FR
+    assert MU == 88753990
+    l8_max = 2 ** 29 - 1                                   # v < 2^261
+    assert l8_max * MU < 2 ** 64 and (l8_max * MU >> 48) < 2 ** 31      # the product and -(int32)q
+    # q <= l8·MU/2^48 <= (v/2^232)(2^280/N)/2^48 = v/N: r >= 0.  And with x = v/2^232: l8 > x - 1, MU > 2^280/N - 1, so
+    # l8·MU/2^48 > v/N - x/2^48 - 2^232/N, and the floor takes less than one more
+    short = 1 + Fr_(2 ** 29, 2 ** 48) + Fr_(2 ** 232, N_FR)
+    assert short < WEAK_OUT and WEAK_OUT * N_FR < 2 ** 256
+    # limb 8 of the result: int64 column sums of nine terms below 2^32 + 2^8·2^29 in magnitude
+    assert 2 ** 32 + (2 ** 8) * 2 ** 29 + 2 ** 36 < 2 ** 62
+    print("Fr   weak_reduce v < 2^261 = %.2f N -> r < %.7f N (contract: < %g N < 2^256 = %.2f N)  ok" % (RN, float(short), WEAK_OUT, PACKED))
+    return float(short)
+
+
+def dit29_plan(logn, tile_log):
+    """(ts, [S of every strided pass]) as wmap29.hip dit29 lays a transform out"""
+    ts = min(logn, tile_log)
+    rest = logn - ts
+    smax = 10 if tile_log == TS_BIG else 6
+    npass = (rest + smax - 1) // smax if rest else 0
+    out, done = [], 0
+    for p in range(npass):
+        S = (rest - done + (npass - p) - 1) // (npass - p)
+        assert 1 <= S <= smax and S <= ts
+        out.append(S)
+        done += S
+    assert done == rest
+    return ts, out
+
+
+def check_ntt_pass():
+    assert PACKED < 5.3
+    g = ntt_first_group(B(PACKED, 1.0))
+    print("Fr   ntt first group  packed < %.2f N -> < %.2f N" % (PACKED, g.V))
+    r4 = ntt_radix4(B(10.0, 1.0)).V - 10.0
+    r2 = ntt_radix2(B(10.0, 1.0)).V - 10.0
+    print("Fr   ntt radix-4 group adds %.2f N, radix-2 stage %.2f N; limbs before normalize below 5·2^29 / 3·2^29" % (r4, r2))
+    x1 = ntt_load1()
+    print("Fr   ntt LOAD 1       (a∘b - c)·vinv < %.3f N" % x1.V)
+    worst = (0.0, None)
+    worst_store = 0.0
+    per_stage_count = {}
+    for tile_log in (TS_SMALL, TS_BIG):
+        for logn in range(0, 29):
+            if tile_log == TS_BIG and logn <= TS_SMALL:
+                continue                                          # ntt_tile_log never takes the big tile there
+            ts, strided = dit29_plan(logn, tile_log)
+            passes = [("first", ts)] + [("strided", S) for S in strided]
+            for i, (kind, S) in enumerate(passes):
+                x = ntt_stages(B(PACKED if kind == "first" else WEAK_OUT, 1.0), S, kind == "first")
+                worst_store = max(worst_store, ntt_stores(x))
+                per_stage_count[(kind, S)] = x.V
+                if x.V > worst[0]:
+                    worst = (x.V, "logn %d, tile 2^%d, %s pass of %d stages" % (logn, tile_log, kind, S))
+    for (kind, S), v in sorted(per_stage_count.items()):
+        print("Fr   ntt %-7s pass, %2d stages: values < %.2f N" % (kind, S, v))
+    print("Fr   ntt largest value in any plan (logn 0..28, both tiles): %.2f N (%s); stores' products < %.3f N  ok" %
+          (worst[0], worst[1], worst_store))
+    return worst[0]
+
+
+def _lazy_sum(term, nterms, renorm_every, reduce_every=None):
+    """acc = Σ term with normalize every `renorm_every` terms (and weak_reduce every `reduce_every`); returns the largest (V, L)"""
+    acc = B(0.0, 0.0)
+    vmax = lmax = 0.0
+    for t in range(nterms):
+        acc = Fq.add(acc, term)
+        vmax, lmax = max(vmax, acc.V), max(lmax, acc.L)
+        if (t + 1) % renorm_every == 0:
+            acc = Fq.norm(acc)
+        if reduce_every and (t + 1) % reduce_every == 0:
+            assert acc.L <= 1.0 and acc.V * N_FR < 2.0 ** 261
+            acc = B(WEAK_OUT, 1.0)
+    assert Fq.norm(acc).V * N_FR < 2.0 ** 261            # weak_reduce(normalize(acc))
+    return vmax, lmax
+
+
+FOLD_REDUCE_EVERY = 64     # k_fold29: weak_reduce every 64th term
+
+
+def check_fold():
+    """k_fold29: acc += mul(a, T), a packed, T canonical; normalize every 4th term, weak_reduce every 64th"""
+    p = Fq.mul(B(PACKED, 1.0), B(1.0, 1.0))
+    assert p.V < 1.04
+    for terms in [2 ** k for k in range(1, 25)]:         # 2^logs terms, logs <= logD - 4
+        v, l = _lazy_sum(p, terms, 4, FOLD_REDUCE_EVERY)
+        assert l <= 5.0
+    print("Fr   k_fold29   products < %.3f N, sums < %.2f N for any number of terms, limbs <= %g·2^29  ok" % (p.V, v, l))
+
+
+def check_sell_accumulate():
+    """k_sell29: a piece's at most SELL_PIECE = 8 terms, each a packed value or its product by a canonical coefficient"""
+    raw = B(PACKED, 1.0)
+    prod = Fq.mul(raw, B(1.0, 1.0))
+    v, l = _lazy_sum(B(max(raw.V, prod.V), 1.0), 8, 4)
+    assert l <= 5.0, "limbs stay below 5·2^29"
+    print("Fr   k_sell29   terms < %.2f N, a piece < %.2f N, limbs <= %g·2^29  ok" % (raw.V, v, l))
+
+
 if __name__ == "__main__":
     check_signed()
     check_sat_row()
+    check_weak_reduce()
+    check_ntt_pass()
+    check_fold()
+    check_sell_accumulate()
     # invariant of stored accumulators (values in units of N) and the K constants of curve29.hpp
     INV = dict(x=13.0, y=8.0, z=3.0)
     KC = dict(KX=14, KY=9, K1=4, K2=6)
