@@ -33,6 +33,7 @@ CG_ERR_UNSATISFIED = -8
 CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
 CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED = 0, 1, 2      # PublicIOType, creds/src/structs.rs:33-37
 CG_SHOW_MADE, CG_SHOW_MALFORMED = 1, 2
+CG_RANGE_N_RAND, CG_RANGE_N_RESP = 18, 6
 
 
 class CrescentGpuError(RuntimeError):
@@ -249,6 +250,16 @@ _SIGNATURES = {
     "cg_show_respond_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                         C.c_void_p]),
     "cg_pvk_free": (None, [C.c_void_p]),
+    "cg_range_pk_load": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]),
+    "cg_range_pk_add_bases": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "cg_range_pk_free": (None, [C.c_void_p]),
+    "cg_range_pk_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "cg_range_commit_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "cg_range_quotient_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_range_open_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "cg_range_respond_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
@@ -1264,6 +1275,99 @@ class Groth16:
             out.append(ShowGroth16(rp[i].tobytes(), comh[i].tobytes(), cs[i], pok_s, [comm[i, j].tobytes() for j in range(n_com)]))
         return out
 
+    @staticmethod
+    def _range_rows(openings, rand, *challenges):
+        """the flat input arrays of a range proof call, checked against one another: (n, openings, rand, challenges...)"""
+        ob = _u8(openings)
+        if ob.size % 64:
+            raise ValueError("openings must be n x 64 bytes (m, r)")
+        n = ob.size // 64
+        return (n, ob, _u8(rand, 32 * CG_RANGE_N_RAND * n)) + tuple(_u8(c, 32 * n) for c in challenges)
+
+    @staticmethod
+    def range_commit_batch_packed(key: "RangeProofKey", slot: int, openings, rand):
+        """cg_range_commit_batch on flat byte arrays laid out as include/crescent_gpu.h states: the commitments of
+        `RangeProof::prove_n_bits` (creds/src/rangeproof.rs:114-339) before its first challenge.  Returns (com_f n x 64,
+        com_g n x 64, ts_out n x 4 x 32 [com_f, com_g, k_0, k_1 compressed], status n) as uint8 arrays."""
+        n, ob, rb = Groth16._range_rows(openings, rand)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        com_f, com_g, ts, status = np.zeros((m, 64), np.uint8), np.zeros((m, 64), np.uint8), np.zeros((m, 4, 32), np.uint8), np.zeros(m, np.uint8)
+        _check(lib().cg_range_commit_batch(key._h, slot, ptr(ob), ptr(rb), n, _ptr(com_f), _ptr(com_g), _ptr(ts), _ptr(status)))
+        return com_f[:n], com_g[:n], ts[:n], status[:n]
+
+    @staticmethod
+    def range_quotient_batch_packed(key: "RangeProofKey", openings, rand, c):
+        """cg_range_quotient_batch: com_q for the challenges c (n x 32 B).  Returns (com_q n x 64, ts_q n x 32, status n)."""
+        n, ob, rb, cb = Groth16._range_rows(openings, rand, c)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        com_q, ts_q, status = np.zeros((m, 64), np.uint8), np.zeros((m, 32), np.uint8), np.zeros(m, np.uint8)
+        _check(lib().cg_range_quotient_batch(key._h, ptr(ob), ptr(rb), ptr(cb), n, _ptr(com_q), _ptr(ts_q), _ptr(status)))
+        return com_q[:n], ts_q[:n], status[:n]
+
+    @staticmethod
+    def range_open_batch_packed(key: "RangeProofKey", openings, rand, c, rho):
+        """cg_range_open_batch: the evaluations and openings for the challenges c and rho (n x 32 B each).  Returns
+        (evals n x 3 x 32, proofs n x 3 x 96 [W uncompressed ‖ random_v], status n)."""
+        n, ob, rb, cb, hb = Groth16._range_rows(openings, rand, c, rho)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        evals, proofs, status = np.zeros((m, 3, 32), np.uint8), np.zeros((m, 3, 96), np.uint8), np.zeros(m, np.uint8)
+        _check(lib().cg_range_open_batch(key._h, ptr(ob), ptr(rb), ptr(cb), ptr(hb), n, _ptr(evals), _ptr(proofs), _ptr(status)))
+        return evals[:n], proofs[:n], status[:n]
+
+    @staticmethod
+    def range_respond_batch(openings, rand, c_dleq, status=None) -> np.ndarray:
+        """cg_range_respond_batch (host only): the DLEQ's responses s = nonce - c_dleq * secret (creds/src/dlog.rs:101-109),
+        n x 6 x 32 uint8: s_00, s_01, s_10..s_13.  status: cg_range_commit_batch's bytes, or None for "all made"."""
+        n, ob, rb, cb = Groth16._range_rows(openings, rand, c_dleq)
+        st = None if status is None else _u8(status, n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        out = np.zeros((max(n, 1), CG_RANGE_N_RESP, 32), np.uint8)
+        _check(lib().cg_range_respond_batch(ptr(ob), ptr(rb), ptr(cb), None if st is None else ptr(st), n, _ptr(out)))
+        return out[:n]
+
+    @staticmethod
+    def show_range_batch(key: "RangeProofKey", slot: int, openings, challenge, rand=None) -> List["RangeProof"]:
+        """`ClientState::show_range` (creds/src/groth16rand.rs:193-229) for n Pedersen openings (m, r) (ints) whose bases are
+        registered as `slot`: the three GPU calls with the caller's transcripts between them, then the responses.
+        challenge(phase, i, data) -> int is the host's Merlin: phase "dleq" gets showing i's 4 x 32 compressed com_f,
+        com_g, k_0, k_1 (creds/src/dlog.rs:56-99; the bases and y are the host's own), "c" the 2 x 32 com_f, com_g
+        (rangeproof.rs:250-257), "rho" the 32 bytes of com_q (:270-274).  This package ships no Merlin.  rand: per opening
+        its 18 scalars in the header's order; None draws them with `secrets.randbelow`.  A malformed opening raises
+        ValueError."""
+        n = len(openings)
+        if n == 0:
+            return []
+        if rand is None:
+            import secrets
+            rand = [[secrets.randbelow(FR_MODULUS) for _ in range(CG_RANGE_N_RAND)] for _ in range(n)]
+        fr = lambda v: int(v).to_bytes(32, "little")
+        ob = _u8(b"".join(fr(m) + fr(r) for m, r in openings))
+        rb = _u8(b"".join(fr(v) for row in rand for v in row))
+
+        def made(status, what):
+            bad = np.nonzero(status != CG_SHOW_MADE)[0]
+            if bad.size:
+                raise ValueError("opening %d is malformed (%s)" % (int(bad[0]), what))
+
+        com_f, com_g, ts, status = Groth16.range_commit_batch_packed(key, slot, ob, rb)
+        made(status, "m, r or a random scalar")
+        c_dleq = [int(challenge("dleq", i, ts[i])) for i in range(n)]
+        cs = [int(challenge("c", i, ts[i, :2])) for i in range(n)]
+        cb = _u8(b"".join(fr(v) for v in cs))
+        com_q, ts_q, status = Groth16.range_quotient_batch_packed(key, ob, rb, cb)
+        made(status, "the challenge c")
+        rhos = [int(challenge("rho", i, ts_q[i])) for i in range(n)]
+        evals, proofs, status = Groth16.range_open_batch_packed(key, ob, rb, cb, _u8(b"".join(fr(v) for v in rhos)))
+        made(status, "the challenge rho")
+        s = Groth16.range_respond_batch(ob, rb, _u8(b"".join(fr(v) for v in c_dleq)))
+        val = lambda a: int.from_bytes(a.tobytes(), "little")
+        return [RangeProof(com_f[i].tobytes(), com_g[i].tobytes(), val(evals[i, 0]), proofs[i, 0].tobytes(), val(evals[i, 1]),
+                           proofs[i, 1].tobytes(), com_q[i].tobytes(), val(evals[i, 2]), proofs[i, 2].tobytes(), c_dleq[i],
+                           [[val(s[i, j]) for j in range(2)], [val(s[i, j]) for j in range(2, 6)]]) for i in range(n)]
+
     @classmethod
     def clear_cache(cls):
         cls._cache.clear()
@@ -1302,6 +1406,82 @@ class PreparedVerifyingKey:
             self.close()
         except Exception:
             pass
+
+
+class RangeProofKey:
+    """`RangeProofPK` (creds/src/rangeproof.rs:26-29) from the bytes of range_pk.bin (creds/src/lib.rs:241), resident on a
+    GPU as fixed-base tables for proofs of n_bits bits (cg_range_pk_load).  Use as a context manager or close()."""
+
+    def __init__(self, range_pk_bytes, n_bits: int, device: int = -1):
+        b = _u8(range_pk_bytes)
+        self.n_bits = int(n_bits)
+        self._h = C.c_void_p()
+        _check(lib().cg_range_pk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, self.n_bits, device))
+
+    def add_bases(self, gamma_abc_point, delta_g1) -> int:
+        """registers the Pedersen bases of one range-checked input (2 x 64 B ark-serialize uncompressed G1) and returns
+        their slot (cg_range_pk_add_bases)"""
+        b = _u8(bytes(gamma_abc_point) + bytes(delta_g1), 128)
+        slot = C.c_uint32()
+        _check(lib().cg_range_pk_add_bases(self._h, _ptr(b), C.byref(slot)))
+        return int(slot.value)
+
+    def last_kernel_ms(self) -> Tuple[float, float]:
+        """(polynomial stage, fixed-base walks): HIP-event milliseconds of the last GPU call on this key"""
+        a, b = C.c_float(), C.c_float()
+        _check(lib().cg_range_pk_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().cg_range_pk_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@dataclass
+class RangeProof:
+    """creds/src/rangeproof.rs:82-93 as its serialized pieces: the commitments 64 B ark-serialize uncompressed G1, each
+    proof 96 B (W uncompressed ‖ random_v, as cg_range_open_batch writes it), the evaluations, dleq_c and the responses
+    dleq_s[statement][j] ints."""
+    com_f: bytes
+    com_g: bytes
+    eval_g: int
+    proof_g: bytes
+    eval_gw: int
+    proof_gw: bytes
+    com_q: bytes
+    eval_w_hat: int
+    proof_w_hat: bytes
+    dleq_c: int
+    dleq_s: List[List[int]]
+
+    def to_bytes(self) -> bytes:
+        """`serialize_uncompressed`, fields in the struct's order; kzg10::Proof is w ‖ Option<Fr> (tag 1, then random_v:
+        always Some here, include/crescent_gpu.h), DLogPoK is c ‖ s: Vec<Vec<Fr>>"""
+        u64 = lambda v: int(v).to_bytes(8, "little")
+        fr = lambda v: int(v).to_bytes(32, "little")
+
+        def proof(p):
+            p = bytes(p)
+            if len(p) != 96:
+                raise ValueError("a proof is 96 bytes: W, then random_v")
+            return p[:64] + b"\x01" + p[64:]
+
+        s = u64(len(self.dleq_s)) + b"".join(u64(len(si)) + b"".join(fr(x) for x in si) for si in self.dleq_s)
+        return (bytes(self.com_f) + bytes(self.com_g) + fr(self.eval_g) + proof(self.proof_g) + fr(self.eval_gw) + proof(self.proof_gw)
+                + bytes(self.com_q) + fr(self.eval_w_hat) + proof(self.proof_w_hat) + fr(self.dleq_c) + s)
 
 
 @dataclass

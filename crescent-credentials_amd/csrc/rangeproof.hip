@@ -1,0 +1,396 @@
+// Creating range proofs on the GPU: `ClientState::show_range` -> `RangeProof::prove_n_bits` (creds/src/rangeproof.rs:114-339)
+// for a batch of Pedersen openings under one KZG key, up to the three Merlin transcripts, which stay with the host, and
+// with every random scalar given by the caller.
+//
+// A cg_range_pk holds, on a device, fixed-base tables (fixed_base.hpp: 32 windows x 256 multiples) of powers_of_g[0..2n+3]
+// and powers_of_gamma_g[0..3] - the only powers prove_n_bits reaches: deg q = deg w^ = 2n + 3 - and, per registered slot,
+// of one pair of Pedersen bases.  Each of the three calls is stateless and runs three kernels per chunk of showings on the
+// handle's own non-blocking stream (a kernel pair, k_range_terms and k_range_sum, makes the points):
+//   k_range_poly    one wave per showing: the polynomial stage (rangepoly.hpp) with its vectors in LDS, lanes taking output
+//                   coefficients; the checks that make a showing CG_SHOW_MALFORMED; the scalar of every fixed-base term,
+//                   canonical, and in the open call the evaluations and the random_v
+//   k_range_terms   one lane per (showing, term): the term's scalar times its base by the 32-addition walk of fixed_base.hpp.
+//                   This is the hot path: 263 walks per proof at n = 32, the lanes of every wave but the last all busy
+//   k_range_sum     one lane per (showing, output point): the point's XYZZ partials summed with the general `add` (chosen
+//                   randomness makes partials coincide or cancel), affine, written as ark-serialize writes it
+// This is the arrangement of cg_show_commit_batch.  A fused kernel - one wave per (showing, point), the partials summed in a
+// tree through LDS and none of them in HBM - was built and measured beside it and lost: a point's 4, 2, 39, 69 or 71 terms
+// leave 38 - 56 % of such a wave's lanes walking, against all of them here (profiles/range_create.md).
+//   commit    com_f, com_g, k_0, k_1          n + 17 terms     (KZG10::commit, kzg10/mod.rs:178-241; dlog.rs:60-91)
+//   quotient  com_q                           2n + 7 terms     (rangeproof.rs:260-268)
+//   open      W of proof_g, proof_gw, proof_w^   4n + 15 terms (KZG10::open, kzg10/mod.rs:247-331)
+// cg_range_respond_batch, the DLEQ's responses once the host's transcript has produced its challenge, is host arithmetic.
+#include <memory>
+
+#include "ark_codec.hpp"
+#include "common.hpp"
+#include "fixed_base.hpp"
+#include "rangepoly.hpp"
+
+namespace cg {
+int translate_current_exception();
+}
+using namespace cg;
+
+namespace {
+
+constexpr uint64_t RCHUNK = 1u << 12;      // showings per launch set: 4n + 15 term scalars each in the open call
+constexpr int RWAVE = 64;
+constexpr uint32_t RP_SLOT = 0x80000000u;  // in tab_of: a table of the call's slot (0 or 1) instead of the key's
+constexpr uint32_t MAX_SLOTS = 64;
+enum { PH_COMMIT = 0, PH_QUOTIENT = 1, PH_OPEN = 2 };
+
+// One output point: terms [term0, term0 + n_terms) of a showing.  It goes to the showing's row of uncompressed buffer
+// `unc_buf` at word unc_at and / or to its row of the compressed buffer at word cmp_at (-1: not written).
+struct RpPoint {
+    uint32_t term0, n_terms;
+    int32_t unc_buf, unc_at, cmp_at;
+};
+struct RpShape {
+    uint32_t n_pts, n_terms;               // per showing
+    uint32_t unc_words[2], cmp_words;      // a showing's row in each output buffer
+    RpPoint pt[4];
+};
+
+struct WaveLane {
+    int lane;
+    static constexpr int nl = RWAVE;
+    __device__ void sync() const { __syncthreads(); }
+};
+
+template <int PHASE>
+__global__ __launch_bounds__(RWAVE) void k_range_poly(RangeConsts kc, const uint32_t* __restrict__ open, const uint32_t* __restrict__ rand,
+                                                     const uint32_t* __restrict__ c, const uint32_t* __restrict__ rho, uint64_t n,
+                                                     uint32_t n_terms, uint32_t* __restrict__ terms, uint32_t* __restrict__ evals,
+                                                     uint32_t* __restrict__ proofs, uint8_t* __restrict__ status) {
+    __shared__ RangeWork W;
+    const uint64_t p = blockIdx.x;
+    if (p >= n) return;
+    WaveLane ln{(int)threadIdx.x};
+    const RangeIn in{open + 16 * p, rand + 8 * RP_N_RAND * p, PHASE >= PH_QUOTIENT ? c + 8 * p : nullptr, PHASE == PH_OPEN ? rho + 8 * p : nullptr};
+    uint32_t* t = terms + 8 * p * n_terms;
+    bool made;                                                    // the same in every lane: it depends on the inputs alone
+    if (PHASE == PH_COMMIT) made = rp_commit(kc, in, W, t, ln);
+    else if (PHASE == PH_QUOTIENT) made = rp_quotient_call(kc, in, W, t, ln);
+    else made = rp_open(kc, in, W, t, evals + 24 * p, proofs + 72 * p, ln);
+    if (ln.lane == 0) status[p] = made ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+    if (PHASE == PH_OPEN && !made && ln.lane < 24) {
+        evals[24 * p + ln.lane] = 0;
+        proofs[72 * p + 24 * (ln.lane >> 3) + 16 + (ln.lane & 7)] = 0;
+    }
+}
+
+// one lane per (showing, term): the term's scalar times its base, from the table; nothing for a malformed showing
+__global__ __launch_bounds__(RWAVE) void k_range_terms(const RpShape* __restrict__ shape, const uint32_t* __restrict__ tab_of,
+                                                      const uint32_t* __restrict__ terms, const G1Affine* __restrict__ tab,
+                                                      const G1Affine* __restrict__ tab_slot, const uint8_t* __restrict__ status,
+                                                      uint64_t n, G1XYZZ* __restrict__ part) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nt = shape->n_terms;
+    if (g >= n * nt) return;
+    if (status[g / nt] != CG_SHOW_MADE) return;
+    const uint32_t of = tab_of[g % nt];
+    const G1Affine* tb = of & RP_SLOT ? tab_slot + (uint64_t)(of & ~RP_SLOT) * FB_NWIN * FB_WIN : tab + (uint64_t)of * FB_NWIN * FB_WIN;
+    part[g] = fixed_base_mul(tb, terms + 8 * g);
+}
+// one lane per (showing, output point): the partials summed with the general `add` (chosen randomness makes partials
+// coincide or cancel), affine, written as ark-serialize writes them; zeros for a malformed showing
+__global__ __launch_bounds__(RWAVE) void k_range_sum(const RpShape* __restrict__ shape, const uint8_t* __restrict__ status,
+                                                    uint64_t n, const G1XYZZ* __restrict__ part, uint32_t* __restrict__ unc0,
+                                                    uint32_t* __restrict__ unc1, uint32_t* __restrict__ cmp) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n_pts = shape->n_pts;
+    if (g >= n * n_pts) return;
+    const uint64_t p = g / n_pts;
+    const RpPoint* sg = &shape->pt[g % n_pts];
+    const bool made = status[p] == CG_SHOW_MADE;
+    uint32_t* u = sg->unc_buf < 0 ? nullptr : (sg->unc_buf ? unc1 : unc0) + p * shape->unc_words[sg->unc_buf] + sg->unc_at;
+    uint32_t* cw = sg->cmp_at < 0 ? nullptr : cmp + p * shape->cmp_words + sg->cmp_at;
+    if (!made) {
+        if (u) for (int l = 0; l < 16; ++l) u[l] = 0;
+        if (cw) for (int l = 0; l < 8; ++l) cw[l] = 0;
+        return;
+    }
+    G1XYZZ acc = G1XYZZ::inf();
+    for (uint32_t j = 0; j < sg->n_terms; ++j) add(acc, part[p * shape->n_terms + sg->term0 + j]);
+    const G1Affine a = to_affine(acc);
+    if (u) dev_put_g1(a, u, false);
+    if (cw) dev_put_g1(a, cw, true);
+}
+
+// the three calls' layouts for a domain of n: which table every term walks (the order rangepoly.hpp writes the scalars
+// in) and which terms make which point.  Tables 0..2n+3 are powers_of_g's, 2n+4..2n+7 powers_of_gamma_g's.
+void range_shapes(uint32_t n, RpShape sh[3], std::vector<uint32_t> tab_of[3]) {
+    const uint32_t G0 = 0, GAM = 2 * n + 4;
+    auto powers = [&](std::vector<uint32_t>& v, uint32_t n_g, uint32_t n_gam) {
+        for (uint32_t i = 0; i < n_g; ++i) v.push_back(G0 + i);
+        for (uint32_t i = 0; i < n_gam; ++i) v.push_back(GAM + i);
+    };
+    memset(sh, 0, 3 * sizeof(RpShape));
+    // commit: m f0 f1 f2 | g~ (n + 3), g0..g3 | t_m t_r | t_f0 t_f1 t_f2 t_m  ->  com_f, com_g, k_0, k_1
+    std::vector<uint32_t>& t0 = tab_of[PH_COMMIT];
+    t0 = {G0, GAM, GAM + 1, GAM + 2};
+    powers(t0, n + 3, 4);
+    t0.insert(t0.end(), {RP_SLOT | 0u, RP_SLOT | 1u, GAM, GAM + 1, GAM + 2, G0});
+    sh[PH_COMMIT] = {4, rp_commit_terms(n), {16, 16}, 32,
+                     {{0, 4, 0, 0, 0}, {4, n + 7, 1, 0, 8}, {n + 11, 2, -1, 0, 16}, {n + 13, 4, -1, 0, 24}}};
+    // quotient: q (2n + 4), q0 q1 q2  ->  com_q
+    powers(tab_of[PH_QUOTIENT], 2 * n + 4, 3);
+    sh[PH_QUOTIENT] = {1, rp_quotient_terms(n), {16, 0}, 8, {{0, 2 * n + 7, 0, 0, 0}}};
+    // open: per proof the witness quotient, then the blinded one; a proof is W (16 words) ‖ random_v (8)
+    powers(tab_of[PH_OPEN], n + 2, 3);
+    powers(tab_of[PH_OPEN], n + 2, 3);
+    powers(tab_of[PH_OPEN], 2 * n + 3, 2);
+    sh[PH_OPEN] = {3, rp_open_terms(n), {72, 0}, 0, {{0, n + 5, 0, 0, -1}, {n + 5, n + 5, 0, 24, -1}, {2 * n + 10, 2 * n + 5, 0, 48, -1}}};
+    for (int ph = 0; ph < 3; ++ph)
+        if (tab_of[ph].size() != sh[ph].n_terms) throw HipError(CG_ERR_HIP, "internal: range proof term layout");
+}
+
+}  // namespace
+
+struct cg_range_pk {
+    int device = 0;
+    uint32_t n_bits = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    float ms_poly = 0, ms_points = 0;      // of the last call, summed over its chunks
+    std::mutex mu;
+    RangeConsts kc;
+    RpShape shape[3];
+    DevBuf<G1Affine> tab;                  // powers_of_g[0..2n+3], then powers_of_gamma_g[0..3]
+    std::vector<DevBuf<G1Affine>> slots;   // per slot: the tables of its two Pedersen bases
+    DevBuf<RpShape> d_shape;               // the three calls' layouts
+    DevBuf<uint32_t> d_tab_of[3];
+    // per-call buffers, grown to the largest chunk seen; bytes are the caller's
+    DevBuf<uint8_t> b_open, b_rand, b_c, b_rho, b_terms, b_unc0, b_unc1, b_cmp, b_evals, b_status;
+    DevBuf<G1XYZZ> b_part;                 // one partial per (showing, term)
+    ~cg_range_pk() {
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+extern "C" int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes, uint64_t len, uint32_t n_bits, int32_t device) {
+    if (!out || !range_pk_bytes) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (n_bits != 2 && n_bits != 4 && n_bits != 8 && n_bits != 16 && n_bits != 32)
+        return fail(CG_ERR_INVALID_ARGUMENT, "n_bits = %u: prove_n_bits takes a power of two, and a value has at most 32 bits here", n_bits);
+    try {
+        // host only: every error of the bytes is reported before any HIP call
+        KeyRd r{range_pk_bytes, len, 0};
+        std::vector<G1Affine> pg(r.count(64)), bases(1, G1Affine::inf());
+        for (G1Affine& p : pg) p = r.g1();
+        std::vector<G1Affine> pgam(r.count(64));
+        for (G1Affine& p : pgam) p = r.g1();
+        if (r.off != len) throw HipError(CG_ERR_PARSE, "trailing bytes after the powers of a range proof key");
+        const uint32_t n = n_bits;
+        if (pg.size() < 2 * n + 4 || pgam.size() < 4)
+            return fail(CG_ERR_MALFORMED_KEY, "%llu powers of g and %llu of gamma_g: proofs of %u bits take %u and 4",
+                        (unsigned long long)pg.size(), (unsigned long long)pgam.size(), n, 2 * n + 4);
+        bases.insert(bases.end(), pg.begin(), pg.begin() + 2 * n + 4);         // build_tables skips the first entry
+        bases.insert(bases.end(), pgam.begin(), pgam.begin() + 4);
+        std::vector<G1Affine> tab;
+        build_tables(bases, tab);
+        std::unique_ptr<cg_range_pk> k(new cg_range_pk());
+        k->n_bits = n;
+        k->kc = range_consts((uint32_t)ilog2_ceil(n));
+        std::vector<uint32_t> tab_of[3];
+        range_shapes(n, k->shape, tab_of);
+        int dev = device;
+        if (dev < 0) CG_HIP(hipGetDevice(&dev));
+        CG_HIP(hipSetDevice(dev));
+        k->device = dev;
+        CG_HIP(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
+        for (hipEvent_t& e : k->ev) CG_HIP(hipEventCreate(&e));
+        k->tab.alloc(tab.size());
+        h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
+        k->d_shape.alloc(3);
+        h2d_sync(k->d_shape.p, k->shape, 3 * sizeof(RpShape), k->st);
+        for (int ph = 0; ph < 3; ++ph) {
+            k->d_tab_of[ph].alloc(tab_of[ph].size());
+            h2d_sync(k->d_tab_of[ph].p, tab_of[ph].data(), tab_of[ph].size() * sizeof(uint32_t), k->st);
+        }
+        *out = k.release();
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+// ark's checked deserialisation of one uncompressed G1 point on the host: flags, coordinates < q, the curve equation
+// (G1 has cofactor 1)
+static bool checked_g1(const uint8_t* b, G1Affine& p) {
+    const uint8_t f = b[63] & 0xC0;
+    if (f == 0xC0) return false;
+    uint8_t yb[32];
+    memcpy(yb, b + 32, 32);
+    yb[31] &= 0x3F;
+    const Fq x = fp_from_bytes<Fq>(b), y = fp_from_bytes<Fq>(yb);
+    if (!fp_is_canonical(x) || !fp_is_canonical(y)) return false;
+    if (f == 0x40) { p = G1Affine::inf(); return true; }
+    p = {to_mont(x), to_mont(y)};
+    return g1_on_curve(p);
+}
+
+extern "C" int cg_range_pk_add_bases(cg_range_pk* k, const uint8_t ped_bases[128], uint32_t* slot) {
+    if (!k || !ped_bases || !slot) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<G1Affine> bases(3, G1Affine::inf()), tab;
+    for (int i = 0; i < 2; ++i)
+        if (!checked_g1(ped_bases + 64 * i, bases[1 + i])) return fail(CG_ERR_INVALID_ARGUMENT, "Pedersen base %d is no valid G1 point", i);
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        if (k->slots.size() >= MAX_SLOTS) return fail(CG_ERR_INVALID_ARGUMENT, "all %u slots of this key are taken", MAX_SLOTS);
+        build_tables(bases, tab);
+        CG_HIP(hipSetDevice(k->device));
+        DevBuf<G1Affine> d(tab.size());
+        h2d_sync(d.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
+        k->slots.push_back(std::move(d));
+        *slot = (uint32_t)k->slots.size() - 1;
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+extern "C" void cg_range_pk_free(cg_range_pk* k) {
+    if (!k) return;
+    (void)hipSetDevice(k->device);
+    delete k;                    // the destructor waits for the handle's stream
+}
+
+// Diagnostic: what the two kernels of the handle's last GPU call took, by HIP events, summed over its chunks
+extern "C" int cg_range_pk_last_kernel_ms(cg_range_pk* k, float* poly_ms, float* points_ms) {
+    if (!k || !poly_ms || !points_ms) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(k->mu);
+    *poly_ms = k->ms_poly;
+    *points_ms = k->ms_points;
+    return CG_OK;
+}
+
+namespace {
+struct RpCall {
+    int phase;
+    uint32_t slot;
+    const uint8_t *open, *rand, *c, *rho;
+    uint64_t n;
+    uint8_t *unc0, *unc1, *cmp, *evals, *status;
+};
+
+int run_range(cg_range_pk* k, const RpCall& a) {
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        const G1Affine* tab_slot = nullptr;
+        if (a.phase == PH_COMMIT) {
+            if (a.slot >= k->slots.size()) return fail(CG_ERR_INVALID_ARGUMENT, "slot %u was not registered on this key (cg_range_pk_add_bases)", a.slot);
+            tab_slot = k->slots[a.slot].p;
+        }
+        if (a.n == 0) return CG_OK;
+        const bool null_in = !a.open || !a.rand || (a.phase >= PH_QUOTIENT && !a.c) || (a.phase == PH_OPEN && !a.rho);
+        const bool null_out = !a.unc0 || !a.status || (a.phase == PH_COMMIT && !a.unc1) || (a.phase != PH_OPEN && !a.cmp) || (a.phase == PH_OPEN && !a.evals);
+        if (null_in || null_out) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+        CG_HIP(hipSetDevice(k->device));
+        const RpShape& sh = k->shape[a.phase];
+        const uint64_t chunk = a.n < RCHUNK ? a.n : RCHUNK;
+        const uint64_t unc0_b = 4 * sh.unc_words[0], unc1_b = 4 * sh.unc_words[1], cmp_b = 4 * sh.cmp_words, ev_b = a.phase == PH_OPEN ? 96 : 0;
+        grow(k->b_open, chunk * 64);
+        grow(k->b_rand, chunk * 32 * RP_N_RAND);
+        grow(k->b_c, chunk * 32);
+        grow(k->b_rho, chunk * 32);
+        grow(k->b_terms, chunk * 32 * sh.n_terms);
+        grow(k->b_unc0, chunk * unc0_b);
+        grow(k->b_unc1, chunk * unc1_b + 16);
+        grow(k->b_cmp, chunk * cmp_b + 16);
+        grow(k->b_evals, chunk * ev_b + 16);
+        grow(k->b_status, chunk);
+        grow(k->b_part, chunk * sh.n_terms);
+        k->ms_poly = k->ms_points = 0;
+        for (uint64_t off = 0; off < a.n; off += chunk) {
+            const uint64_t m = a.n - off < chunk ? a.n - off : chunk;
+            rows_up(k->st, k->b_open, a.open, off, m, 64);
+            rows_up(k->st, k->b_rand, a.rand, off, m, 32 * RP_N_RAND);
+            if (a.phase >= PH_QUOTIENT) rows_up(k->st, k->b_c, a.c, off, m, 32);
+            if (a.phase == PH_OPEN) rows_up(k->st, k->b_rho, a.rho, off, m, 32);
+            const uint32_t *d_open = (const uint32_t*)k->b_open.p, *d_rand = (const uint32_t*)k->b_rand.p, *d_c = (const uint32_t*)k->b_c.p,
+                           *d_rho = (const uint32_t*)k->b_rho.p;
+            uint32_t *d_terms = (uint32_t*)k->b_terms.p, *d_ev = (uint32_t*)k->b_evals.p, *d_u0 = (uint32_t*)k->b_unc0.p;
+            CG_HIP(hipEventRecord(k->ev[0], k->st));
+            if (a.phase == PH_COMMIT)
+                k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.p);
+            else if (a.phase == PH_QUOTIENT)
+                k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.p);
+            else
+                k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.p);
+            CG_KERNEL_CHECK();
+            CG_HIP(hipEventRecord(k->ev[1], k->st));
+            k_range_terms<<<ceil_div(m * sh.n_terms, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + a.phase, k->d_tab_of[a.phase].p, d_terms, k->tab.p,
+                                                                                 tab_slot, k->b_status.p, m, k->b_part.p);
+            CG_KERNEL_CHECK();
+            k_range_sum<<<ceil_div(m * sh.n_pts, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + a.phase, k->b_status.p, m, k->b_part.p, d_u0,
+                                                                           (uint32_t*)k->b_unc1.p, (uint32_t*)k->b_cmp.p);
+            CG_KERNEL_CHECK();
+            CG_HIP(hipEventRecord(k->ev[2], k->st));
+            rows_down(k->st, a.unc0, k->b_unc0, off, m, unc0_b);
+            rows_down(k->st, a.unc1, k->b_unc1, off, m, unc1_b);
+            rows_down(k->st, a.cmp, k->b_cmp, off, m, cmp_b);
+            rows_down(k->st, a.evals, k->b_evals, off, m, ev_b);
+            rows_down(k->st, a.status, k->b_status, off, m, 1);
+            CG_HIP(hipStreamSynchronize(k->st));
+            float t0 = 0, t1 = 0;
+            CG_HIP(hipEventElapsedTime(&t0, k->ev[0], k->ev[1]));
+            CG_HIP(hipEventElapsedTime(&t1, k->ev[1], k->ev[2]));
+            k->ms_poly += t0;
+            k->ms_points += t1;
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+}  // namespace
+
+extern "C" int cg_range_commit_batch(cg_range_pk* k, uint32_t slot, const uint8_t* openings, const uint8_t* rand, uint64_t n,
+                                     uint8_t* com_f, uint8_t* com_g, uint8_t* ts_out, uint8_t* status) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    return run_range(k, RpCall{PH_COMMIT, slot, openings, rand, nullptr, nullptr, n, com_f, com_g, ts_out, nullptr, status});
+}
+
+extern "C" int cg_range_quotient_batch(cg_range_pk* k, const uint8_t* openings, const uint8_t* rand, const uint8_t* c, uint64_t n,
+                                       uint8_t* com_q, uint8_t* ts_q, uint8_t* status) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    return run_range(k, RpCall{PH_QUOTIENT, 0, openings, rand, c, nullptr, n, com_q, nullptr, ts_q, nullptr, status});
+}
+
+extern "C" int cg_range_open_batch(cg_range_pk* k, const uint8_t* openings, const uint8_t* rand, const uint8_t* c, const uint8_t* rho,
+                                   uint64_t n, uint8_t* evals, uint8_t* proofs, uint8_t* status) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    return run_range(k, RpCall{PH_OPEN, 0, openings, rand, c, rho, n, proofs, nullptr, nullptr, evals, status});
+}
+
+// DLogPoK::prove's responses (dlog.rs:101-109) for the DLEQ of a range proof (rangeproof.rs:226-245): statement 0 holds
+// (m, r) under the nonces (t_m, t_r), statement 1 (f0, f1, f2, m) under (t_f0, t_f1, t_f2, t_m).  Plain host arithmetic.
+extern "C" int cg_range_respond_batch(const uint8_t* openings, const uint8_t* rand, const uint8_t* c_dleq, const uint8_t* status,
+                                      uint64_t n, uint8_t* pok_s) {
+    if (n == 0) return CG_OK;
+    if (!openings || !rand || !c_dleq || !pok_s) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    static const int SECRET[RP_N_RESP] = {-1, -2, RP_F, RP_F + 1, RP_F + 2, -1};      // -1: m, -2: r, else a rand index
+    static const int NONCE[RP_N_RESP] = {RP_TM, RP_TR, RP_TF, RP_TF + 1, RP_TF + 2, RP_TM};
+    auto secret = [&](uint64_t p, int t) { return SECRET[t] < 0 ? openings + 64 * p + 32 * (-1 - SECRET[t]) : rand + 32 * (p * RP_N_RAND + SECRET[t]); };
+    auto nonce = [&](uint64_t p, int t) { return rand + 32 * (p * RP_N_RAND + NONCE[t]); };
+    for (uint64_t p = 0; p < n; ++p) {                            // every value first: an error writes nothing
+        if (status && status[p] != CG_SHOW_MADE) continue;
+        bool ok = scalar_is_canonical(c_dleq + 32 * p);
+        for (int t = 0; t < RP_N_RESP; ++t) ok = ok && scalar_is_canonical(secret(p, t)) && scalar_is_canonical(nonce(p, t));
+        if (!ok) return fail(CG_ERR_INVALID_ARGUMENT, "showing %llu: an opening, a rand scalar or c is not below the scalar modulus", (unsigned long long)p);
+    }
+    for (uint64_t p = 0; p < n; ++p) {
+        uint8_t* out = pok_s + 32 * RP_N_RESP * p;
+        if (status && status[p] != CG_SHOW_MADE) {
+            memset(out, 0, 32 * RP_N_RESP);
+            continue;
+        }
+        const Fr c = to_mont(fp_from_bytes<Fr>(c_dleq + 32 * p));            // c·R times a canonical x is c·x, canonical
+        for (int t = 0; t < RP_N_RESP; ++t)
+            fp_to_bytes(sub(fp_from_bytes<Fr>(nonce(p, t)), mul(c, fp_from_bytes<Fr>(secret(p, t)))), out + 32 * t);
+    }
+    return CG_OK;
+}

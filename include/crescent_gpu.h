@@ -697,6 +697,83 @@ int cg_show_commit_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, cons
 int cg_show_respond_batch(const uint8_t* io_types, uint64_t n_io, const uint8_t* inputs, const uint8_t* rand,
                           const uint8_t* pok_c, const uint8_t* status, uint64_t n, uint8_t* pok_s);
 void cg_pvk_free(cg_pvk* k);
+
+/* Creating range proofs: `ClientState::show_range` (creds/src/groth16rand.rs:193-229) -> `RangeProof::prove_n_bits`
+ * (creds/src/rangeproof.rs:114-339) for n Pedersen openings under one KZG key, the other half of a showing
+ * (creds/src/lib.rs:373, :471, :509), in three GPU calls around the host's Merlin transcripts and one host-only call.  As
+ * with showings the library draws no randomness and runs no transcript:
+ *
+ *               com_f, com_g, k_0, k_1 --> DLEQ transcript  --> c_dleq      (dlog.rs:56-99)
+ *   commit  --> com_f, com_g ------------> range transcript --> c           (rangeproof.rs:250-257)
+ *   quotient (c) --> com_q --------------> range transcript --> rho         (:270-274)
+ *   open (c, rho) --> eval_g, proof_g, eval_gw, proof_gw, eval_w_hat, proof_w_hat   (:277-325)
+ *   respond (c_dleq) --> s = nonce - c_dleq * secret                        (dlog.rs:101-109)
+ *
+ * The three GPU calls are stateless: each recomputes what it needs from openings, rand and the challenges, as
+ * cg_show_respond_batch re-reads its inputs; nothing is kept on the handle between calls ("Creating range
+ * proofs").
+ * openings: n x 2 x 32 B canonical Fr, `ped_open.m` and `ped_open.r` (dlog.rs:24-29).
+ * rand:     n x CG_RANGE_N_RAND x 32 B canonical Fr, in the order the reference draws them:
+ *   b0 b1 b2 (the blinding of g, rangeproof.rs:169-170) | f0 f1 f2 (rand_f, :216) | t_m t_r (the nonces of the DLEQ's
+ *   statement 0, dlog.rs:60-67) | t_f0 t_f1 t_f2 (of statement 1; its fourth nonce is t_m, eq_pos = (0, 3), and is not
+ *   supplied) | g0 g1 g2 g3 (rand_g, rangeproof.rs:248) | q0 q1 q2 (rand_q, :268)
+ * status:   n x CG_SHOW_MADE / CG_SHOW_MALFORMED, written by each call from its own inputs.  A malformed showing gets
+ *   zero bytes in every output of that call and leaves its neighbours alone.  Malformed: any scalar the call reads >= r;
+ *   m >= 2^n_bits (the reference asserts against it, groth16rand.rs:202-204); f0..f2 all zero, g0..g3 all zero or q0..q2
+ *   all zero (the reference would emit a non-hiding commitment and `random_v = None`); in cg_range_open_batch rho^n_bits
+ *   = 1, which covers rho = 1, where the reference divides by zero (rangeproof.rs:293).
+ * DEVIATION: `random_v` is always written.  The reference writes `None` for proof_w_hat only when f_coeff * rand_f +
+ *   q_coeff * rand_q cancels to the zero polynomial (kzg10/mod.rs:287-291); that showing is made here with random_v = 0 and
+ *   a W without hiding term, which is the same group element and evaluation.
+ * Argument errors (a null array, an unknown slot) are reported before any HIP call; n = 0 is CG_OK; calls on one handle
+ * serialise, different handles are independent. */
+typedef struct cg_range_pk cg_range_pk;
+enum { CG_RANGE_N_RAND = 18, CG_RANGE_N_RESP = 6 };
+/* Replaces: `read_from_file` of range_pk.bin (creds/src/lib.rs:241; `Powers`, forks/ark-poly-commit/src/kzg10/
+ *           data_structures.rs:144-176: u64 length and that many 64-byte ark-uncompressed G1 points for powers_of_g, then
+ *           the same for powers_of_gamma_g), read unchecked as the reference does, + the upload to a device (-1 = current)
+ *           of fixed-base tables of powers_of_g[0..2 n_bits + 3] and powers_of_gamma_g[0..3]: deg q = deg w_hat =
+ *           2 n_bits + 3, so these are all the powers prove_n_bits reaches (36 MB at n_bits = 32).
+ * Bytes that are not exactly that are CG_ERR_PARSE; n_bits outside {2, 4, 8, 16, 32} is CG_ERR_INVALID_ARGUMENT (the
+ * reference takes a power of two, RANGE_PROOF_INTERVAL_BITS = 32); fewer than 2 n_bits + 4 powers of g or 4 of gamma_g is
+ * CG_ERR_MALFORMED_KEY.  All of them are reported before any HIP call. */
+int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes, uint64_t len, uint32_t n_bits, int32_t device);
+/* Registers one pair of Pedersen bases - an input's `gamma_abc_g1[pos]` and `delta_g1` (groth16rand.rs:135-139, :319-323), 2 x 64 B
+ * ark-serialize uncompressed - builds their tables and returns the slot cg_range_commit_batch takes.  An mdl endpoint
+ * registers one pair per range-checked attribute; up to 64 slots.  A point that fails ark's checked G1 deserialisation
+ * is CG_ERR_INVALID_ARGUMENT. */
+int cg_range_pk_add_bases(cg_range_pk* k, const uint8_t ped_bases[128], uint32_t* slot);
+void cg_range_pk_free(cg_range_pk* k);
+/* Diagnostic: the HIP-event time of the two kernels (the polynomial stage, the fixed-base walks) of the handle's last GPU
+ * call, summed over its chunks.  (No counterpart in the reference.) */
+int cg_range_pk_last_kernel_ms(cg_range_pk* k, float* poly_ms, float* points_ms);
+/* Replaces: the commitments of prove_n_bits before its first challenge: `KZG10::commit` of f = m and of g blinded
+ *           (rangeproof.rs:143-172, :216, :248; kzg10/mod.rs:178-241) and the commitments k_0, k_1 of the DLEQ's
+ *           `DLogPoK::prove` (rangeproof.rs:218-245, dlog.rs:60-91), on the GPU.
+ * com_f, com_g: n x 64 B ark-serialize uncompressed.
+ * ts_out: n x 4 x 32 B ark-serialize COMPRESSED G1, the bytes `add_to_transcript` appends (utils.rs:29-37): com_f, com_g
+ *         (both transcripts' view of them), k_0 = t_m B_0 + t_r B_1 over the slot's bases, k_1 = t_f0 gamma_g[0] +
+ *         t_f1 gamma_g[1] + t_f2 gamma_g[2] + t_m g[0]. */
+int cg_range_commit_batch(cg_range_pk* k, uint32_t slot, const uint8_t* openings, const uint8_t* rand, uint64_t n,
+                          uint8_t* com_f, uint8_t* com_g, uint8_t* ts_out, uint8_t* status);
+/* Replaces: q1, q2, q3, q = q1 + c q2 + c^2 q3 and `KZG10::commit` of q (rangeproof.rs:183-213, :258-268).
+ * c: n x 32 B canonical Fr.  com_q: n x 64 B uncompressed;  ts_q: n x 32 B, com_q compressed. */
+int cg_range_quotient_batch(cg_range_pk* k, const uint8_t* openings, const uint8_t* rand, const uint8_t* c, uint64_t n,
+                            uint8_t* com_q, uint8_t* ts_q, uint8_t* status);
+/* Replaces: the three evaluations and `KZG10::open` calls of rangeproof.rs:277-325 (kzg10/mod.rs:247-331).
+ * c, rho: n x 32 B canonical Fr.  evals: n x 3 x 32 B: eval_g, eval_gw, eval_w_hat.  proofs: n x 3 x 96 B, each
+ * W (64 B uncompressed) ‖ random_v (32 B), for proof_g, proof_gw, proof_w_hat. */
+int cg_range_open_batch(cg_range_pk* k, const uint8_t* openings, const uint8_t* rand, const uint8_t* c, const uint8_t* rho,
+                        uint64_t n, uint8_t* evals, uint8_t* proofs, uint8_t* status);
+/* Replaces: the responses of the DLEQ's `DLogPoK::prove` (dlog.rs:101-109) once the host's transcript has produced
+ *           c_dleq.  Host only, on the calling thread, as cg_show_respond_batch: no handle, no HIP call.
+ * status: cg_range_commit_batch's bytes, or NULL for "all made"; a showing whose byte is not CG_SHOW_MADE is not read and
+ * gets zero bytes.  pok_s: n x CG_RANGE_N_RESP x 32 B: s_00, s_01 (secrets m, r), then s_10..s_13 (f0, f1, f2, m); s_13
+ * equals s_00.  A value >= r in a showing that is read, its c_dleq included, is CG_ERR_INVALID_ARGUMENT naming the
+ * showing, and nothing is written. */
+int cg_range_respond_batch(const uint8_t* openings, const uint8_t* rand, const uint8_t* c_dleq, const uint8_t* status,
+                           uint64_t n, uint8_t* pok_s);
+
 /* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
  * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the
  * PreparedVerifyingKey bytes (*len of them; pvk_out = NULL only reports *len).  A buffer shorter than *len is

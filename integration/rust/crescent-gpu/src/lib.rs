@@ -869,3 +869,130 @@ impl Drop for GpuVerifyingKey {
         unsafe { sys::cg_pvk_free(self.h) }
     }
 }
+
+/// A KZG key resident on the GPU for creating range proofs (`RangeProof::prove_n_bits`, creds/src/rangeproof.rs:114-339)
+/// in batches: three GPU calls around the host's transcripts, then the responses ("Creating range proofs").
+pub struct GpuRangeKey {
+    h: *mut sys::cg_range_pk,
+}
+unsafe impl Send for GpuRangeKey {}
+unsafe impl Sync for GpuRangeKey {} // calls on one handle serialise inside the library
+
+/// What `commit_batch` returns: com_f, com_g n x 64 B uncompressed; ts n x 4 x 32 B compressed (com_f, com_g, k_0, k_1)
+pub struct RangeCommitments {
+    pub com_f: Vec<u8>,
+    pub com_g: Vec<u8>,
+    pub ts: Vec<u8>,
+    pub status: Vec<u8>,
+}
+/// com_q n x 64 B uncompressed; ts_q n x 32 B compressed
+pub struct RangeQuotients {
+    pub com_q: Vec<u8>,
+    pub ts_q: Vec<u8>,
+    pub status: Vec<u8>,
+}
+/// evals n x 3 x 32 B (eval_g, eval_gw, eval_w_hat); proofs n x 3 x 96 B (W uncompressed, then random_v)
+pub struct RangeOpenings {
+    pub evals: Vec<u8>,
+    pub proofs: Vec<u8>,
+    pub status: Vec<u8>,
+}
+
+impl GpuRangeKey {
+    /// `range_pk_bytes`: range_pk.bin as `write_to_file` writes it (creds/src/lib.rs:241); `n_bits`: 32 in the product
+    pub fn load(range_pk_bytes: &[u8], n_bits: u32) -> Result<Self, SynthesisError> {
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe { sys::cg_range_pk_load(&mut h, range_pk_bytes.as_ptr(), range_pk_bytes.len() as u64, n_bits, -1) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(GpuRangeKey { h })
+    }
+
+    /// Registers the Pedersen bases of one range-checked input (groth16rand.rs:135-139) and returns their slot.
+    pub fn add_bases(&self, gamma_abc_point: &G1Affine, delta_g1: &G1Affine) -> Result<u32, SynthesisError> {
+        let mut b = Vec::with_capacity(128);
+        for p in [gamma_abc_point, delta_g1] {
+            p.serialize_uncompressed(&mut b).map_err(|_| SynthesisError::AssignmentMissing)?;
+        }
+        let mut slot = 0u32;
+        let rc = unsafe { sys::cg_range_pk_add_bases(self.h, b.as_ptr(), &mut slot) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(slot)
+    }
+
+    /// `openings`: n x (m, r); `rand`: n x 18 scalars in the header's order
+    pub fn commit_batch(&self, slot: u32, openings: &[Fr], rand: &[Fr]) -> Result<RangeCommitments, SynthesisError> {
+        let n = openings.len() / 2;
+        if openings.len() != 2 * n || rand.len() != n * sys::CG_RANGE_N_RAND {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (ob, rb) = (canonical_bytes(openings), canonical_bytes(rand));
+        let mut out = RangeCommitments { com_f: vec![0u8; n * 64], com_g: vec![0u8; n * 64], ts: vec![0u8; n * 128], status: vec![0u8; n] };
+        let rc = unsafe {
+            sys::cg_range_commit_batch(self.h, slot, ob.as_ptr(), rb.as_ptr(), n as u64, out.com_f.as_mut_ptr(), out.com_g.as_mut_ptr(),
+                                       out.ts.as_mut_ptr(), out.status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(out)
+    }
+
+    pub fn quotient_batch(&self, openings: &[Fr], rand: &[Fr], c: &[Fr]) -> Result<RangeQuotients, SynthesisError> {
+        let n = c.len();
+        if openings.len() != 2 * n || rand.len() != n * sys::CG_RANGE_N_RAND {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (ob, rb, cb) = (canonical_bytes(openings), canonical_bytes(rand), canonical_bytes(c));
+        let mut out = RangeQuotients { com_q: vec![0u8; n * 64], ts_q: vec![0u8; n * 32], status: vec![0u8; n] };
+        let rc = unsafe {
+            sys::cg_range_quotient_batch(self.h, ob.as_ptr(), rb.as_ptr(), cb.as_ptr(), n as u64, out.com_q.as_mut_ptr(),
+                                         out.ts_q.as_mut_ptr(), out.status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(out)
+    }
+
+    pub fn open_batch(&self, openings: &[Fr], rand: &[Fr], c: &[Fr], rho: &[Fr]) -> Result<RangeOpenings, SynthesisError> {
+        let n = c.len();
+        if openings.len() != 2 * n || rand.len() != n * sys::CG_RANGE_N_RAND || rho.len() != n {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (ob, rb, cb, hb) = (canonical_bytes(openings), canonical_bytes(rand), canonical_bytes(c), canonical_bytes(rho));
+        let mut out = RangeOpenings { evals: vec![0u8; n * 96], proofs: vec![0u8; n * 288], status: vec![0u8; n] };
+        let rc = unsafe {
+            sys::cg_range_open_batch(self.h, ob.as_ptr(), rb.as_ptr(), cb.as_ptr(), hb.as_ptr(), n as u64, out.evals.as_mut_ptr(),
+                                     out.proofs.as_mut_ptr(), out.status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(out)
+    }
+
+    /// The DLEQ's responses (dlog.rs:101-109): n x 6 canonical 32-byte scalars, s_00 s_01 | s_10..s_13.  Host arithmetic only.
+    pub fn respond_batch(openings: &[Fr], rand: &[Fr], c_dleq: &[Fr], status: &[u8]) -> Result<Vec<u8>, SynthesisError> {
+        let n = c_dleq.len();
+        if openings.len() != 2 * n || rand.len() != n * sys::CG_RANGE_N_RAND || status.len() != n {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (ob, rb, cb) = (canonical_bytes(openings), canonical_bytes(rand), canonical_bytes(c_dleq));
+        let mut s = vec![0u8; n * sys::CG_RANGE_N_RESP * 32];
+        let rc = unsafe { sys::cg_range_respond_batch(ob.as_ptr(), rb.as_ptr(), cb.as_ptr(), status.as_ptr(), n as u64, s.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(s)
+    }
+}
+
+impl Drop for GpuRangeKey {
+    fn drop(&mut self) {
+        unsafe { sys::cg_range_pk_free(self.h) }
+    }
+}

@@ -25,6 +25,8 @@ pub const CG_IO_HIDDEN: u8 = 1;
 pub const CG_IO_COMMITTED: u8 = 2;
 pub const CG_SHOW_MADE: u8 = 1;
 pub const CG_SHOW_MALFORMED: u8 = 2;
+pub const CG_RANGE_N_RAND: usize = 18;
+pub const CG_RANGE_N_RESP: usize = 6;
 
 #[repr(C)]
 pub struct cg_proving_key {
@@ -159,6 +161,7 @@ pub enum cg_partial {}
 pub enum cg_msm_ctx {}
 pub enum cg_qap_ctx {}
 pub enum cg_pvk {}
+pub enum cg_range_pk {}
 
 extern "C" {
     pub fn cg_init(n_devices: c_int, device_ids: *const c_int) -> c_int;
@@ -378,4 +381,54 @@ extern "C" {
         pok_s: *mut u8,
     ) -> c_int;
     pub fn cg_pvk_free(k: *mut cg_pvk);
+    pub fn cg_range_pk_load(
+        out: *mut *mut cg_range_pk,
+        range_pk_bytes: *const u8,
+        len: u64,
+        n_bits: u32,
+        device: i32,
+    ) -> c_int;
+    pub fn cg_range_pk_add_bases(k: *mut cg_range_pk, ped_bases: *const u8, slot: *mut u32) -> c_int;
+    pub fn cg_range_pk_free(k: *mut cg_range_pk);
+    pub fn cg_range_pk_last_kernel_ms(k: *mut cg_range_pk, poly_ms: *mut f32, points_ms: *mut f32) -> c_int;
+    pub fn cg_range_commit_batch(
+        k: *mut cg_range_pk,
+        slot: u32,
+        openings: *const u8,
+        rand: *const u8,
+        n: u64,
+        com_f: *mut u8,
+        com_g: *mut u8,
+        ts_out: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_range_quotient_batch(
+        k: *mut cg_range_pk,
+        openings: *const u8,
+        rand: *const u8,
+        c: *const u8,
+        n: u64,
+        com_q: *mut u8,
+        ts_q: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_range_open_batch(
+        k: *mut cg_range_pk,
+        openings: *const u8,
+        rand: *const u8,
+        c: *const u8,
+        rho: *const u8,
+        n: u64,
+        evals: *mut u8,
+        proofs: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_range_respond_batch(
+        openings: *const u8,
+        rand: *const u8,
+        c_dleq: *const u8,
+        status: *const u8,
+        n: u64,
+        pok_s: *mut u8,
+    ) -> c_int;
 }
