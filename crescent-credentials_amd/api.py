@@ -22,6 +22,7 @@ _LIB_PATH = os.environ.get("CRESCENT_GPU_LIB") or os.path.join(_HERE, "libcresce
 TUNING_LIB_PATH = os.path.join(_HERE, "libcrescent_gpu_tuning.so")
 
 FR_MODULUS = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+FQ_MODULUS = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
 CG_FORM_CANONICAL, CG_FORM_MONTGOMERY = 0, 1
 CG_FLAG_H_COEFFICIENT_BASIS = 1
 CG_FLAG_LATENCY_MODE, CG_FLAG_THROUGHPUT_MODE, CG_FLAG_SPIN_WAIT, CG_FLAG_CONTIGUOUS_H_SHARDS, CG_FLAG_H_SCALARS_EXTERNAL = 2, 4, 8, 16, 32
@@ -260,6 +261,11 @@ _SIGNATURES = {
     "cg_range_open_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     "cg_range_respond_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cg_range_vk_load": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]),
+    "cg_range_vk_add_bases": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "cg_range_vk_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "cg_range_vk_free": (None, [C.c_void_p]),
+    "cg_range_verify_batch": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint64, C.c_void_p, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
@@ -1368,6 +1374,59 @@ class Groth16:
                            proofs[i, 1].tobytes(), com_q[i].tobytes(), val(evals[i, 2]), proofs[i, 2].tobytes(), c_dleq[i],
                            [[val(s[i, j]) for j in range(2)], [val(s[i, j]) for j in range(2, 6)]]) for i in range(n)]
 
+    @staticmethod
+    def range_verify_batch_packed(vk: "RangeVerifyingKey", slot: int, ped_com, com_f, com_g, com_q, evals, proofs, c, rho, randomizers,
+                                  pok_c=None, pok_s=None):
+        """cg_range_verify_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = com_f / 64):
+        `RangeProof::verify_n_bits` (creds/src/rangeproof.rs:342-424) between its transcripts.  pok_c = None checks the
+        openings and the evaluation identity only (ped_com may then be None too).  Returns (verdicts n, k_out n x 2 x 32 or
+        None) as uint8 arrays."""
+        fb = _u8(com_f)
+        if fb.size % 64:
+            raise ValueError("com_f must be n x 64 bytes")
+        n = fb.size // 64
+        gb, qb, eb, pb = _u8(com_g, 64 * n), _u8(com_q, 64 * n), _u8(evals, 96 * n), _u8(proofs, 288 * n)
+        cb, hb, zb = _u8(c, 32 * n), _u8(rho, 32 * n), _u8(randomizers, 32 * n)
+        ptr = lambda a: _ptr(a) if a is not None and a.size else None
+        verdicts = np.zeros(max(n, 1), np.uint8)
+        cm = pc = ps = k = None
+        if pok_c is not None:
+            cm, pc, ps = _u8(ped_com, 64 * n), _u8(pok_c, 32 * n), _u8(pok_s, 32 * CG_RANGE_N_RESP * n)
+            k = np.zeros((max(n, 1), 2, 32), np.uint8)
+        _check(lib().cg_range_verify_batch(vk._h, slot, ptr(cm), ptr(fb), ptr(gb), ptr(qb), ptr(eb), ptr(pb), ptr(cb), ptr(hb), ptr(zb),
+                                           ptr(pc), ptr(ps), n, _ptr(verdicts), None if k is None else _ptr(k)))
+        return verdicts[:n], (None if k is None else k[:n])
+
+    @staticmethod
+    def verify_range_batch(vk: "RangeVerifyingKey", slot: int, ped_coms, proofs: List["RangeProof"], challenge, randomizers=None) -> List[bool]:
+        """`ShowRange::verify` (creds/src/groth16rand.rs) for n range proofs about the Pedersen commitments ped_coms (64 B
+        ark-serialize uncompressed G1 each) whose bases are registered as `slot`: the mirror of show_range_batch.
+        challenge(phase, i, data) -> int is the host's Merlin, called with the data show_range_batch passes: "c" gets the
+        2 x 32 compressed com_f, com_g, "rho" the 32 bytes of com_q, "dleq" the 4 x 32 com_f, com_g and the recomputed
+        k_0, k_1.  randomizers: per proof (r_1, r_2) below 2^128; None draws them with `secrets`.  Returns one bool per
+        proof: the verdict is CG_VERIFY_ACCEPT and the recomputed DLEQ challenge equals the proof's dleq_c."""
+        n = len(proofs)
+        if len(ped_coms) != n:
+            raise ValueError("one Pedersen commitment per proof")
+        if n == 0:
+            return []
+        if randomizers is None:
+            import secrets
+            randomizers = [(secrets.randbits(128), secrets.randbits(128)) for _ in range(n)]
+        fr = lambda v: int(v).to_bytes(32, "little")
+        join = lambda f: _u8(b"".join(f(p) for p in proofs))
+        cf, cg, cq = (np.stack([_g1_compress(getattr(p, name)) for p in proofs]) for name in ("com_f", "com_g", "com_q"))
+        cs = [int(challenge("c", i, np.stack([cf[i], cg[i]]))) for i in range(n)]
+        rhos = [int(challenge("rho", i, cq[i])) for i in range(n)]
+        verdicts, k = Groth16.range_verify_batch_packed(
+            vk, slot, _u8(b"".join(bytes(y) for y in ped_coms)), join(lambda p: bytes(p.com_f)), join(lambda p: bytes(p.com_g)),
+            join(lambda p: bytes(p.com_q)), join(lambda p: fr(p.eval_g) + fr(p.eval_gw) + fr(p.eval_w_hat)),
+            join(lambda p: bytes(p.proof_g) + bytes(p.proof_gw) + bytes(p.proof_w_hat)), _u8(b"".join(fr(v) for v in cs)),
+            _u8(b"".join(fr(v) for v in rhos)), _u8(b"".join(int(r).to_bytes(16, "little") for row in randomizers for r in row)),
+            join(lambda p: fr(p.dleq_c)), join(lambda p: b"".join(fr(x) for si in p.dleq_s for x in si)))
+        return [bool(verdicts[i] == CG_VERIFY_ACCEPT) and int(challenge("dleq", i, np.stack([cf[i], cg[i], k[i, 0], k[i, 1]]))) == int(proofs[i].dleq_c)
+                for i in range(n)]
+
     @classmethod
     def clear_cache(cls):
         cls._cache.clear()
@@ -1435,6 +1494,65 @@ class RangeProofKey:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             lib().cg_range_pk_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _g1_compress(unc) -> np.ndarray:
+    """ark-serialize's compressed form of an uncompressed G1 point: x with the SWFlags - a flag bit and no arithmetic
+    (the transcripts absorb commitments compressed, creds/src/utils.rs:29-37)"""
+    b = bytes(unc)
+    if len(b) != 64:
+        raise ValueError("an uncompressed G1 point is 64 bytes")
+    out = bytearray(b[:32])
+    if b[63] & 0x40:
+        out[31] |= 0x40
+    else:
+        y = int.from_bytes(b[32:63] + bytes([b[63] & 0x3F]), "little")
+        if y > FQ_MODULUS - y:
+            out[31] |= 0x80
+    return np.frombuffer(bytes(out), np.uint8)
+
+
+class RangeVerifyingKey:
+    """`RangeProofVK` (creds/src/rangeproof.rs:74-78) from the 640 bytes of range_vk.bin, resident on a GPU with h and
+    beta_h prepared and fixed-base tables of g, gamma_g and com_f_basis, for proofs of n_bits bits (cg_range_vk_load).
+    Use as a context manager or close()."""
+
+    def __init__(self, range_vk_bytes, n_bits: int, device: int = -1):
+        b = _u8(range_vk_bytes)
+        self.n_bits = int(n_bits)
+        self._h = C.c_void_p()
+        _check(lib().cg_range_vk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, self.n_bits, device))
+
+    def add_bases(self, gamma_abc_point, delta_g1) -> int:
+        """registers the Pedersen bases of one range-checked input (2 x 64 B ark-serialize uncompressed G1) and returns
+        their slot (cg_range_vk_add_bases)"""
+        b = _u8(bytes(gamma_abc_point) + bytes(delta_g1), 128)
+        slot = C.c_uint32()
+        _check(lib().cg_range_vk_add_bases(self._h, _ptr(b), C.byref(slot)))
+        return int(slot.value)
+
+    def last_kernel_ms(self) -> Tuple[float, float]:
+        """(group stage, pairing): HIP-event milliseconds of the last call on this key"""
+        a, b = C.c_float(), C.c_float()
+        _check(lib().cg_range_vk_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().cg_range_vk_free(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

@@ -1,5 +1,6 @@
-// What the entries that read and write ark-serialize on the device share (verify.hip, rangeproof.hip): the strict host
-// reader of a serialized key, the point codec of the kernels, and the per-call buffers' growth and row copies.
+// What the entries that read and write ark-serialize on the device share (verify.hip, rangeproof.hip, rangeverify.hip):
+// the strict host reader of a serialized key, the point codec of the kernels, and the per-call buffers' growth and row
+// copies.
 // For .hip files only.
 #pragma once
 #include "common.hpp"
@@ -65,6 +66,21 @@ struct KeyRd {
         return n;
     }
 };
+
+// ark's checked deserialisation of one uncompressed G1 point on the host (the Pedersen bases a range proof key registers):
+// flags, coordinates < q, the curve equation (G1 has cofactor 1)
+[[maybe_unused]] bool checked_g1(const uint8_t* b, G1Affine& p) {
+    const uint8_t f = b[63] & 0xC0;
+    if (f == 0xC0) return false;
+    uint8_t yb[32];
+    memcpy(yb, b + 32, 32);
+    yb[31] &= 0x3F;
+    const Fq x = fp_from_bytes<Fq>(b), y = fp_from_bytes<Fq>(yb);
+    if (!fp_is_canonical(x) || !fp_is_canonical(y)) return false;
+    if (f == 0x40) { p = G1Affine::inf(); return true; }
+    p = {to_mont(x), to_mont(y)};
+    return g1_on_curve(p);
+}
 
 // ---- device side: ark-serialize points, read (checked, or unchecked for the chains) and written ---------------------------
 __device__ __forceinline__ bool limbs_below(const uint32_t a[8], const uint32_t n[8]) {

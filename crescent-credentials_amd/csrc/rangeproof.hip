@@ -217,21 +217,6 @@ extern "C" int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes
     }
 }
 
-// ark's checked deserialisation of one uncompressed G1 point on the host: flags, coordinates < q, the curve equation
-// (G1 has cofactor 1)
-static bool checked_g1(const uint8_t* b, G1Affine& p) {
-    const uint8_t f = b[63] & 0xC0;
-    if (f == 0xC0) return false;
-    uint8_t yb[32];
-    memcpy(yb, b + 32, 32);
-    yb[31] &= 0x3F;
-    const Fq x = fp_from_bytes<Fq>(b), y = fp_from_bytes<Fq>(yb);
-    if (!fp_is_canonical(x) || !fp_is_canonical(y)) return false;
-    if (f == 0x40) { p = G1Affine::inf(); return true; }
-    p = {to_mont(x), to_mont(y)};
-    return g1_on_curve(p);
-}
-
 extern "C" int cg_range_pk_add_bases(cg_range_pk* k, const uint8_t ped_bases[128], uint32_t* slot) {
     if (!k || !ped_bases || !slot) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     std::vector<G1Affine> bases(3, G1Affine::inf()), tab;

@@ -1,0 +1,386 @@
+// Verifying range proofs on the GPU: `ShowRange::verify` -> `RangeProof::verify_n_bits` (creds/src/rangeproof.rs:342-424)
+// for a batch of proofs under one `RangeProofVK`, up to the Merlin transcripts, which stay with the host (c and rho come
+// in, the DLEQ's recomputed commitments go out), and with the two randomizers of `KZG10::batch_check` given by the caller.
+//
+// A cg_range_vk holds, on a device, the 91 line coefficients of prepared h and of prepared beta_h, fixed-base tables
+// (fixed_base.hpp) of g, gamma_g and the four com_f_basis points and, per registered slot, of one pair of Pedersen bases.
+// cg_range_verify_batch runs five kernels per chunk of showings on the handle's own non-blocking stream.  Scalars and
+// partials are laid out TERM-MAJOR within the chunk (term t of showing p at t·m + p), so that a wave holds one kind of term:
+// one table for a fixed-base wave, one chain length for a variable-base wave.
+//   k_rv_check    one lane per showing: the scalar stage (rangeverify.hpp: range checks, rho^n, one inversion, the identity
+//                 and eq_pos bits, the ten merged term scalars) and ark's checked deserialisation of the seven points
+//                                                                                                     -> one flag byte
+//   k_rv_terms    one lane per (term, showing): the fixed-base terms (Σ r_i v_i)·g, (Σ r_i random_v_i)·gamma_g and, with a
+//                 DLEQ, the six responses on the slot's bases and com_f_basis, from the tables; then, in workgroups of their
+//                 own, the variable-base chains: eight of batch_check, c_dleq·ped_com and c_dleq·com_f.  A chain is as long
+//                 as its scalar: 128 doublings for r_1·W_gw and r_2·W_w^, 129 for (1 + r_1)·com_g, 254 for the rest
+//                                                                                                     -> XYZZ partials
+//   k_rv_sum      one lane per (output point, showing): total_c, -total_w (affine, for the pairing), k_0 and k_1 (ark-serialize
+//                 compressed, what the transcript absorbs under b"k").  The general `add` throughout: chosen proofs make
+//                 partials coincide or cancel
+//   k_rv_miller   one lane per showing: multi_miller_loop<0> over (-total_w, prepared beta_h), (total_c, prepared h); a pair
+//                 whose G1 point is O, or whose key point is, is dropped as ark's multi_miller_loop drops it
+//   k_rv_final    one lane per showing: final exponentiation, == one, and the two bits               -> one verdict byte
+// A malformed showing costs nothing after k_rv_check: every later lane of it returns at once.
+#include <memory>
+
+#include "ark_codec.hpp"
+#include "common.hpp"
+#include "fixed_base.hpp"
+#include "pairing.hpp"
+#include "rangeverify.hpp"
+
+namespace cg {
+int translate_current_exception();
+}
+using namespace cg;
+
+namespace {
+
+// showings per launch set.  A call is bound by latency, not by width: the pairing kernels hold one wave per SIMD, so the
+// chip takes 65536 showings side by side and a chunk of 1 and one of 4096 take the same 46 ms (profiles/range_verify.md);
+// chunks run one after the other, so a chunk is as large as cg_verify_batch's.  4 KB of device memory per showing.
+constexpr uint64_t RVCHUNK = 1u << 15;
+constexpr int RVBLOCK = 64;
+constexpr int NC = PairingConsts::N_COEFFS;
+constexpr uint32_t MAX_SLOTS = 64;
+constexpr uint32_t RV_VK_BYTES = 640;      // g | gamma_g | h | beta_h | com_f_basis[4]
+// the key's tables: g, gamma_g, then com_f_basis
+enum { TAB_G = 0, TAB_GAMMA_G = 1, TAB_CFB = 2, N_TABS = 6 };
+constexpr uint32_t N_FIX_DLEQ = RP_N_RESP, N_VAR_DLEQ = 2;
+
+// one call's arrays on the device, as the caller laid them out
+struct RvArgs {
+    const uint32_t *ped_com, *com_f, *com_g, *com_q;      // 16 words per showing
+    const uint32_t *evals, *proofs;                       // 24, 72
+    const uint32_t *c, *rho, *rz;                         // 8, 8, 8
+    const uint32_t *pok_c, *pok_s;                        // 8, 48; null without a DLEQ
+    uint64_t m;
+    uint32_t n_fixed, n_var;                              // 2 + 6, 8 + 2 with a DLEQ
+};
+
+__global__ __launch_bounds__(RVBLOCK) void k_rv_check(RangeConsts kc, RvArgs a, uint32_t* __restrict__ scal, uint8_t* __restrict__ flags) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.m) return;
+    const RvIn in{a.evals + 24 * p, a.proofs + 72 * p, a.c + 8 * p, a.rho + 8 * p, a.rz + 8 * p,
+                  a.pok_c ? a.pok_c + 8 * p : nullptr, a.pok_c ? a.pok_s + 48 * p : nullptr};
+    uint32_t f = rv_scalars(kc, in, scal + 8 * p, a.m);
+    bool ok = true;
+    (void)dev_g1(a.com_f + 16 * p, ok);
+    (void)dev_g1(a.com_g + 16 * p, ok);
+    (void)dev_g1(a.com_q + 16 * p, ok);
+    for (int j = 0; j < 3; ++j) (void)dev_g1(a.proofs + 72 * p + 24 * j, ok);
+    if (a.pok_c) (void)dev_g1(a.ped_com + 16 * p, ok);            // without a DLEQ the commitment is not read
+    if (!ok) f = RV_MALFORMED;
+    flags[p] = (uint8_t)f;
+}
+
+// k·y for an affine y and k < 2^bits: `bits` doublings, each followed by a mixed addition where the bit is set
+__device__ __forceinline__ G1XYZZ chain_mul(const G1Affine& y, const uint32_t* k, int bits) {
+    G1XYZZ acc = G1XYZZ::inf();
+    for (int b = bits - 1; b >= 0; --b) {
+        acc = dbl(acc);
+        if ((k[b >> 5] >> (b & 31)) & 1u) madd(acc, y);
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(RVBLOCK) void k_rv_terms(RvArgs a, const uint32_t* __restrict__ scal, const uint8_t* __restrict__ flags,
+                                                     const G1Affine* __restrict__ tab, const G1Affine* __restrict__ tab_slot,
+                                                     G1XYZZ* __restrict__ part) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t m = a.m, n_fixed_lanes = m * a.n_fixed;
+    if (g < n_fixed_lanes) {
+        const uint32_t t = (uint32_t)(g / m);
+        const uint64_t p = g % m;
+        if (flags[p] & RV_MALFORMED) return;
+        const uint32_t* x;
+        const G1Affine* tb;
+        if (t < RV_N_FIX_KZG) {
+            x = scal + 8 * ((RV_N_VAR_KZG + t) * m + p);
+            tb = tab + (uint64_t)(TAB_G + t) * FB_NWIN * FB_WIN;
+        } else {                                                  // s_00 s_01 on the slot's bases, s_10..s_13 on com_f_basis
+            const uint32_t j = t - RV_N_FIX_KZG;
+            x = a.pok_s + 8 * (RP_N_RESP * p + j);
+            tb = j < 2 ? tab_slot + (uint64_t)j * FB_NWIN * FB_WIN : tab + (uint64_t)(TAB_CFB + j - 2) * FB_NWIN * FB_WIN;
+        }
+        part[g] = fixed_base_mul(tb, x);
+        return;
+    }
+    // the variable-base lanes (chains several times as long) start at a workgroup of their own
+    const uint64_t var_at = (n_fixed_lanes + RVBLOCK - 1) / RVBLOCK * RVBLOCK;
+    if (g < var_at || g - var_at >= m * a.n_var) return;
+    const uint64_t v = g - var_at;
+    const uint32_t t = (uint32_t)(v / m);
+    const uint64_t p = v % m;
+    if (flags[p] & RV_MALFORMED) return;
+    const uint32_t *pt, *k;
+    int bits = 254;
+    if (t < RV_N_VAR_KZG) {
+        k = scal + 8 * (t * m + p);
+        bits = rv_scalar_bits((int)t);
+        pt = t == RV_COM_G ? a.com_g + 16 * p : t == RV_COM_F ? a.com_f + 16 * p : t == RV_COM_Q ? a.com_q + 16 * p
+             : a.proofs + 72 * p + 24 * (t == RV_W_G ? 0 : (t == RV_W_GW || t == RV_TW_GW) ? 1 : 2);
+    } else {                                                      // c_dleq·y_i: y = [ped_com, com_f]  (c < r < 2^254)
+        k = a.pok_c + 8 * p;
+        pt = t == RV_N_VAR_KZG ? a.ped_com + 16 * p : a.com_f + 16 * p;
+    }
+    part[(a.n_fixed + t) * m + p] = chain_mul(dev_g1_unchecked(pt), k, bits);
+}
+
+__global__ __launch_bounds__(RVBLOCK) void k_rv_sum(RvArgs a, const uint8_t* __restrict__ flags, const G1XYZZ* __restrict__ part,
+                                                   G1Affine* __restrict__ pair_pts, uint32_t* __restrict__ k_out) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t m = a.m;
+    const uint32_t n_out = a.pok_c ? 4 : 2;
+    if (g >= m * n_out) return;
+    const uint32_t o = (uint32_t)(g / m);
+    const uint64_t p = g % m;
+    const bool bad = flags[p] & RV_MALFORMED;
+    auto fixed = [&](uint32_t t) { return part[t * m + p]; };
+    auto var = [&](uint32_t t) { return part[(a.n_fixed + t) * m + p]; };
+    if (o < 2) {
+        if (bad) return;                                          // k_rv_miller does not read it
+        G1XYZZ acc;
+        if (o == 0) {                                             // total_c (kzg10/mod.rs:377-393)
+            acc = var(RV_COM_G);
+            for (uint32_t t = RV_COM_F; t <= RV_W_W; ++t) add(acc, var(t));
+            add(acc, neg(fixed(0)));
+            add(acc, neg(fixed(1)));
+        } else {                                                  // -total_w (:397)
+            acc = G1XYZZ::from_affine(dev_g1_unchecked(a.proofs + 72 * p));
+            add(acc, var(RV_TW_GW));
+            add(acc, var(RV_TW_W));
+            acc = neg(acc);
+        }
+        pair_pts[o * m + p] = to_affine(acc);
+        return;
+    }
+    uint32_t* out = k_out + 8 * (2 * p + (o - 2));
+    if (bad) {
+        for (int l = 0; l < 8; ++l) out[l] = 0;
+        return;
+    }
+    // k_0 = s_00 B_0 + s_01 B_1 + c ped_com;  k_1 = Σ s_1j com_f_basis[j] + c com_f  (dlog.rs:135-145)
+    G1XYZZ acc = var(RV_N_VAR_KZG + (o - 2));
+    const uint32_t lo = o == 2 ? RV_N_FIX_KZG : RV_N_FIX_KZG + 2, hi = o == 2 ? RV_N_FIX_KZG + 2 : RV_N_FIX_KZG + RP_N_RESP;
+    for (uint32_t t = lo; t < hi; ++t) add(acc, fixed(t));
+    dev_put_g1(to_affine(acc), out, true);
+}
+
+__global__ __launch_bounds__(RVBLOCK) void k_rv_miller(const G1Affine* __restrict__ pair_pts, const uint8_t* __restrict__ flags, uint64_t m,
+                                                      const EllCoeff* beta_h_c, const EllCoeff* h_c, int beta_h_live, int h_live,
+                                                      Fq12* __restrict__ f) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m || (flags[p] & RV_MALFORMED)) return;
+    MillerPairs mp;
+    mp.p[0] = pair_pts[m + p]; mp.q[0] = G2Affine::inf(); mp.tab[0] = beta_h_c; mp.live[0] = !mp.p[0].is_inf() && beta_h_live;
+    mp.p[1] = pair_pts[p]; mp.q[1] = G2Affine::inf(); mp.tab[1] = h_c; mp.live[1] = !mp.p[1].is_inf() && h_live;
+    mp.p[2] = G1Affine::inf(); mp.q[2] = G2Affine::inf(); mp.tab[2] = nullptr; mp.live[2] = false;
+    f[p] = multi_miller_loop<0>(mp);
+}
+
+__global__ __launch_bounds__(RVBLOCK) void k_rv_final(const Fq12* __restrict__ f, const uint8_t* __restrict__ flags, uint64_t m,
+                                                     uint8_t* __restrict__ verdict) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t fl = flags[p];
+    if (fl & RV_MALFORMED) {
+        verdict[p] = CG_VERIFY_MALFORMED;
+        return;
+    }
+    Fq12 r;
+    const bool some = final_exponentiation(f[p], r);
+    const bool ok = some && r == Fq12::one() && (fl & RV_IDENTITY) && (fl & RV_EQ_POS);
+    verdict[p] = ok ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
+}
+
+}  // namespace
+
+struct cg_range_vk {
+    int device = 0;
+    uint32_t n_bits = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    float ms_group = 0, ms_pairing = 0;    // of the last call, summed over its chunks
+    std::mutex mu;
+    RangeConsts kc;
+    int h_live = 0, beta_h_live = 0;
+    DevBuf<EllCoeff> h_c, beta_h_c;        // prepared h, prepared beta_h
+    DevBuf<G1Affine> tab;                  // g, gamma_g, com_f_basis[0..3]
+    std::vector<DevBuf<G1Affine>> slots;   // per slot: the tables of its two Pedersen bases
+    // per-call buffers, grown to the largest chunk seen; bytes are the caller's
+    DevBuf<uint8_t> b_ped, b_comf, b_comg, b_comq, b_evals, b_proofs, b_c, b_rho, b_rz, b_pokc, b_poks, b_k, b_flags, b_verdict;
+    DevBuf<uint32_t> b_scal;               // RV_N_SCALARS per showing, term-major
+    DevBuf<G1XYZZ> b_part;                 // one partial per (term, showing)
+    DevBuf<G1Affine> b_pair;               // total_c, then -total_w
+    DevBuf<Fq12> b_miller;
+    ~cg_range_vk() {
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
+extern "C" int cg_range_vk_load(cg_range_vk** out, const uint8_t* range_vk_bytes, uint64_t len, uint32_t n_bits, int32_t device) {
+    if (!out || !range_vk_bytes) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (n_bits != 2 && n_bits != 4 && n_bits != 8 && n_bits != 16 && n_bits != 32)
+        return fail(CG_ERR_INVALID_ARGUMENT, "n_bits = %u: verify_n_bits takes a power of two, and a value has at most 32 bits here", n_bits);
+    try {
+        // host only: every error of the bytes is reported before any HIP call
+        if (len != RV_VK_BYTES)
+            throw HipError(CG_ERR_PARSE, "a range proof verifying key is 640 bytes: g, gamma_g, h, beta_h and the four points of com_f_basis");
+        KeyRd r{range_vk_bytes, len, 0};
+        std::vector<G1Affine> bases(1 + N_TABS, G1Affine::inf());                // build_tables skips the first entry
+        bases[1 + TAB_G] = r.g1();
+        bases[1 + TAB_GAMMA_G] = r.g1();
+        const G2Affine h = r.g2(), beta_h = r.g2();
+        for (int i = 0; i < 4; ++i) bases[1 + TAB_CFB + i] = r.g1();
+        std::vector<G1Affine> tab;
+        build_tables(bases, tab);
+        // G2Prepared::from, as the reference's deserialiser computes it (kzg10/data_structures.rs:246-264); O is marked
+        std::vector<EllCoeff> h_c(NC), beta_h_c(NC);
+        if (!h.is_inf()) g2_prepare(h, h_c.data());
+        if (!beta_h.is_inf()) g2_prepare(beta_h, beta_h_c.data());
+        std::unique_ptr<cg_range_vk> k(new cg_range_vk());
+        k->n_bits = n_bits;
+        k->kc = range_consts((uint32_t)ilog2_ceil(n_bits));
+        k->h_live = !h.is_inf();
+        k->beta_h_live = !beta_h.is_inf();
+        int dev = device;
+        if (dev < 0) CG_HIP(hipGetDevice(&dev));
+        CG_HIP(hipSetDevice(dev));
+        k->device = dev;
+        CG_HIP(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
+        for (hipEvent_t& e : k->ev) CG_HIP(hipEventCreate(&e));
+        k->tab.alloc(tab.size());
+        h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
+        k->h_c.alloc(NC);
+        k->beta_h_c.alloc(NC);
+        h2d_sync(k->h_c.p, h_c.data(), NC * sizeof(EllCoeff), k->st);
+        h2d_sync(k->beta_h_c.p, beta_h_c.data(), NC * sizeof(EllCoeff), k->st);
+        *out = k.release();
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+extern "C" int cg_range_vk_add_bases(cg_range_vk* k, const uint8_t ped_bases[128], uint32_t* slot) {
+    if (!k || !ped_bases || !slot) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<G1Affine> bases(3, G1Affine::inf()), tab;
+    for (int i = 0; i < 2; ++i)
+        if (!checked_g1(ped_bases + 64 * i, bases[1 + i])) return fail(CG_ERR_INVALID_ARGUMENT, "Pedersen base %d is no valid G1 point", i);
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        if (k->slots.size() >= MAX_SLOTS) return fail(CG_ERR_INVALID_ARGUMENT, "all %u slots of this key are taken", MAX_SLOTS);
+        build_tables(bases, tab);
+        CG_HIP(hipSetDevice(k->device));
+        DevBuf<G1Affine> d(tab.size());
+        h2d_sync(d.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
+        k->slots.push_back(std::move(d));
+        *slot = (uint32_t)k->slots.size() - 1;
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+extern "C" void cg_range_vk_free(cg_range_vk* k) {
+    if (!k) return;
+    (void)hipSetDevice(k->device);
+    delete k;                    // the destructor waits for the handle's stream
+}
+
+// Diagnostic: what the kernels of the handle's last call took, by HIP events, summed over its chunks: the group stage
+// (k_rv_check, k_rv_terms, k_rv_sum) and the pairing (k_rv_miller, k_rv_final)
+extern "C" int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms) {
+    if (!k || !group_ms || !pairing_ms) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::mutex> lk(k->mu);
+    *group_ms = k->ms_group;
+    *pairing_ms = k->ms_pairing;
+    return CG_OK;
+}
+
+extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
+                                     const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c,
+                                     const uint8_t* rho, const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s,
+                                     uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        if (slot >= k->slots.size()) return fail(CG_ERR_INVALID_ARGUMENT, "slot %u was not registered on this key (cg_range_vk_add_bases)", slot);
+        if (n == 0) return CG_OK;
+        const bool pok = pok_c != nullptr;
+        if (!com_f || !com_g || !com_q || !evals || !proofs || !c || !rho || !randomizers || !verdicts ||
+            (pok && (!ped_com || !pok_s || !k_out)))
+            return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t chunk = n < RVCHUNK ? n : RVCHUNK;
+        const uint32_t n_fixed = RV_N_FIX_KZG + (pok ? N_FIX_DLEQ : 0), n_var = RV_N_VAR_KZG + (pok ? N_VAR_DLEQ : 0);
+        grow(k->b_ped, chunk * 64);
+        grow(k->b_comf, chunk * 64);
+        grow(k->b_comg, chunk * 64);
+        grow(k->b_comq, chunk * 64);
+        grow(k->b_evals, chunk * 96);
+        grow(k->b_proofs, chunk * 288);
+        grow(k->b_c, chunk * 32);
+        grow(k->b_rho, chunk * 32);
+        grow(k->b_rz, chunk * 32);
+        grow(k->b_pokc, chunk * 32);
+        grow(k->b_poks, chunk * 32 * RP_N_RESP);
+        grow(k->b_k, chunk * 64);
+        grow(k->b_flags, chunk);
+        grow(k->b_verdict, chunk);
+        grow(k->b_scal, chunk * 8 * RV_N_SCALARS);
+        grow(k->b_part, chunk * (uint64_t)(RV_N_FIX_KZG + N_FIX_DLEQ + RV_N_VAR_KZG + N_VAR_DLEQ));
+        grow(k->b_pair, chunk * 2);
+        grow(k->b_miller, chunk);
+        k->ms_group = k->ms_pairing = 0;
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            if (pok) {
+                rows_up(k->st, k->b_ped, ped_com, off, m, 64);
+                rows_up(k->st, k->b_pokc, pok_c, off, m, 32);
+                rows_up(k->st, k->b_poks, pok_s, off, m, 32 * RP_N_RESP);
+            }
+            rows_up(k->st, k->b_comf, com_f, off, m, 64);
+            rows_up(k->st, k->b_comg, com_g, off, m, 64);
+            rows_up(k->st, k->b_comq, com_q, off, m, 64);
+            rows_up(k->st, k->b_evals, evals, off, m, 96);
+            rows_up(k->st, k->b_proofs, proofs, off, m, 288);
+            rows_up(k->st, k->b_c, c, off, m, 32);
+            rows_up(k->st, k->b_rho, rho, off, m, 32);
+            rows_up(k->st, k->b_rz, randomizers, off, m, 32);
+            auto w = [](const DevBuf<uint8_t>& b) { return (const uint32_t*)b.p; };
+            const RvArgs a{w(k->b_ped), w(k->b_comf), w(k->b_comg), w(k->b_comq), w(k->b_evals), w(k->b_proofs), w(k->b_c), w(k->b_rho),
+                           w(k->b_rz), pok ? w(k->b_pokc) : nullptr, pok ? w(k->b_poks) : nullptr, m, n_fixed, n_var};
+            const uint32_t grid = ceil_div(m, RVBLOCK);
+            CG_HIP(hipEventRecord(k->ev[0], k->st));
+            k_rv_check<<<grid, RVBLOCK, 0, k->st>>>(k->kc, a, k->b_scal.p, k->b_flags.p);
+            CG_KERNEL_CHECK();
+            k_rv_terms<<<ceil_div(m * n_fixed, RVBLOCK) + ceil_div(m * n_var, RVBLOCK), RVBLOCK, 0, k->st>>>(
+                a, k->b_scal.p, k->b_flags.p, k->tab.p, k->slots[slot].p, k->b_part.p);
+            CG_KERNEL_CHECK();
+            k_rv_sum<<<ceil_div(m * (pok ? 4 : 2), RVBLOCK), RVBLOCK, 0, k->st>>>(a, k->b_flags.p, k->b_part.p, k->b_pair.p, (uint32_t*)k->b_k.p);
+            CG_KERNEL_CHECK();
+            CG_HIP(hipEventRecord(k->ev[1], k->st));
+            k_rv_miller<<<grid, RVBLOCK, 0, k->st>>>(k->b_pair.p, k->b_flags.p, m, k->beta_h_c.p, k->h_c.p, k->beta_h_live, k->h_live, k->b_miller.p);
+            CG_KERNEL_CHECK();
+            k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.p, m, k->b_verdict.p);
+            CG_KERNEL_CHECK();
+            CG_HIP(hipEventRecord(k->ev[2], k->st));
+            rows_down(k->st, verdicts, k->b_verdict, off, m, 1);
+            if (pok) rows_down(k->st, k_out, k->b_k, off, m, 64);
+            CG_HIP(hipStreamSynchronize(k->st));
+            float t0 = 0, t1 = 0;
+            CG_HIP(hipEventElapsedTime(&t0, k->ev[0], k->ev[1]));
+            CG_HIP(hipEventElapsedTime(&t1, k->ev[1], k->ev[2]));
+            k->ms_group += t0;
+            k->ms_pairing += t1;
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}

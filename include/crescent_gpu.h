@@ -774,6 +774,65 @@ int cg_range_open_batch(cg_range_pk* k, const uint8_t* openings, const uint8_t* 
 int cg_range_respond_batch(const uint8_t* openings, const uint8_t* rand, const uint8_t* c_dleq, const uint8_t* status,
                            uint64_t n, uint8_t* pok_s);
 
+/* Verifying range proofs: `ShowRange::verify` (creds/src/lib.rs:650, :852, :881) -> `RangeProof::verify_n_bits`
+ * (creds/src/rangeproof.rs:342-424) for n proofs under one `RangeProofVK`, the other half of verifying a showing beside
+ * cg_verify_show_batch.  The split is the same: the group arithmetic, the pairing check of `KZG10::batch_check`
+ * (forks/ark-poly-commit/src/kzg10/mod.rs:357-411), the evaluation identity (rangeproof.rs:395-412) and the DLEQ's eq_pos
+ * comparison (dlog.rs:155-164) run on the GPU; every Merlin transcript and the final `c == self.c` stay with the host
+ * ("Verifying range proofs"):
+ *
+ *   com_f, com_g (compressed) --> range transcript --> c;  com_q --> rho      (rangeproof.rs:352-366)
+ *   verify (c, rho, r_1, r_2) --> verdicts, k_0, k_1
+ *   bases, k_i, y_i ------------> DLEQ transcript --> c' == pok_c ?           (dlog.rs:130-174)
+ *
+ * The library draws no randomness: batch_check's randomizers r_1, r_2 (`u128::rand`, kzg10/mod.rs:390; r_0 = 1) are the
+ * caller's, as r, s of cg_prove are.  They must be unpredictable to whoever made the proofs. */
+typedef struct cg_range_vk cg_range_vk;
+/* Replaces: `read_from_file` of range_vk.bin (`RangeProofVK`, rangeproof.rs:74-78): the KZG `VerifierKey` as its
+ *           hand-written serialisation writes it (kzg10/data_structures.rs:217-264: g 64 B | gamma_g 64 B | h 128 B |
+ *           beta_h 128 B, ark-serialize uncompressed) and com_f_basis as four uncompressed G1 points with no length
+ *           prefix: 640 bytes exactly, read unchecked as the reference reads them; prepared_h and prepared_beta_h are
+ *           computed here as the reference's deserialiser computes them (a G2 point at infinity gives a prepared point
+ *           marked infinity, whose pair the pairing check skips) + the upload to a device (-1 = current) of both and of
+ *           fixed-base tables of g, gamma_g and com_f_basis.
+ * Another length, a coordinate >= q or invalid point flags are CG_ERR_PARSE; n_bits outside {2, 4, 8, 16, 32} is
+ * CG_ERR_INVALID_ARGUMENT.  All of them are reported before any HIP call. */
+int cg_range_vk_load(cg_range_vk** out, const uint8_t* range_vk_bytes, uint64_t len, uint32_t n_bits, int32_t device);
+/* As cg_range_pk_add_bases: registers an input's `gamma_abc_g1[pos]` and `delta_g1` (groth16rand.rs:319-323), the bases of
+ * the Pedersen commitment a range proof speaks about, 2 x 64 B ark-serialize uncompressed, checked; up to 64 slots. */
+int cg_range_vk_add_bases(cg_range_vk* k, const uint8_t ped_bases[128], uint32_t* slot);
+/* Diagnostic: the HIP-event time of the handle's last call, summed over its chunks: the group stage (checks, scalar
+ * multiplications, sums) and the pairing (Miller loop, final exponentiation).  (No counterpart in the reference.) */
+int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms);
+void cg_range_vk_free(cg_range_vk* k);
+/* Replaces: `verify_n_bits` between its transcripts, for n proofs whose commitment has the bases of `slot`.  The pieces
+ *           of a `RangeProof` come in the layouts the cg_range_* creation calls write, so a round trip repacks nothing:
+ * ped_com, com_f, com_g, com_q: n x 64 B ark-serialize uncompressed G1 (ped_com: the Pedersen commitment, y_0 of the DLEQ)
+ * evals:       n x 3 x 32 B canonical Fr: eval_g, eval_gw, eval_w_hat
+ * proofs:      n x 3 x 96 B: W (64 B uncompressed) ‖ random_v (32 B) of proof_g, proof_gw, proof_w_hat; a random_v of
+ *              `None` is passed as 0, which is the same group element
+ * c, rho:      n x 32 B canonical Fr, the range transcript's two challenges
+ * randomizers: n x 2 x 16 B little-endian u128: r_1, r_2; any value, 0 included
+ * pok_c:       n x 32 B, the DLEQ's c (dleq_proof.c); NULL = steps up to the evaluation identity only: ped_com, pok_s and
+ *              k_out are then not touched
+ * pok_s:       n x CG_RANGE_N_RESP x 32 B: s_00 s_01 s_10..s_13, as cg_range_respond_batch writes them
+ * verdicts:    n x CG_VERIFY_*.  CG_VERIFY_ACCEPT: e(-total_w, beta_h) e(total_c, h) = 1, the evaluation identity holds and
+ *              (with a DLEQ) s_00 == s_13; the showing is valid when the host's recomputed DLEQ challenge also equals
+ *              pok_c.  CG_VERIFY_REJECT: one of the three fails.  CG_VERIFY_MALFORMED (that showing only, its k_out bytes
+ *              zero, its neighbours untouched): one of the seven points fails ark's checked G1 deserialisation (a
+ *              coordinate >= q, invalid flags, off the curve; the identity is legal), a scalar is >= r, or rho is 1 or
+ *              w^(n_bits - 1), the two values at which the reference divides by zero and panics.  Every other rho with
+ *              rho^n_bits = 1 is computed as the reference computes it (q_coeff = f_coeff = 0, com_w_hat = O).
+ * k_out:       n x 2 x 32 B ark-serialize COMPRESSED G1: k_0 = s_00 B_0 + s_01 B_1 + c ped_com and k_1 = s_10 gamma_g[0] +
+ *              s_11 gamma_g[1] + s_12 gamma_g[2] + s_13 g[0] + c com_f (dlog.rs:135-145), the bytes
+ *              `add_to_transcript(b"k", ..)` appends, in the encoding of cg_range_commit_batch's ts_out[2..3].
+ * Argument errors (a null array, an unknown slot) are reported before any HIP call; n = 0 is CG_OK; calls on one handle
+ * serialise, different handles are independent. */
+int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
+                          const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c, const uint8_t* rho,
+                          const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts,
+                          uint8_t* k_out);
+
 /* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
  * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the
  * PreparedVerifyingKey bytes (*len of them; pvk_out = NULL only reports *len).  A buffer shorter than *len is

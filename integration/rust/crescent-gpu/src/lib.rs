@@ -996,3 +996,97 @@ impl Drop for GpuRangeKey {
         unsafe { sys::cg_range_pk_free(self.h) }
     }
 }
+
+/// A `RangeProofVK` (creds/src/rangeproof.rs:74-78) resident on the GPU for verifying range proofs in batches
+/// (`RangeProof::verify_n_bits`, rangeproof.rs:342-424) between the host's transcripts ("Verifying range proofs").
+pub struct GpuRangeVerifyingKey {
+    h: *mut sys::cg_range_vk,
+}
+unsafe impl Send for GpuRangeVerifyingKey {}
+unsafe impl Sync for GpuRangeVerifyingKey {} // calls on one handle serialise inside the library
+
+/// The flat arrays of `cg_range_verify_batch`, one row per proof, in the layouts the creation calls write
+pub struct RangeProofRows<'a> {
+    /// n x 64 B uncompressed each: the Pedersen commitment, then the proof's three commitments
+    pub ped_com: &'a [u8],
+    pub com_f: &'a [u8],
+    pub com_g: &'a [u8],
+    pub com_q: &'a [u8],
+    /// n x 3 x 32 B (eval_g, eval_gw, eval_w_hat); n x 3 x 96 B (W uncompressed, then random_v; `None` as 0)
+    pub evals: &'a [u8],
+    pub proofs: &'a [u8],
+    /// the range transcript's challenges, n each
+    pub c: &'a [Fr],
+    pub rho: &'a [Fr],
+    /// n x (r_1, r_2): `KZG10::batch_check`'s randomizers, drawn by the caller
+    pub randomizers: &'a [u128],
+    /// dleq_proof.c, n; dleq_proof.s flattened, n x 6
+    pub pok_c: &'a [Fr],
+    pub pok_s: &'a [Fr],
+}
+
+impl GpuRangeVerifyingKey {
+    /// `range_vk_bytes`: the 640 bytes of range_vk.bin; `n_bits`: 32 in the product
+    pub fn load(range_vk_bytes: &[u8], n_bits: u32) -> Result<Self, SynthesisError> {
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe { sys::cg_range_vk_load(&mut h, range_vk_bytes.as_ptr(), range_vk_bytes.len() as u64, n_bits, -1) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(GpuRangeVerifyingKey { h })
+    }
+
+    /// Registers the Pedersen bases of one range-checked input (groth16rand.rs:319-323) and returns their slot.
+    pub fn add_bases(&self, gamma_abc_point: &G1Affine, delta_g1: &G1Affine) -> Result<u32, SynthesisError> {
+        let mut b = Vec::with_capacity(128);
+        for p in [gamma_abc_point, delta_g1] {
+            p.serialize_uncompressed(&mut b).map_err(|_| SynthesisError::AssignmentMissing)?;
+        }
+        let mut slot = 0u32;
+        let rc = unsafe { sys::cg_range_vk_add_bases(self.h, b.as_ptr(), &mut slot) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(slot)
+    }
+
+    /// (group stage, pairing) HIP-event milliseconds of the last call
+    pub fn last_kernel_ms(&self) -> Result<(f32, f32), SynthesisError> {
+        let (mut a, mut b) = (0f32, 0f32);
+        let rc = unsafe { sys::cg_range_vk_last_kernel_ms(self.h, &mut a, &mut b) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((a, b))
+    }
+
+    /// Returns (verdicts: n x CG_VERIFY_*, k: n x 2 x 32 B compressed k_0, k_1).  A proof is valid when its verdict is
+    /// CG_VERIFY_ACCEPT and the DLEQ transcript over the bases, k and y (dlog.rs:130-174) gives back its pok_c.
+    pub fn verify_batch(&self, slot: u32, rows: &RangeProofRows) -> Result<(Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = rows.c.len();
+        if rows.ped_com.len() != n * 64 || rows.com_f.len() != n * 64 || rows.com_g.len() != n * 64 || rows.com_q.len() != n * 64
+            || rows.evals.len() != n * 96 || rows.proofs.len() != n * 288 || rows.rho.len() != n || rows.randomizers.len() != 2 * n
+            || rows.pok_c.len() != n || rows.pok_s.len() != n * sys::CG_RANGE_N_RESP
+        {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (cb, hb, pc, ps) = (canonical_bytes(rows.c), canonical_bytes(rows.rho), canonical_bytes(rows.pok_c), canonical_bytes(rows.pok_s));
+        let zb: Vec<u8> = rows.randomizers.iter().flat_map(|r| r.to_le_bytes()).collect();
+        let (mut verdicts, mut k) = (vec![0u8; n], vec![0u8; n * 64]);
+        let rc = unsafe {
+            sys::cg_range_verify_batch(self.h, slot, rows.ped_com.as_ptr(), rows.com_f.as_ptr(), rows.com_g.as_ptr(), rows.com_q.as_ptr(),
+                                       rows.evals.as_ptr(), rows.proofs.as_ptr(), cb.as_ptr(), hb.as_ptr(), zb.as_ptr(), pc.as_ptr(),
+                                       ps.as_ptr(), n as u64, verdicts.as_mut_ptr(), k.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((verdicts, k))
+    }
+}
+
+impl Drop for GpuRangeVerifyingKey {
+    fn drop(&mut self) {
+        unsafe { sys::cg_range_vk_free(self.h) }
+    }
+}

@@ -162,6 +162,7 @@ pub enum cg_msm_ctx {}
 pub enum cg_qap_ctx {}
 pub enum cg_pvk {}
 pub enum cg_range_pk {}
+pub enum cg_range_vk {}
 
 extern "C" {
     pub fn cg_init(n_devices: c_int, device_ids: *const c_int) -> c_int;
@@ -430,5 +431,33 @@ extern "C" {
         status: *const u8,
         n: u64,
         pok_s: *mut u8,
+    ) -> c_int;
+    pub fn cg_range_vk_load(
+        out: *mut *mut cg_range_vk,
+        range_vk_bytes: *const u8,
+        len: u64,
+        n_bits: u32,
+        device: i32,
+    ) -> c_int;
+    pub fn cg_range_vk_add_bases(k: *mut cg_range_vk, ped_bases: *const u8, slot: *mut u32) -> c_int;
+    pub fn cg_range_vk_last_kernel_ms(k: *mut cg_range_vk, group_ms: *mut f32, pairing_ms: *mut f32) -> c_int;
+    pub fn cg_range_vk_free(k: *mut cg_range_vk);
+    pub fn cg_range_verify_batch(
+        k: *mut cg_range_vk,
+        slot: u32,
+        ped_com: *const u8,
+        com_f: *const u8,
+        com_g: *const u8,
+        com_q: *const u8,
+        evals: *const u8,
+        proofs: *const u8,
+        c: *const u8,
+        rho: *const u8,
+        randomizers: *const u8,
+        pok_c: *const u8,
+        pok_s: *const u8,
+        n: u64,
+        verdicts: *mut u8,
+        k_out: *mut u8,
     ) -> c_int;
 }
