@@ -830,8 +830,53 @@ def host_unregister(a: np.ndarray) -> None:
     _check(lib().cg_host_unregister(C.c_void_p(a.ctypes.data)))
 
 
-class QapContext:
+class _Handle:
+    """What the classes that own one C handle share.  `_h` is the c_void_p their load call fills and `_free` names the C
+    symbol that releases it.  close() is idempotent, `with` closes on exit, and __del__ swallows errors (an interpreter
+    that is shutting down may have let go of the library already)."""
+    _free = ""
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(lib(), self._free)(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _RangeSlots:
+    """The slots and the kernel times of the two range keys (RangeProofKey, RangeVerifyingKey); `_add_bases` and
+    `_last_kernel_ms` name the C symbols."""
+
+    def add_bases(self, gamma_abc_point, delta_g1) -> int:
+        """registers the Pedersen bases of one range-checked input (2 x 64 B ark-serialize uncompressed G1) and returns
+        their slot (cg_range_pk_add_bases / cg_range_vk_add_bases)"""
+        b = _u8(bytes(gamma_abc_point) + bytes(delta_g1), 128)
+        slot = C.c_uint32()
+        _check(getattr(lib(), self._add_bases)(self._h, _ptr(b), C.byref(slot)))
+        return int(slot.value)
+
+    def last_kernel_ms(self) -> Tuple[float, float]:
+        """HIP-event milliseconds of the last GPU call on this key, by stage: (polynomial stage, fixed-base walks) of a
+        RangeProofKey, (group stage, pairing) of a RangeVerifyingKey"""
+        a, b = C.c_float(), C.c_float()
+        _check(getattr(lib(), self._last_kernel_ms)(self._h, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
+
+class QapContext(_Handle):
     """Three constraint matrices resident on one GPU with their domain tables, no proving key (cg_qap_ctx)."""
+    _free = "cg_qap_free"
 
     def __init__(self, matrices: ConstraintMatrices, device: int = -1, scalar_form: int = CG_FORM_CANONICAL):
         """scalar_form: the form of the assignments witness_map / check_witness take and of the h witness_map returns
@@ -865,17 +910,6 @@ class QapContext:
     def witness_map_dev(self, d_assignment: int, d_h: int) -> None:
         """assignment (num_variables x 32 B) and h (domain_size x 32 B) both in this GPU's memory"""
         _check(lib().cg_qap_witness_map(self._h, C.c_void_p(d_assignment), 1, C.c_void_p(d_h), 1))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cg_qap_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class R1CSToQAP:
@@ -1432,10 +1466,11 @@ class Groth16:
         cls._cache.clear()
 
 
-class PreparedVerifyingKey:
+class PreparedVerifyingKey(_Handle):
     """forks/groth16/src/data_structures.rs:62-71, parsed from its serialized bytes (`deserialize_uncompressed_unchecked`,
     creds/src/utils.rs:186) and resident on a GPU (cg_pvk_load): alpha_g1_beta_g2, the prepared gamma / delta lines and
     fixed-base tables of gamma_abc_g1.  Use as a context manager or close()."""
+    _free = "cg_pvk_free"
 
     def __init__(self, pvk_bytes, device: int = -1):
         b = _u8(pvk_bytes)
@@ -1449,64 +1484,17 @@ class PreparedVerifyingKey:
         _check(lib().cg_pvk_num_inputs(self._h, C.byref(n)))
         return int(n.value)
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cg_pvk_free(self._h)
-            self._h = C.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RangeProofKey:
+class RangeProofKey(_RangeSlots, _Handle):
     """`RangeProofPK` (creds/src/rangeproof.rs:26-29) from the bytes of range_pk.bin (creds/src/lib.rs:241), resident on a
     GPU as fixed-base tables for proofs of n_bits bits (cg_range_pk_load).  Use as a context manager or close()."""
+    _free, _add_bases, _last_kernel_ms = "cg_range_pk_free", "cg_range_pk_add_bases", "cg_range_pk_last_kernel_ms"
 
     def __init__(self, range_pk_bytes, n_bits: int, device: int = -1):
         b = _u8(range_pk_bytes)
         self.n_bits = int(n_bits)
         self._h = C.c_void_p()
         _check(lib().cg_range_pk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, self.n_bits, device))
-
-    def add_bases(self, gamma_abc_point, delta_g1) -> int:
-        """registers the Pedersen bases of one range-checked input (2 x 64 B ark-serialize uncompressed G1) and returns
-        their slot (cg_range_pk_add_bases)"""
-        b = _u8(bytes(gamma_abc_point) + bytes(delta_g1), 128)
-        slot = C.c_uint32()
-        _check(lib().cg_range_pk_add_bases(self._h, _ptr(b), C.byref(slot)))
-        return int(slot.value)
-
-    def last_kernel_ms(self) -> Tuple[float, float]:
-        """(polynomial stage, fixed-base walks): HIP-event milliseconds of the last GPU call on this key"""
-        a, b = C.c_float(), C.c_float()
-        _check(lib().cg_range_pk_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
-        return float(a.value), float(b.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cg_range_pk_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _g1_compress(unc) -> np.ndarray:
@@ -1525,47 +1513,17 @@ def _g1_compress(unc) -> np.ndarray:
     return np.frombuffer(bytes(out), np.uint8)
 
 
-class RangeVerifyingKey:
+class RangeVerifyingKey(_RangeSlots, _Handle):
     """`RangeProofVK` (creds/src/rangeproof.rs:74-78) from the 640 bytes of range_vk.bin, resident on a GPU with h and
     beta_h prepared and fixed-base tables of g, gamma_g and com_f_basis, for proofs of n_bits bits (cg_range_vk_load).
     Use as a context manager or close()."""
+    _free, _add_bases, _last_kernel_ms = "cg_range_vk_free", "cg_range_vk_add_bases", "cg_range_vk_last_kernel_ms"
 
     def __init__(self, range_vk_bytes, n_bits: int, device: int = -1):
         b = _u8(range_vk_bytes)
         self.n_bits = int(n_bits)
         self._h = C.c_void_p()
         _check(lib().cg_range_vk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, self.n_bits, device))
-
-    def add_bases(self, gamma_abc_point, delta_g1) -> int:
-        """registers the Pedersen bases of one range-checked input (2 x 64 B ark-serialize uncompressed G1) and returns
-        their slot (cg_range_vk_add_bases)"""
-        b = _u8(bytes(gamma_abc_point) + bytes(delta_g1), 128)
-        slot = C.c_uint32()
-        _check(lib().cg_range_vk_add_bases(self._h, _ptr(b), C.byref(slot)))
-        return int(slot.value)
-
-    def last_kernel_ms(self) -> Tuple[float, float]:
-        """(group stage, pairing): HIP-event milliseconds of the last call on this key"""
-        a, b = C.c_float(), C.c_float()
-        _check(lib().cg_range_vk_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
-        return float(a.value), float(b.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cg_range_vk_free(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 @dataclass
@@ -1761,9 +1719,10 @@ def ifft_in_place(data, coset: bool = False) -> np.ndarray:
     return _ntt(data, True, coset)
 
 
-class MsmContext:
+class MsmContext(_Handle):
     """A fixed set of G1 (group=1) or G2 (group=2) bases resident on the GPU with its window tables; `run` is
     msm_bigint against them (cg_msm_load_* / cg_msm_run)."""
+    _free = "cg_msm_free"
 
     def __init__(self, bases, group: int = 1, coord_form: int = CG_FORM_CANONICAL, window_bits: int = 0, device: int = -1,
                  scalars_montgomery: bool = False):
@@ -1795,20 +1754,10 @@ class MsmContext:
         _check(lib().cg_msm_run(self._h, ptr, on_device, n, _ptr(out), C.byref(tm) if timings else None))
         return (out.tobytes(), tm.as_dict()) if timings else out.tobytes()
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cg_msm_free(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class NttContext:
+class NttContext(_Handle):
     """A radix-2 domain of size 2^log_n resident on the GPU (cg_ntt_load / cg_ntt_run)."""
+    _free = "cg_ntt_free"
 
     def __init__(self, log_n: int, device: int = -1):
         self.log_n = log_n
@@ -1825,17 +1774,6 @@ class NttContext:
         ms = C.c_float(0)
         _check(lib().cg_ntt_run(self._h, d_ptr, 1, 1 if inverse else 0, 1 if coset else 0, C.byref(ms)))
         return float(ms.value)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().cg_ntt_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def fixed_base_g1(scalars) -> bytes:

@@ -1,6 +1,7 @@
 // What the entries that read and write ark-serialize on the device share (verify.hip, rangeproof.hip, rangeverify.hip):
-// the strict host reader of a serialized key, the point codec of the kernels, and the per-call buffers' growth and row
-// copies.
+// the strict host reader of a serialized key, the point codec of the kernels, and `grow` for the device buffers that
+// hold no caller's bytes.  The handles' host code - stream, slots, the per-call arrays and their row copies - is in
+// key_handle.hpp, which includes this file.
 // For .hip files only.
 #pragma once
 #include "common.hpp"
@@ -192,14 +193,6 @@ __device__ __forceinline__ Fr dev_fr(const uint32_t* w) {
 template <class T>
 static void grow(DevBuf<T>& b, uint64_t count) {
     if (b.n < count) b.alloc(count);
-}
-// rows [off, off + m) of a caller's array, `stride` bytes each, to the start of a device buffer and back, on the handle's
-// stream; nothing for an array the layout leaves empty (stride 0) or the caller may leave out (null)
-static void rows_up(hipStream_t st, DevBuf<uint8_t>& d, const uint8_t* h, uint64_t off, uint64_t m, uint64_t stride) {
-    if (h && stride) CG_HIP(hipMemcpyAsync(d.p, h + off * stride, m * stride, hipMemcpyHostToDevice, st));
-}
-static void rows_down(hipStream_t st, uint8_t* h, const DevBuf<uint8_t>& d, uint64_t off, uint64_t m, uint64_t stride) {
-    if (h && stride) CG_HIP(hipMemcpyAsync(h + off * stride, d.p, m * stride, hipMemcpyDeviceToHost, st));
 }
 
 }  // namespace

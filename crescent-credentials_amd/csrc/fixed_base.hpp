@@ -2,7 +2,7 @@
 // bases with one inversion, and the walk every kernel takes through one (the verifier's x_i·gamma_abc[i+1], a showing's
 // responses and nonces, r2·delta_g2 over Fq2, and the setup's six FixedBase::msm calls, generator.rs:140-194).
 // Next to it what the same two files share besides: the standard generators, which are the setup's fixed bases and one of
-// a key's, and the variable-base chain of the verifier's kernels.
+// a key's, and the one variable-base chain of the verifiers' and the showing creator's kernels (scalar_mul_mixed).
 // Host and device; builds under plain g++ the way pairing.hpp does (tests/cpp/test_pairing.cpp).
 #pragma once
 #include <vector>
@@ -70,20 +70,25 @@ CG_HD XYZZ<F> fixed_base_mul(const Affine<F>* tab, const uint32_t k[8]) {
     return XYZZ<F>{acc.x, acc.y, acc.zz, acc.zzz};
 }
 
-// k * y for an affine y and k < 2^254 (any canonical scalar: r < 2^254): 254 doublings, each followed by a mixed addition
-// where the bit is set, from bit 253 down.  The doublings before the first set bit return at once.
+// k * y for an affine y and k < 2^bits (0 <= bits <= 256): `bits` doublings, each followed by a mixed addition where the bit
+// is set, from bit bits - 1 down.  The doublings before the first set bit return at once.  The one variable-base chain of
+// the kernels: a length known where it is inlined (the 254 below) costs what a loop written for that length costs.
 template <class F>
-CG_HD XYZZ<F> scalar_mul_254_mixed(const Affine<F>& y, const uint32_t k[8]) {
+CG_HD XYZZ<F> scalar_mul_mixed(const Affine<F>& y, const uint32_t* k, int bits) {
     XYZZ<F> acc = XYZZ<F>::inf();
-    for (int wi = 7; wi >= 0; --wi) {
+    const int top = (bits - 1) >> 5;
+    for (int wi = top; wi >= 0; --wi) {
         const uint32_t kw = k[wi];
-        for (int b = wi == 7 ? 29 : 31; b >= 0; --b) {
+        for (int b = wi == top ? (bits - 1) & 31 : 31; b >= 0; --b) {
             acc = dbl(acc);
             if ((kw >> b) & 1u) madd(acc, y);
         }
     }
     return acc;
 }
+// any canonical scalar: r < 2^254
+template <class F>
+CG_HD XYZZ<F> scalar_mul_254_mixed(const Affine<F>& y, const uint32_t k[8]) { return scalar_mul_mixed(y, k, 254); }
 
 // The standard generators (ark-bn254 g1.rs, g2.rs; the fork fixes them, generator.rs:34-35), host side, Montgomery form.
 // G2's coordinates are parsed from their decimal strings, as ark-bn254's source states them, instead of trusting

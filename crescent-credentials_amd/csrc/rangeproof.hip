@@ -20,16 +20,15 @@
 //   quotient  com_q                           2n + 7 terms     (rangeproof.rs:260-268)
 //   open      W of proof_g, proof_gw, proof_w^   4n + 15 terms (KZG10::open, kzg10/mod.rs:247-331)
 // cg_range_respond_batch, the DLEQ's responses once the host's transcript has produced its challenge, is host arithmetic.
+// The handle's device, stream and lock, the timing of the two stages, the slots and the per-call arrays are key_handle.hpp's
+// (KeyHandle, StageTimer, PedersenSlots, RowBuf), shared with cg_pvk and cg_range_vk; so are the responses (dlog_respond).
 #include <memory>
 
-#include "ark_codec.hpp"
 #include "common.hpp"
 #include "fixed_base.hpp"
+#include "key_handle.hpp"
 #include "rangepoly.hpp"
 
-namespace cg {
-int translate_current_exception();
-}
 using namespace cg;
 
 namespace {
@@ -37,7 +36,6 @@ namespace {
 constexpr uint64_t RCHUNK = 1u << 12;      // showings per launch set: 4n + 15 term scalars each in the open call
 constexpr int RWAVE = 64;
 constexpr uint32_t RP_SLOT = 0x80000000u;  // in tab_of: a table of the call's slot (0 or 1) instead of the key's
-constexpr uint32_t MAX_SLOTS = 64;
 enum { PH_COMMIT = 0, PH_QUOTIENT = 1, PH_OPEN = 2 };
 
 // One output point: terms [term0, term0 + n_terms) of a showing.  It goes to the showing's row of uncompressed buffer
@@ -148,33 +146,26 @@ void range_shapes(uint32_t n, RpShape sh[3], std::vector<uint32_t> tab_of[3]) {
 
 }  // namespace
 
-struct cg_range_pk {
-    int device = 0;
+struct cg_range_pk : KeyHandle {
     uint32_t n_bits = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    float ms_poly = 0, ms_points = 0;      // of the last call, summed over its chunks
-    std::mutex mu;
+    StageTimer timer;                      // the polynomial stage, the points
     RangeConsts kc;
     RpShape shape[3];
     DevBuf<G1Affine> tab;                  // powers_of_g[0..2n+3], then powers_of_gamma_g[0..3]
-    std::vector<DevBuf<G1Affine>> slots;   // per slot: the tables of its two Pedersen bases
+    PedersenSlots slots;                   // per slot: the tables of its two Pedersen bases
     DevBuf<RpShape> d_shape;               // the three calls' layouts
     DevBuf<uint32_t> d_tab_of[3];
-    // per-call buffers, grown to the largest chunk seen; bytes are the caller's
-    DevBuf<uint8_t> b_open, b_rand, b_c, b_rho, b_terms, b_unc0, b_unc1, b_cmp, b_evals, b_status;
+    // per-call arrays with their row widths (a call's layout sets the others), grown to the largest chunk seen; bytes are
+    // the caller's
+    RowBuf b_open{64}, b_rand{32 * RP_N_RAND}, b_c{32}, b_rho{32}, b_terms, b_unc0, b_unc1, b_cmp, b_evals, b_status{1};
     DevBuf<G1XYZZ> b_part;                 // one partial per (showing, term)
-    ~cg_range_pk() {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    ~cg_range_pk() { drain(); }            // before the buffers above are freed (key_handle.hpp)
 };
 
 extern "C" int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes, uint64_t len, uint32_t n_bits, int32_t device) {
     if (!out || !range_pk_bytes) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    if (n_bits != 2 && n_bits != 4 && n_bits != 8 && n_bits != 16 && n_bits != 32)
-        return fail(CG_ERR_INVALID_ARGUMENT, "n_bits = %u: prove_n_bits takes a power of two, and a value has at most 32 bits here", n_bits);
+    if (int rc = check_range_bits(n_bits, "prove_n_bits")) return rc;
     try {
         // host only: every error of the bytes is reported before any HIP call
         KeyRd r{range_pk_bytes, len, 0};
@@ -196,12 +187,8 @@ extern "C" int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes
         k->kc = range_consts((uint32_t)ilog2_ceil(n));
         std::vector<uint32_t> tab_of[3];
         range_shapes(n, k->shape, tab_of);
-        int dev = device;
-        if (dev < 0) CG_HIP(hipGetDevice(&dev));
-        CG_HIP(hipSetDevice(dev));
-        k->device = dev;
-        CG_HIP(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
-        for (hipEvent_t& e : k->ev) CG_HIP(hipEventCreate(&e));
+        k->open(device);
+        k->timer.create();
         k->tab.alloc(tab.size());
         h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
         k->d_shape.alloc(3);
@@ -219,38 +206,13 @@ extern "C" int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes
 
 extern "C" int cg_range_pk_add_bases(cg_range_pk* k, const uint8_t ped_bases[128], uint32_t* slot) {
     if (!k || !ped_bases || !slot) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    std::vector<G1Affine> bases(3, G1Affine::inf()), tab;
-    for (int i = 0; i < 2; ++i)
-        if (!checked_g1(ped_bases + 64 * i, bases[1 + i])) return fail(CG_ERR_INVALID_ARGUMENT, "Pedersen base %d is no valid G1 point", i);
-    try {
-        std::lock_guard<std::mutex> lk(k->mu);
-        if (k->slots.size() >= MAX_SLOTS) return fail(CG_ERR_INVALID_ARGUMENT, "all %u slots of this key are taken", MAX_SLOTS);
-        build_tables(bases, tab);
-        CG_HIP(hipSetDevice(k->device));
-        DevBuf<G1Affine> d(tab.size());
-        h2d_sync(d.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
-        k->slots.push_back(std::move(d));
-        *slot = (uint32_t)k->slots.size() - 1;
-        return CG_OK;
-    } catch (...) {
-        return translate_current_exception();
-    }
+    return k->slots.add(*k, ped_bases, slot);
 }
 
-extern "C" void cg_range_pk_free(cg_range_pk* k) {
-    if (!k) return;
-    (void)hipSetDevice(k->device);
-    delete k;                    // the destructor waits for the handle's stream
-}
+extern "C" void cg_range_pk_free(cg_range_pk* k) { free_handle(k); }
 
 // Diagnostic: what the two kernels of the handle's last GPU call took, by HIP events, summed over its chunks
-extern "C" int cg_range_pk_last_kernel_ms(cg_range_pk* k, float* poly_ms, float* points_ms) {
-    if (!k || !poly_ms || !points_ms) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> lk(k->mu);
-    *poly_ms = k->ms_poly;
-    *points_ms = k->ms_points;
-    return CG_OK;
-}
+extern "C" int cg_range_pk_last_kernel_ms(cg_range_pk* k, float* poly_ms, float* points_ms) { return last_kernel_ms(k, poly_ms, points_ms); }
 
 namespace {
 struct RpCall {
@@ -264,11 +226,7 @@ struct RpCall {
 int run_range(cg_range_pk* k, const RpCall& a) {
     try {
         std::lock_guard<std::mutex> lk(k->mu);
-        const G1Affine* tab_slot = nullptr;
-        if (a.phase == PH_COMMIT) {
-            if (a.slot >= k->slots.size()) return fail(CG_ERR_INVALID_ARGUMENT, "slot %u was not registered on this key (cg_range_pk_add_bases)", a.slot);
-            tab_slot = k->slots[a.slot].p;
-        }
+        const G1Affine* tab_slot = a.phase == PH_COMMIT ? k->slots.table(a.slot, "cg_range_pk_add_bases") : nullptr;
         if (a.n == 0) return CG_OK;
         const bool null_in = !a.open || !a.rand || (a.phase >= PH_QUOTIENT && !a.c) || (a.phase == PH_OPEN && !a.rho);
         const bool null_out = !a.unc0 || !a.status || (a.phase == PH_COMMIT && !a.unc1) || (a.phase != PH_OPEN && !a.cmp) || (a.phase == PH_OPEN && !a.evals);
@@ -276,55 +234,45 @@ int run_range(cg_range_pk* k, const RpCall& a) {
         CG_HIP(hipSetDevice(k->device));
         const RpShape& sh = k->shape[a.phase];
         const uint64_t chunk = a.n < RCHUNK ? a.n : RCHUNK;
-        const uint64_t unc0_b = 4 * sh.unc_words[0], unc1_b = 4 * sh.unc_words[1], cmp_b = 4 * sh.cmp_words, ev_b = a.phase == PH_OPEN ? 96 : 0;
-        grow(k->b_open, chunk * 64);
-        grow(k->b_rand, chunk * 32 * RP_N_RAND);
-        grow(k->b_c, chunk * 32);
-        grow(k->b_rho, chunk * 32);
-        grow(k->b_terms, chunk * 32 * sh.n_terms);
-        grow(k->b_unc0, chunk * unc0_b);
-        grow(k->b_unc1, chunk * unc1_b + 16);
-        grow(k->b_cmp, chunk * cmp_b + 16);
-        grow(k->b_evals, chunk * ev_b + 16);
-        grow(k->b_status, chunk);
+        for (RowBuf* b : {&k->b_open, &k->b_rand, &k->b_c, &k->b_rho, &k->b_status}) b->reserve(chunk);
+        k->b_terms.reserve(chunk, 32 * sh.n_terms);
+        k->b_unc0.reserve(chunk, 4 * sh.unc_words[0]);
+        k->b_unc1.reserve(chunk, 4 * sh.unc_words[1]);
+        k->b_cmp.reserve(chunk, 4 * sh.cmp_words);
+        k->b_evals.reserve(chunk, a.phase == PH_OPEN ? 96 : 0);
         grow(k->b_part, chunk * sh.n_terms);
-        k->ms_poly = k->ms_points = 0;
+        k->timer.reset();
         for (uint64_t off = 0; off < a.n; off += chunk) {
             const uint64_t m = a.n - off < chunk ? a.n - off : chunk;
-            rows_up(k->st, k->b_open, a.open, off, m, 64);
-            rows_up(k->st, k->b_rand, a.rand, off, m, 32 * RP_N_RAND);
-            if (a.phase >= PH_QUOTIENT) rows_up(k->st, k->b_c, a.c, off, m, 32);
-            if (a.phase == PH_OPEN) rows_up(k->st, k->b_rho, a.rho, off, m, 32);
-            const uint32_t *d_open = (const uint32_t*)k->b_open.p, *d_rand = (const uint32_t*)k->b_rand.p, *d_c = (const uint32_t*)k->b_c.p,
-                           *d_rho = (const uint32_t*)k->b_rho.p;
-            uint32_t *d_terms = (uint32_t*)k->b_terms.p, *d_ev = (uint32_t*)k->b_evals.p, *d_u0 = (uint32_t*)k->b_unc0.p;
-            CG_HIP(hipEventRecord(k->ev[0], k->st));
+            k->b_open.up(k->st, a.open, off, m);
+            k->b_rand.up(k->st, a.rand, off, m);
+            if (a.phase >= PH_QUOTIENT) k->b_c.up(k->st, a.c, off, m);
+            if (a.phase == PH_OPEN) k->b_rho.up(k->st, a.rho, off, m);
+            const uint32_t *d_open = k->b_open.words(), *d_rand = k->b_rand.words(), *d_c = k->b_c.words(), *d_rho = k->b_rho.words();
+            uint32_t *d_terms = k->b_terms.words_mut(), *d_ev = k->b_evals.words_mut(), *d_u0 = k->b_unc0.words_mut();
+            k->timer.mark(0, k->st);
             if (a.phase == PH_COMMIT)
-                k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.p);
+                k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes());
             else if (a.phase == PH_QUOTIENT)
-                k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.p);
+                k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes());
             else
-                k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.p);
+                k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes());
             CG_KERNEL_CHECK();
-            CG_HIP(hipEventRecord(k->ev[1], k->st));
+            k->timer.mark(1, k->st);
             k_range_terms<<<ceil_div(m * sh.n_terms, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + a.phase, k->d_tab_of[a.phase].p, d_terms, k->tab.p,
-                                                                                 tab_slot, k->b_status.p, m, k->b_part.p);
+                                                                                 tab_slot, k->b_status.bytes(), m, k->b_part.p);
             CG_KERNEL_CHECK();
-            k_range_sum<<<ceil_div(m * sh.n_pts, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + a.phase, k->b_status.p, m, k->b_part.p, d_u0,
-                                                                           (uint32_t*)k->b_unc1.p, (uint32_t*)k->b_cmp.p);
+            k_range_sum<<<ceil_div(m * sh.n_pts, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + a.phase, k->b_status.bytes(), m, k->b_part.p, d_u0,
+                                                                           k->b_unc1.words_mut(), k->b_cmp.words_mut());
             CG_KERNEL_CHECK();
-            CG_HIP(hipEventRecord(k->ev[2], k->st));
-            rows_down(k->st, a.unc0, k->b_unc0, off, m, unc0_b);
-            rows_down(k->st, a.unc1, k->b_unc1, off, m, unc1_b);
-            rows_down(k->st, a.cmp, k->b_cmp, off, m, cmp_b);
-            rows_down(k->st, a.evals, k->b_evals, off, m, ev_b);
-            rows_down(k->st, a.status, k->b_status, off, m, 1);
+            k->timer.mark(2, k->st);
+            k->b_unc0.down(k->st, a.unc0, off, m);
+            k->b_unc1.down(k->st, a.unc1, off, m);
+            k->b_cmp.down(k->st, a.cmp, off, m);
+            k->b_evals.down(k->st, a.evals, off, m);
+            k->b_status.down(k->st, a.status, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
-            float t0 = 0, t1 = 0;
-            CG_HIP(hipEventElapsedTime(&t0, k->ev[0], k->ev[1]));
-            CG_HIP(hipEventElapsedTime(&t1, k->ev[1], k->ev[2]));
-            k->ms_poly += t0;
-            k->ms_points += t1;
+            k->timer.add();
         }
         return CG_OK;
     } catch (...) {
@@ -359,23 +307,7 @@ extern "C" int cg_range_respond_batch(const uint8_t* openings, const uint8_t* ra
     if (!openings || !rand || !c_dleq || !pok_s) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     static const int SECRET[RP_N_RESP] = {-1, -2, RP_F, RP_F + 1, RP_F + 2, -1};      // -1: m, -2: r, else a rand index
     static const int NONCE[RP_N_RESP] = {RP_TM, RP_TR, RP_TF, RP_TF + 1, RP_TF + 2, RP_TM};
-    auto secret = [&](uint64_t p, int t) { return SECRET[t] < 0 ? openings + 64 * p + 32 * (-1 - SECRET[t]) : rand + 32 * (p * RP_N_RAND + SECRET[t]); };
-    auto nonce = [&](uint64_t p, int t) { return rand + 32 * (p * RP_N_RAND + NONCE[t]); };
-    for (uint64_t p = 0; p < n; ++p) {                            // every value first: an error writes nothing
-        if (status && status[p] != CG_SHOW_MADE) continue;
-        bool ok = scalar_is_canonical(c_dleq + 32 * p);
-        for (int t = 0; t < RP_N_RESP; ++t) ok = ok && scalar_is_canonical(secret(p, t)) && scalar_is_canonical(nonce(p, t));
-        if (!ok) return fail(CG_ERR_INVALID_ARGUMENT, "showing %llu: an opening, a rand scalar or c is not below the scalar modulus", (unsigned long long)p);
-    }
-    for (uint64_t p = 0; p < n; ++p) {
-        uint8_t* out = pok_s + 32 * RP_N_RESP * p;
-        if (status && status[p] != CG_SHOW_MADE) {
-            memset(out, 0, 32 * RP_N_RESP);
-            continue;
-        }
-        const Fr c = to_mont(fp_from_bytes<Fr>(c_dleq + 32 * p));            // c·R times a canonical x is c·x, canonical
-        for (int t = 0; t < RP_N_RESP; ++t)
-            fp_to_bytes(sub(fp_from_bytes<Fr>(nonce(p, t)), mul(c, fp_from_bytes<Fr>(secret(p, t)))), out + 32 * t);
-    }
-    return CG_OK;
+    auto secret = [&](uint64_t p, uint32_t t) { return SECRET[t] < 0 ? openings + 64 * p + 32 * (-1 - SECRET[t]) : rand + 32 * (p * RP_N_RAND + SECRET[t]); };
+    auto nonce = [&](uint64_t p, uint32_t t) { return rand + 32 * (p * RP_N_RAND + NONCE[t]); };
+    return dlog_respond(n, RP_N_RESP, status, c_dleq, secret, nonce, pok_s, "an opening");
 }

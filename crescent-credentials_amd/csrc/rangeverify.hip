@@ -22,17 +22,16 @@
 //                 whose G1 point is O, or whose key point is, is dropped as ark's multi_miller_loop drops it
 //   k_rv_final    one lane per showing: final exponentiation, == one, and the two bits               -> one verdict byte
 // A malformed showing costs nothing after k_rv_check: every later lane of it returns at once.
+// The handle's device, stream and lock, the timing of the two stages, the slots and the per-call arrays are key_handle.hpp's
+// (KeyHandle, StageTimer, PedersenSlots, RowBuf), shared with cg_pvk and cg_range_pk; the chains are scalar_mul_mixed.
 #include <memory>
 
-#include "ark_codec.hpp"
 #include "common.hpp"
 #include "fixed_base.hpp"
+#include "key_handle.hpp"
 #include "pairing.hpp"
 #include "rangeverify.hpp"
 
-namespace cg {
-int translate_current_exception();
-}
 using namespace cg;
 
 namespace {
@@ -43,7 +42,6 @@ namespace {
 constexpr uint64_t RVCHUNK = 1u << 15;
 constexpr int RVBLOCK = 64;
 constexpr int NC = PairingConsts::N_COEFFS;
-constexpr uint32_t MAX_SLOTS = 64;
 constexpr uint32_t RV_VK_BYTES = 640;      // g | gamma_g | h | beta_h | com_f_basis[4]
 // the key's tables: g, gamma_g, then com_f_basis
 enum { TAB_G = 0, TAB_GAMMA_G = 1, TAB_CFB = 2, N_TABS = 6 };
@@ -73,16 +71,6 @@ __global__ __launch_bounds__(RVBLOCK) void k_rv_check(RangeConsts kc, RvArgs a, 
     if (a.pok_c) (void)dev_g1(a.ped_com + 16 * p, ok);            // without a DLEQ the commitment is not read
     if (!ok) f = RV_MALFORMED;
     flags[p] = (uint8_t)f;
-}
-
-// k·y for an affine y and k < 2^bits: `bits` doublings, each followed by a mixed addition where the bit is set
-__device__ __forceinline__ G1XYZZ chain_mul(const G1Affine& y, const uint32_t* k, int bits) {
-    G1XYZZ acc = G1XYZZ::inf();
-    for (int b = bits - 1; b >= 0; --b) {
-        acc = dbl(acc);
-        if ((k[b >> 5] >> (b & 31)) & 1u) madd(acc, y);
-    }
-    return acc;
 }
 
 __global__ __launch_bounds__(RVBLOCK) void k_rv_terms(RvArgs a, const uint32_t* __restrict__ scal, const uint8_t* __restrict__ flags,
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(RVBLOCK) void k_rv_terms(RvArgs a, const uint32_t* 
         k = a.pok_c + 8 * p;
         pt = t == RV_N_VAR_KZG ? a.ped_com + 16 * p : a.com_f + 16 * p;
     }
-    part[(a.n_fixed + t) * m + p] = chain_mul(dev_g1_unchecked(pt), k, bits);
+    part[(a.n_fixed + t) * m + p] = scalar_mul_mixed(dev_g1_unchecked(pt), k, bits);
 }
 
 __global__ __launch_bounds__(RVBLOCK) void k_rv_sum(RvArgs a, const uint8_t* __restrict__ flags, const G1XYZZ* __restrict__ part,
@@ -197,35 +185,28 @@ __global__ __launch_bounds__(RVBLOCK) void k_rv_final(const Fq12* __restrict__ f
 
 }  // namespace
 
-struct cg_range_vk {
-    int device = 0;
+struct cg_range_vk : KeyHandle {
     uint32_t n_bits = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    float ms_group = 0, ms_pairing = 0;    // of the last call, summed over its chunks
-    std::mutex mu;
+    StageTimer timer;                      // the group stage, the pairing
     RangeConsts kc;
     int h_live = 0, beta_h_live = 0;
     DevBuf<EllCoeff> h_c, beta_h_c;        // prepared h, prepared beta_h
     DevBuf<G1Affine> tab;                  // g, gamma_g, com_f_basis[0..3]
-    std::vector<DevBuf<G1Affine>> slots;   // per slot: the tables of its two Pedersen bases
-    // per-call buffers, grown to the largest chunk seen; bytes are the caller's
-    DevBuf<uint8_t> b_ped, b_comf, b_comg, b_comq, b_evals, b_proofs, b_c, b_rho, b_rz, b_pokc, b_poks, b_k, b_flags, b_verdict;
+    PedersenSlots slots;                   // per slot: the tables of its two Pedersen bases
+    // per-call arrays with their row widths, grown to the largest chunk seen; bytes are the caller's
+    RowBuf b_ped{64}, b_comf{64}, b_comg{64}, b_comq{64}, b_evals{96}, b_proofs{288}, b_c{32}, b_rho{32}, b_rz{32}, b_pokc{32},
+        b_poks{32 * RP_N_RESP}, b_k{64}, b_flags{1}, b_verdict{1};
     DevBuf<uint32_t> b_scal;               // RV_N_SCALARS per showing, term-major
     DevBuf<G1XYZZ> b_part;                 // one partial per (term, showing)
     DevBuf<G1Affine> b_pair;               // total_c, then -total_w
     DevBuf<Fq12> b_miller;
-    ~cg_range_vk() {
-        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
+    ~cg_range_vk() { drain(); }            // before the buffers above are freed (key_handle.hpp)
 };
 
 extern "C" int cg_range_vk_load(cg_range_vk** out, const uint8_t* range_vk_bytes, uint64_t len, uint32_t n_bits, int32_t device) {
     if (!out || !range_vk_bytes) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    if (n_bits != 2 && n_bits != 4 && n_bits != 8 && n_bits != 16 && n_bits != 32)
-        return fail(CG_ERR_INVALID_ARGUMENT, "n_bits = %u: verify_n_bits takes a power of two, and a value has at most 32 bits here", n_bits);
+    if (int rc = check_range_bits(n_bits, "verify_n_bits")) return rc;
     try {
         // host only: every error of the bytes is reported before any HIP call
         if (len != RV_VK_BYTES)
@@ -247,12 +228,8 @@ extern "C" int cg_range_vk_load(cg_range_vk** out, const uint8_t* range_vk_bytes
         k->kc = range_consts((uint32_t)ilog2_ceil(n_bits));
         k->h_live = !h.is_inf();
         k->beta_h_live = !beta_h.is_inf();
-        int dev = device;
-        if (dev < 0) CG_HIP(hipGetDevice(&dev));
-        CG_HIP(hipSetDevice(dev));
-        k->device = dev;
-        CG_HIP(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
-        for (hipEvent_t& e : k->ev) CG_HIP(hipEventCreate(&e));
+        k->open(device);
+        k->timer.create();
         k->tab.alloc(tab.size());
         h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
         k->h_c.alloc(NC);
@@ -268,39 +245,14 @@ extern "C" int cg_range_vk_load(cg_range_vk** out, const uint8_t* range_vk_bytes
 
 extern "C" int cg_range_vk_add_bases(cg_range_vk* k, const uint8_t ped_bases[128], uint32_t* slot) {
     if (!k || !ped_bases || !slot) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    std::vector<G1Affine> bases(3, G1Affine::inf()), tab;
-    for (int i = 0; i < 2; ++i)
-        if (!checked_g1(ped_bases + 64 * i, bases[1 + i])) return fail(CG_ERR_INVALID_ARGUMENT, "Pedersen base %d is no valid G1 point", i);
-    try {
-        std::lock_guard<std::mutex> lk(k->mu);
-        if (k->slots.size() >= MAX_SLOTS) return fail(CG_ERR_INVALID_ARGUMENT, "all %u slots of this key are taken", MAX_SLOTS);
-        build_tables(bases, tab);
-        CG_HIP(hipSetDevice(k->device));
-        DevBuf<G1Affine> d(tab.size());
-        h2d_sync(d.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
-        k->slots.push_back(std::move(d));
-        *slot = (uint32_t)k->slots.size() - 1;
-        return CG_OK;
-    } catch (...) {
-        return translate_current_exception();
-    }
+    return k->slots.add(*k, ped_bases, slot);
 }
 
-extern "C" void cg_range_vk_free(cg_range_vk* k) {
-    if (!k) return;
-    (void)hipSetDevice(k->device);
-    delete k;                    // the destructor waits for the handle's stream
-}
+extern "C" void cg_range_vk_free(cg_range_vk* k) { free_handle(k); }
 
 // Diagnostic: what the kernels of the handle's last call took, by HIP events, summed over its chunks: the group stage
 // (k_rv_check, k_rv_terms, k_rv_sum) and the pairing (k_rv_miller, k_rv_final)
-extern "C" int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms) {
-    if (!k || !group_ms || !pairing_ms) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> lk(k->mu);
-    *group_ms = k->ms_group;
-    *pairing_ms = k->ms_pairing;
-    return CG_OK;
-}
+extern "C" int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms) { return last_kernel_ms(k, group_ms, pairing_ms); }
 
 extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
                                      const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c,
@@ -309,7 +261,7 @@ extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     try {
         std::lock_guard<std::mutex> lk(k->mu);
-        if (slot >= k->slots.size()) return fail(CG_ERR_INVALID_ARGUMENT, "slot %u was not registered on this key (cg_range_vk_add_bases)", slot);
+        const G1Affine* tab_slot = k->slots.table(slot, "cg_range_vk_add_bases");
         if (n == 0) return CG_OK;
         const bool pok = pok_c != nullptr;
         if (!com_f || !com_g || !com_q || !evals || !proofs || !c || !rho || !randomizers || !verdicts ||
@@ -318,66 +270,51 @@ extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < RVCHUNK ? n : RVCHUNK;
         const uint32_t n_fixed = RV_N_FIX_KZG + (pok ? N_FIX_DLEQ : 0), n_var = RV_N_VAR_KZG + (pok ? N_VAR_DLEQ : 0);
-        grow(k->b_ped, chunk * 64);
-        grow(k->b_comf, chunk * 64);
-        grow(k->b_comg, chunk * 64);
-        grow(k->b_comq, chunk * 64);
-        grow(k->b_evals, chunk * 96);
-        grow(k->b_proofs, chunk * 288);
-        grow(k->b_c, chunk * 32);
-        grow(k->b_rho, chunk * 32);
-        grow(k->b_rz, chunk * 32);
-        grow(k->b_pokc, chunk * 32);
-        grow(k->b_poks, chunk * 32 * RP_N_RESP);
-        grow(k->b_k, chunk * 64);
-        grow(k->b_flags, chunk);
-        grow(k->b_verdict, chunk);
+        for (RowBuf* b : {&k->b_ped, &k->b_comf, &k->b_comg, &k->b_comq, &k->b_evals, &k->b_proofs, &k->b_c, &k->b_rho, &k->b_rz, &k->b_pokc,
+                          &k->b_poks, &k->b_k, &k->b_flags, &k->b_verdict})
+            b->reserve(chunk);
         grow(k->b_scal, chunk * 8 * RV_N_SCALARS);
         grow(k->b_part, chunk * (uint64_t)(RV_N_FIX_KZG + N_FIX_DLEQ + RV_N_VAR_KZG + N_VAR_DLEQ));
         grow(k->b_pair, chunk * 2);
         grow(k->b_miller, chunk);
-        k->ms_group = k->ms_pairing = 0;
+        k->timer.reset();
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
             if (pok) {
-                rows_up(k->st, k->b_ped, ped_com, off, m, 64);
-                rows_up(k->st, k->b_pokc, pok_c, off, m, 32);
-                rows_up(k->st, k->b_poks, pok_s, off, m, 32 * RP_N_RESP);
+                k->b_ped.up(k->st, ped_com, off, m);
+                k->b_pokc.up(k->st, pok_c, off, m);
+                k->b_poks.up(k->st, pok_s, off, m);
             }
-            rows_up(k->st, k->b_comf, com_f, off, m, 64);
-            rows_up(k->st, k->b_comg, com_g, off, m, 64);
-            rows_up(k->st, k->b_comq, com_q, off, m, 64);
-            rows_up(k->st, k->b_evals, evals, off, m, 96);
-            rows_up(k->st, k->b_proofs, proofs, off, m, 288);
-            rows_up(k->st, k->b_c, c, off, m, 32);
-            rows_up(k->st, k->b_rho, rho, off, m, 32);
-            rows_up(k->st, k->b_rz, randomizers, off, m, 32);
-            auto w = [](const DevBuf<uint8_t>& b) { return (const uint32_t*)b.p; };
-            const RvArgs a{w(k->b_ped), w(k->b_comf), w(k->b_comg), w(k->b_comq), w(k->b_evals), w(k->b_proofs), w(k->b_c), w(k->b_rho),
-                           w(k->b_rz), pok ? w(k->b_pokc) : nullptr, pok ? w(k->b_poks) : nullptr, m, n_fixed, n_var};
+            k->b_comf.up(k->st, com_f, off, m);
+            k->b_comg.up(k->st, com_g, off, m);
+            k->b_comq.up(k->st, com_q, off, m);
+            k->b_evals.up(k->st, evals, off, m);
+            k->b_proofs.up(k->st, proofs, off, m);
+            k->b_c.up(k->st, c, off, m);
+            k->b_rho.up(k->st, rho, off, m);
+            k->b_rz.up(k->st, randomizers, off, m);
+            const RvArgs a{k->b_ped.words(), k->b_comf.words(), k->b_comg.words(), k->b_comq.words(), k->b_evals.words(), k->b_proofs.words(),
+                           k->b_c.words(), k->b_rho.words(), k->b_rz.words(), pok ? k->b_pokc.words() : nullptr,
+                           pok ? k->b_poks.words() : nullptr, m, n_fixed, n_var};
             const uint32_t grid = ceil_div(m, RVBLOCK);
-            CG_HIP(hipEventRecord(k->ev[0], k->st));
-            k_rv_check<<<grid, RVBLOCK, 0, k->st>>>(k->kc, a, k->b_scal.p, k->b_flags.p);
+            k->timer.mark(0, k->st);
+            k_rv_check<<<grid, RVBLOCK, 0, k->st>>>(k->kc, a, k->b_scal.p, k->b_flags.bytes());
             CG_KERNEL_CHECK();
             k_rv_terms<<<ceil_div(m * n_fixed, RVBLOCK) + ceil_div(m * n_var, RVBLOCK), RVBLOCK, 0, k->st>>>(
-                a, k->b_scal.p, k->b_flags.p, k->tab.p, k->slots[slot].p, k->b_part.p);
+                a, k->b_scal.p, k->b_flags.bytes(), k->tab.p, tab_slot, k->b_part.p);
             CG_KERNEL_CHECK();
-            k_rv_sum<<<ceil_div(m * (pok ? 4 : 2), RVBLOCK), RVBLOCK, 0, k->st>>>(a, k->b_flags.p, k->b_part.p, k->b_pair.p, (uint32_t*)k->b_k.p);
+            k_rv_sum<<<ceil_div(m * (pok ? 4 : 2), RVBLOCK), RVBLOCK, 0, k->st>>>(a, k->b_flags.bytes(), k->b_part.p, k->b_pair.p, k->b_k.words_mut());
             CG_KERNEL_CHECK();
-            CG_HIP(hipEventRecord(k->ev[1], k->st));
-            k_rv_miller<<<grid, RVBLOCK, 0, k->st>>>(k->b_pair.p, k->b_flags.p, m, k->beta_h_c.p, k->h_c.p, k->beta_h_live, k->h_live, k->b_miller.p);
+            k->timer.mark(1, k->st);
+            k_rv_miller<<<grid, RVBLOCK, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live, k->h_live, k->b_miller.p);
             CG_KERNEL_CHECK();
-            k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.p, m, k->b_verdict.p);
+            k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, k->b_verdict.bytes());
             CG_KERNEL_CHECK();
-            CG_HIP(hipEventRecord(k->ev[2], k->st));
-            rows_down(k->st, verdicts, k->b_verdict, off, m, 1);
-            if (pok) rows_down(k->st, k_out, k->b_k, off, m, 64);
+            k->timer.mark(2, k->st);
+            k->b_verdict.down(k->st, verdicts, off, m);
+            if (pok) k->b_k.down(k->st, k_out, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
-            float t0 = 0, t1 = 0;
-            CG_HIP(hipEventElapsedTime(&t0, k->ev[0], k->ev[1]));
-            CG_HIP(hipEventElapsedTime(&t1, k->ev[1], k->ev[2]));
-            k->ms_group += t0;
-            k->ms_pairing += t1;
+            k->timer.add();
         }
         return CG_OK;
     } catch (...) {

@@ -39,19 +39,17 @@
 //                 points and the k_i of DLogPoK::prove (creds/src/dlog.rs:60-75), affine, as ark-serialize writes them
 // cg_show_respond_batch, the responses once the host's transcript has produced c, is host arithmetic.
 //
-// Shared by the three entries: the double-and-add chains are fixed_base.hpp's scalar_mul_254_mixed; the section "ark-serialize
-// points" below reads and writes every point on the device; io_layout parses a call's io_types once, for the verifier's and
-// the creator's shapes alike; and the handle has one set of per-call buffers, named by what they hold.
+// Shared by the three entries: the double-and-add chains are fixed_base.hpp's scalar_mul_254_mixed; ark_codec.hpp reads and
+// writes every point on the device; io_layout parses a call's io_types once, for the verifier's and the creator's shapes
+// alike; and the handle has one set of per-call arrays, named by what they hold.  Shared with the range keys, in
+// key_handle.hpp: the handle's device, stream and lock, an array with its row width (RowBuf), the responses (dlog_respond).
 #include <memory>
 
-#include "ark_codec.hpp"
 #include "common.hpp"
 #include "fixed_base.hpp"
+#include "key_handle.hpp"
 #include "pairing.hpp"
 
-namespace cg {
-int translate_current_exception();
-}
 using namespace cg;
 
 namespace {
@@ -388,11 +386,8 @@ __global__ __launch_bounds__(VBLOCK) void k_mk_out(const uint32_t* __restrict__ 
 
 }  // namespace
 
-struct cg_pvk {
-    int device = 0;
+struct cg_pvk : KeyHandle {
     uint64_t n_inputs = 0;
-    hipStream_t st = nullptr;
-    std::mutex mu;
     G1Affine g0;
     Fq12 alpha_beta;
     int gamma_live = 0, delta_live = 0;
@@ -400,21 +395,22 @@ struct cg_pvk {
     DevBuf<G1Affine> tab;                  // gamma_abc_g1[1..], delta_g1, the G1 generator
     DevBuf<G2Affine> tab_g2;               // delta_g2
     DevBuf<EllCoeff> gamma_c, delta_c;
-    // per-call buffers, named by what they hold and shared by the three entries: each is grown, never shrunk, to the largest
-    // chunk and layout seen.  Bytes are ark-serialize's, as the caller passes and receives them.
-    DevBuf<uint8_t> b_proofs;              // proofs in: 256 B per item
-    DevBuf<uint8_t> b_inputs;              // scalars per (item, input): public inputs, revealed inputs, a client state's inputs
-    DevBuf<uint8_t> b_rows;                // scalars per (item, row): the responses of a showing, or a client state's rand
-    DevBuf<uint8_t> b_chal;                // the challenge c per item
-    DevBuf<uint8_t> b_comh, b_comm, b_k;   // com_hidden, the committed points and the k points per item, read or written
-    DevBuf<uint8_t> b_rproofs;             // re-randomised proofs out
-    DevBuf<uint8_t> b_status, b_verdict;
+    // per-call arrays, named by what they hold and shared by the three entries: each is grown, never shrunk, to the largest
+    // chunk and layout seen.  Bytes are ark-serialize's, as the caller passes and receives them; a width that depends on the
+    // call's io_types is set by the call.
+    RowBuf b_proofs{256};                  // proofs in
+    RowBuf b_inputs;                       // scalars per (item, input): public inputs, revealed inputs, a client state's inputs
+    RowBuf b_rows;                         // scalars per (item, row): the responses of a showing, or a client state's rand
+    RowBuf b_chal{32};                     // the challenge c per item
+    RowBuf b_comh{64}, b_comm, b_k;        // com_hidden, the committed points and the k points per item, read or written
+    RowBuf b_rproofs{256};                 // re-randomised proofs out
+    RowBuf b_status{1}, b_verdict{1};
     DevBuf<G1XYZZ> b_part;
     DevBuf<G2XYZZ> b_part_g2;
     DevBuf<ParsedProof> b_parsed;
     DevBuf<Fq12> b_miller;
     DevBuf<uint32_t> b_desc;               // the call's term descriptor: tab_of of k_show_terms, desc of k_mk_*
-    ~cg_pvk() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+    ~cg_pvk() { drain(); }                 // before the buffers above are freed (key_handle.hpp)
 };
 
 extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len, int32_t device) {
@@ -433,18 +429,14 @@ extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len,
         std::vector<G2Affine> tab_g2;                   // r2·delta_g2 of rerandomize_proof (prover.rs:247)
         build_tables(std::vector<G2Affine>{G2Affine::inf(), hk.vk.delta_g2}, tab_g2);
         const G2Affine g2_gen = g2_generator();
-        int dev = device;
-        if (dev < 0) CG_HIP(hipGetDevice(&dev));
-        CG_HIP(hipSetDevice(dev));
         std::unique_ptr<cg_pvk> k(new cg_pvk());
-        k->device = dev;
         k->n_inputs = hk.vk.gamma_abc.size() - 1;
         k->g0 = hk.vk.gamma_abc[0];
         k->alpha_beta = hk.alpha_beta;
         k->gamma_live = hk.gamma_live;
         k->delta_live = hk.delta_live;
         k->gamma_is_one = hk.vk.gamma_g2.x == g2_gen.x && hk.vk.gamma_g2.y == g2_gen.y;       // generator.rs:28
-        CG_HIP(hipStreamCreateWithFlags(&k->st, hipStreamNonBlocking));
+        k->open(device);
         k->tab.alloc(tab.size() ? tab.size() : 1);
         h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
         k->tab_g2.alloc(tab_g2.size());
@@ -479,32 +471,29 @@ extern "C" int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inpu
         CG_HIP(hipSetDevice(k->device));
         const uint64_t ell = n_inputs;
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
-        grow(k->b_inputs, chunk * ell * 32 + 32);
-        grow(k->b_proofs, chunk * 256);
-        grow(k->b_status, chunk);
-        grow(k->b_verdict, chunk);
+        k->b_inputs.reserve(chunk, ell * 32);
+        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict}) b->reserve(chunk);
         grow(k->b_part, chunk * ell + 1);
         grow(k->b_parsed, chunk);
         grow(k->b_miller, chunk);
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            rows_up(k->st, k->b_inputs, inputs, off, m, ell * 32);
-            rows_up(k->st, k->b_proofs, proofs, off, m, 256);
+            k->b_inputs.up(k->st, inputs, off, m);
+            k->b_proofs.up(k->st, proofs, off, m);
             if (ell) {
-                k_vfy_inputs<<<ceil_div(m * ell, VBLOCK), VBLOCK, 0, k->st>>>((const uint32_t*)k->b_inputs.p, m, (uint32_t)ell,
-                                                                             k->tab.p, k->b_part.p);
+                k_vfy_inputs<<<ceil_div(m * ell, VBLOCK), VBLOCK, 0, k->st>>>(k->b_inputs.words(), m, (uint32_t)ell, k->tab.p, k->b_part.p);
                 CG_KERNEL_CHECK();
             }
             const uint32_t grid = ceil_div(m, VBLOCK);
-            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->b_proofs.p, (const uint32_t*)k->b_inputs.p, m, (uint32_t)ell,
-                                                    k->b_part.p, k->g0, k->b_parsed.p, k->b_status.p);
+            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>(k->b_proofs.words(), k->b_inputs.words(), m, (uint32_t)ell, k->b_part.p, k->g0,
+                                                    k->b_parsed.p, k->b_status.bytes());
             CG_KERNEL_CHECK();
-            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
+            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.bytes(), m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
                                                      k->delta_live, k->b_miller.p);
             CG_KERNEL_CHECK();
-            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.p, m, k->alpha_beta, k->b_verdict.p);
+            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.bytes(), m, k->alpha_beta, k->b_verdict.bytes());
             CG_KERNEL_CHECK();
-            rows_down(k->st, verdicts, k->b_verdict, off, m, 1);
+            k->b_verdict.down(k->st, verdicts, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -609,55 +598,51 @@ extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
         const uint32_t n_stmt = sh.n_com + 1;
-        grow(k->b_proofs, chunk * 256);
-        grow(k->b_status, chunk);
-        grow(k->b_verdict, chunk);
+        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict, &k->b_comh, &k->b_chal}) b->reserve(chunk);
+        k->b_inputs.reserve(chunk, sh.n_rev * 32);
+        k->b_comm.reserve(chunk, sh.n_com * 64);
+        k->b_rows.reserve(chunk, sh.n_resp * 32);
+        k->b_k.reserve(chunk, n_stmt * 32);
         grow(k->b_parsed, chunk);
         grow(k->b_miller, chunk);
         grow(k->b_part, chunk * sh.n_terms + 1);
-        grow(k->b_inputs, chunk * sh.n_rev * 32 + 32);
-        grow(k->b_comh, chunk * 64);
-        grow(k->b_comm, chunk * sh.n_com * 64 + 64);
-        grow(k->b_chal, chunk * 32);
-        grow(k->b_rows, chunk * sh.n_resp * 32);
-        grow(k->b_k, chunk * n_stmt * 32);
         grow(k->b_desc, tab_of.size() + 1);
         h2d_sync(k->b_desc.p, tab_of.data(), tab_of.size() * sizeof(uint32_t), k->st);
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            rows_up(k->st, k->b_proofs, rand_proofs, off, m, 256);
-            rows_up(k->st, k->b_comh, com_hidden, off, m, 64);
-            rows_up(k->st, k->b_inputs, revealed, off, m, sh.n_rev * 32);
-            rows_up(k->st, k->b_comm, committed, off, m, sh.n_com * 64);
+            k->b_proofs.up(k->st, rand_proofs, off, m);
+            k->b_comh.up(k->st, com_hidden, off, m);
+            k->b_inputs.up(k->st, revealed, off, m);
+            k->b_comm.up(k->st, committed, off, m);
             if (pok) {
-                rows_up(k->st, k->b_chal, pok_c, off, m, 32);
-                rows_up(k->st, k->b_rows, pok_s, off, m, sh.n_resp * 32);
+                k->b_chal.up(k->st, pok_c, off, m);
+                k->b_rows.up(k->st, pok_s, off, m);
             }
-            const uint32_t *d_rev = (const uint32_t*)k->b_inputs.p, *d_s = (const uint32_t*)k->b_rows.p, *d_c = (const uint32_t*)k->b_chal.p,
-                           *d_comh = (const uint32_t*)k->b_comh.p, *d_comm = (const uint32_t*)k->b_comm.p;
+            const uint32_t *d_rev = k->b_inputs.words(), *d_s = k->b_rows.words(), *d_c = k->b_chal.words(), *d_comh = k->b_comh.words(),
+                           *d_comm = k->b_comm.words();
             if (sh.n_terms) {
                 const uint32_t blocks = ceil_div(m * sh.n_fixed, VBLOCK) + ceil_div(m * sh.n_var, VBLOCK);
                 k_show_terms<<<blocks, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_desc.p, k->tab.p, k->b_part.p);
                 CG_KERNEL_CHECK();
             }
             const uint32_t grid = ceil_div(m, VBLOCK);
-            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>((const uint32_t*)k->b_proofs.p, d_rev, m, 0u, k->b_part.p, k->g0, k->b_parsed.p,
-                                                    k->b_status.p);
+            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>(k->b_proofs.words(), d_rev, m, 0u, k->b_part.p, k->g0, k->b_parsed.p,
+                                                    k->b_status.bytes());
             CG_KERNEL_CHECK();
             k_show_check<<<grid, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_part.p, k->g0, k->b_parsed.p,
-                                                     k->b_status.p);
+                                                     k->b_status.bytes());
             CG_KERNEL_CHECK();
             if (pok) {
-                k_show_k<<<ceil_div(m * n_stmt, VBLOCK), VBLOCK, 0, k->st>>>(m, sh, k->b_part.p, k->b_status.p, (uint32_t*)k->b_k.p);
+                k_show_k<<<ceil_div(m * n_stmt, VBLOCK), VBLOCK, 0, k->st>>>(m, sh, k->b_part.p, k->b_status.bytes(), k->b_k.words_mut());
                 CG_KERNEL_CHECK();
             }
-            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.p, m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
+            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.bytes(), m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
                                                      k->delta_live, k->b_miller.p);
             CG_KERNEL_CHECK();
-            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.p, m, k->alpha_beta, k->b_verdict.p);
+            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.bytes(), m, k->alpha_beta, k->b_verdict.bytes());
             CG_KERNEL_CHECK();
-            rows_down(k->st, verdicts, k->b_verdict, off, m, 1);
-            if (pok) rows_down(k->st, k_out, k->b_k, off, m, n_stmt * 32);
+            k->b_verdict.down(k->st, verdicts, off, m);
+            if (pok) k->b_k.down(k->st, k_out, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -692,40 +677,37 @@ extern "C" int cg_show_commit_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
         const uint32_t n_stmt = sh.n_com + 1;
-        grow(k->b_proofs, chunk * 256);
-        grow(k->b_inputs, chunk * sh.n_io * 32 + 32);
-        grow(k->b_status, chunk);
+        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_rproofs, &k->b_comh}) b->reserve(chunk);
+        k->b_inputs.reserve(chunk, sh.n_io * 32);
+        k->b_rows.reserve(chunk, sh.n_rand * 32);
+        k->b_comm.reserve(chunk, sh.n_com * 64);
+        k->b_k.reserve(chunk, n_stmt * 32);
         grow(k->b_part, chunk * sh.n_terms + 1);
-        grow(k->b_rows, chunk * sh.n_rand * 32);
         grow(k->b_part_g2, chunk);
-        grow(k->b_rproofs, chunk * 256);
-        grow(k->b_comh, chunk * 64);
-        grow(k->b_comm, chunk * sh.n_com * 64 + 64);
-        grow(k->b_k, chunk * n_stmt * 32);
         grow(k->b_desc, desc.size());
         h2d_sync(k->b_desc.p, desc.data(), desc.size() * sizeof(uint32_t), k->st);
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            rows_up(k->st, k->b_proofs, proofs, off, m, 256);
-            rows_up(k->st, k->b_inputs, inputs, off, m, sh.n_io * 32);
-            rows_up(k->st, k->b_rows, rand, off, m, sh.n_rand * 32);
-            const uint32_t *d_pr = (const uint32_t*)k->b_proofs.p, *d_in = (const uint32_t*)k->b_inputs.p, *d_rd = (const uint32_t*)k->b_rows.p;
-            k_mk_check<<<ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_in, d_rd, m, sh, k->b_desc.p, k->b_status.p);
+            k->b_proofs.up(k->st, proofs, off, m);
+            k->b_inputs.up(k->st, inputs, off, m);
+            k->b_rows.up(k->st, rand, off, m);
+            const uint32_t *d_pr = k->b_proofs.words(), *d_in = k->b_inputs.words(), *d_rd = k->b_rows.words();
+            k_mk_check<<<ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_in, d_rd, m, sh, k->b_desc.p, k->b_status.bytes());
             CG_KERNEL_CHECK();
             k_mk_fixed<<<ceil_div(m * sh.n_fix, VBLOCK), VBLOCK, 0, k->st>>>(d_in, d_rd, m, sh, k->b_desc.p, k->tab.p, k->b_part.p);
             CG_KERNEL_CHECK();
             k_mk_var<<<ceil_div(2 * m, VBLOCK) + ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_rd, m, sh, k->tab_g2.p, k->b_part.p,
                                                                                          k->b_part_g2.p);
             CG_KERNEL_CHECK();
-            k_mk_out<<<ceil_div(m * sh.n_out, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, k->b_part.p, k->b_part_g2.p, k->b_status.p,
-                                                                          (uint32_t*)k->b_rproofs.p, (uint32_t*)k->b_comh.p,
-                                                                          (uint32_t*)k->b_comm.p, (uint32_t*)k->b_k.p);
+            k_mk_out<<<ceil_div(m * sh.n_out, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, k->b_part.p, k->b_part_g2.p, k->b_status.bytes(),
+                                                                          k->b_rproofs.words_mut(), k->b_comh.words_mut(),
+                                                                          k->b_comm.words_mut(), k->b_k.words_mut());
             CG_KERNEL_CHECK();
-            rows_down(k->st, rand_proofs, k->b_rproofs, off, m, 256);
-            rows_down(k->st, com_hidden, k->b_comh, off, m, 64);
-            rows_down(k->st, committed, k->b_comm, off, m, sh.n_com * 64);
-            rows_down(k->st, k_out, k->b_k, off, m, n_stmt * 32);
-            rows_down(k->st, status, k->b_status, off, m, 1);
+            k->b_rproofs.down(k->st, rand_proofs, off, m);
+            k->b_comh.down(k->st, com_hidden, off, m);
+            k->b_comm.down(k->st, committed, off, m);
+            k->b_k.down(k->st, k_out, off, m);
+            k->b_status.down(k->st, status, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -748,30 +730,10 @@ extern "C" int cg_show_respond_batch(const uint8_t* io_types, uint64_t n_io, con
         return src[t] & MK_RAND ? rand + 32 * (p * sh.n_rand + (src[t] & ~MK_RAND)) : inputs + 32 * (p * sh.n_io + src[t]);
     };
     auto nonce = [&](uint64_t p, uint32_t t) { return rand + 32 * (p * sh.n_rand + 3 + sh.n_com + t); };
-    for (uint64_t p = 0; p < n; ++p) {                            // every value first: an error writes nothing
-        if (status && status[p] != CG_SHOW_MADE) continue;
-        bool ok = scalar_is_canonical(pok_c + 32 * p);
-        for (uint32_t t = 0; t < sh.n_resp; ++t) ok = ok && scalar_is_canonical(secret(p, t)) && scalar_is_canonical(nonce(p, t));
-        if (!ok) return fail(CG_ERR_INVALID_ARGUMENT, "showing %llu: an input, a rand scalar or c is not below the scalar modulus", (unsigned long long)p);
-    }
-    for (uint64_t p = 0; p < n; ++p) {
-        uint8_t* out = pok_s + 32 * p * sh.n_resp;
-        if (status && status[p] != CG_SHOW_MADE) {
-            memset(out, 0, 32 * (size_t)sh.n_resp);
-            continue;
-        }
-        const Fr c = to_mont(fp_from_bytes<Fr>(pok_c + 32 * p));             // c·R times a canonical x is c·x, canonical
-        for (uint32_t t = 0; t < sh.n_resp; ++t)
-            fp_to_bytes(sub(fp_from_bytes<Fr>(nonce(p, t)), mul(c, fp_from_bytes<Fr>(secret(p, t)))), out + 32 * t);
-    }
-    return CG_OK;
+    return dlog_respond(n, sh.n_resp, status, pok_c, secret, nonce, pok_s, "an input");
 }
 
-extern "C" void cg_pvk_free(cg_pvk* k) {
-    if (!k) return;
-    (void)hipSetDevice(k->device);
-    delete k;                    // the destructor waits for the handle's stream
-}
+extern "C" void cg_pvk_free(cg_pvk* k) { free_handle(k); }
 
 // prepare_verifying_key (verifier.rs:13-20) on the host: one pairing and two G2Prepared, written as ark-serialize writes a
 // PreparedVerifyingKey (data_structures.rs:62-71): the VerifyingKey bytes as given, alpha_g1_beta_g2, gamma_g2_neg_pc,

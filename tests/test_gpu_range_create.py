@@ -312,6 +312,26 @@ def test_two_slots_on_one_handle(cc, key4):
     assert got_a[2][0, 3].tobytes() == got_b[2][0, 3].tobytes()
 
 
+def test_the_slot_limit_and_the_last_slot(cc):
+    """A key takes 64 slots (csrc/key_handle.hpp, PedersenSlots::MAX_SLOTS): the 65th registration is an argument error, and
+    a commitment on slot 63 is the one slot 0 makes when both hold the same bases."""
+    K = RV.key(4)
+    pair = [o.g1_uncompressed(P) for P in bases_of()]
+    with cc.RangeProofKey(K.data, 4) as gpu:
+        assert [gpu.add_bases(*pair) for _ in range(64)] == list(range(64))
+        with pytest.raises(cc.CrescentGpuError, match="slots of this key are taken") as e:
+            gpu.add_bases(*pair)
+        assert e.value.code == INVALID_ARGUMENT
+        x = make(K, bases_of(), *draw(random.Random(24), 4))
+        ob, rb, _, _, _ = RV.pack([x])
+        first = cc.Groth16.range_commit_batch_packed(gpu, 0, ob, rb)
+        last = cc.Groth16.range_commit_batch_packed(gpu, 63, ob, rb)
+    w_f, w_g, w_ts = RV.expected_commit(x)
+    assert first[0][0].tobytes() == w_f and first[1][0].tobytes() == w_g and first[2][0].tobytes() == w_ts and first[3][0] == RV.MADE
+    for a, b in zip(first, last):
+        assert a.tobytes() == b.tobytes()
+
+
 def test_argument_errors_under_a_handle(cc, key4):
     K, gpu, slot = key4
     L = cc.lib()

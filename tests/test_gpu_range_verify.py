@@ -327,6 +327,25 @@ def test_round_trip_with_show_range_batch(cc, vk4):
     assert cc.Groth16.verify_range_batch(gpu, slot, [], [], challenge) == []
 
 
+def test_the_slot_limit_and_the_last_slot(cc, vk4, valid):
+    """A key takes 64 slots (csrc/key_handle.hpp, PedersenSlots::MAX_SLOTS): the 65th registration is an argument error, and
+    a proof verified on slot 63 gets the verdict and the k bytes slot 0 gives when both hold the same bases."""
+    K = vk4[0]
+    pair = [unc(P) for P in V.bases_of()]
+    gpu, slot = load(cc, K)
+    try:
+        assert slot == 0 and [gpu.add_bases(*pair) for _ in range(63)] == list(range(1, 64))
+        with pytest.raises(cc.CrescentGpuError, match="slots of this key are taken") as e:
+            gpu.add_bases(*pair)
+        assert e.value.code == INVALID_ARGUMENT
+        rows = valid[0][18:19]
+        (w_v, w_k), = check(cc, gpu, 0, K, rows)
+        verdicts, k = run(cc, gpu, 63, rows)
+        assert w_v == ACCEPT and verdicts[0] == w_v and k[0].tobytes() == w_k
+    finally:
+        gpu.close()
+
+
 def test_argument_errors_under_a_handle(cc, vk4):
     K, gpu, slot = vk4
     L = cc.lib()
