@@ -242,6 +242,8 @@ _SIGNATURES = {
     "cg_client_state_free": (None, [C.c_void_p]),
     "cg_pvk_load": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_int32]),
     "cg_pvk_num_inputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "cg_pvk_set_latency_mode": (C.c_int, [C.c_void_p, C.c_int32]),
+    "cg_pvk_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cg_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cg_verify_show_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
@@ -264,6 +266,7 @@ _SIGNATURES = {
     "cg_range_vk_load": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]),
     "cg_range_vk_add_bases": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "cg_range_vk_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "cg_range_vk_set_latency_mode": (C.c_int, [C.c_void_p, C.c_int32]),
     "cg_range_vk_free": (None, [C.c_void_p]),
     "cg_range_verify_batch": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint64, C.c_void_p, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -852,6 +855,16 @@ class _Handle:
             self.close()
         except Exception:
             pass
+
+
+class _LatencyMode:
+    """The pairing stage's arrangement of the two verifying keys (PreparedVerifyingKey, RangeVerifyingKey);
+    `_set_latency_mode` names the C symbol."""
+
+    def set_latency(self, on: bool) -> None:
+        """True: one workgroup per proof, for a host that answers one request at a time; False (the default): one lane per
+        proof, for batches (cg_pvk_set_latency_mode / cg_range_vk_set_latency_mode).  The verdicts are the same."""
+        _check(getattr(lib(), self._set_latency_mode)(self._h, 1 if on else 0))
 
 
 class _RangeSlots:
@@ -1466,16 +1479,25 @@ class Groth16:
         cls._cache.clear()
 
 
-class PreparedVerifyingKey(_Handle):
+class PreparedVerifyingKey(_LatencyMode, _Handle):
     """forks/groth16/src/data_structures.rs:62-71, parsed from its serialized bytes (`deserialize_uncompressed_unchecked`,
     creds/src/utils.rs:186) and resident on a GPU (cg_pvk_load): alpha_g1_beta_g2, the prepared gamma / delta lines and
-    fixed-base tables of gamma_abc_g1.  Use as a context manager or close()."""
-    _free = "cg_pvk_free"
+    fixed-base tables of gamma_abc_g1.  latency=True switches the handle to the one-workgroup-per-proof arrangement
+    (set_latency).  Use as a context manager or close()."""
+    _free, _set_latency_mode = "cg_pvk_free", "cg_pvk_set_latency_mode"
 
-    def __init__(self, pvk_bytes, device: int = -1):
+    def __init__(self, pvk_bytes, device: int = -1, latency: bool = False):
         b = _u8(pvk_bytes)
         self._h = C.c_void_p()
         _check(lib().cg_pvk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, device))
+        if latency:
+            self.set_latency(True)
+
+    def last_kernel_ms(self) -> Tuple[float, float]:
+        """HIP-event milliseconds of the last verifying call on this key: (group stage, pairing)"""
+        a, b = C.c_float(), C.c_float()
+        _check(lib().cg_pvk_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
 
     @property
     def num_inputs(self) -> int:
@@ -1513,17 +1535,21 @@ def _g1_compress(unc) -> np.ndarray:
     return np.frombuffer(bytes(out), np.uint8)
 
 
-class RangeVerifyingKey(_RangeSlots, _Handle):
+class RangeVerifyingKey(_LatencyMode, _RangeSlots, _Handle):
     """`RangeProofVK` (creds/src/rangeproof.rs:74-78) from the 640 bytes of range_vk.bin, resident on a GPU with h and
     beta_h prepared and fixed-base tables of g, gamma_g and com_f_basis, for proofs of n_bits bits (cg_range_vk_load).
+    latency=True switches the handle to the one-workgroup-per-proof pairing (set_latency).
     Use as a context manager or close()."""
     _free, _add_bases, _last_kernel_ms = "cg_range_vk_free", "cg_range_vk_add_bases", "cg_range_vk_last_kernel_ms"
+    _set_latency_mode = "cg_range_vk_set_latency_mode"
 
-    def __init__(self, range_vk_bytes, n_bits: int, device: int = -1):
+    def __init__(self, range_vk_bytes, n_bits: int, device: int = -1, latency: bool = False):
         b = _u8(range_vk_bytes)
         self.n_bits = int(n_bits)
         self._h = C.c_void_p()
         _check(lib().cg_range_vk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, self.n_bits, device))
+        if latency:
+            self.set_latency(True)
 
 
 @dataclass

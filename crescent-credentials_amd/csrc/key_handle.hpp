@@ -65,6 +65,16 @@ int last_kernel_ms(K* k, float* first, float* second) {
     return CG_OK;
 }
 
+// cg_pvk_set_latency_mode / cg_range_vk_set_latency_mode: a handle with a `latency` flag, taken under its lock
+template <class K>
+int set_latency_mode(K* k, int32_t on) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (on != 0 && on != 1) return fail(CG_ERR_INVALID_ARGUMENT, "latency mode is 0 or 1, not %d", on);
+    std::lock_guard<std::mutex> lk(k->mu);
+    k->latency = on != 0;
+    return CG_OK;
+}
+
 // The Pedersen bases registered on a range key: per slot the fixed-base tables of one pair (2 x 1 MB on the device).
 struct PedersenSlots {
     static constexpr uint32_t MAX_SLOTS = 64;

@@ -30,6 +30,7 @@
 #include "fixed_base.hpp"
 #include "key_handle.hpp"
 #include "pairing.hpp"
+#include "pairing_team.hpp"
 #include "rangeverify.hpp"
 
 using namespace cg;
@@ -183,10 +184,42 @@ __global__ __launch_bounds__(RVBLOCK) void k_rv_final(const Fq12* __restrict__ f
     verdict[p] = ok ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
 }
 
+// the latency arrangement of the two kernels above (cg_range_vk_set_latency_mode): one workgroup per showing, pairing_team.hpp
+__global__ __launch_bounds__(TEAM_WIDTH) void k_rv_lone_miller(const G1Affine* __restrict__ pair_pts, const uint8_t* __restrict__ flags, uint64_t m,
+                                                             const EllCoeff* beta_h_c, const EllCoeff* h_c, int beta_h_live, int h_live,
+                                                             Fq12* __restrict__ f) {
+    __shared__ TeamMem sh;
+    const uint64_t p = blockIdx.x;
+    // uniform: p is the workgroup's index and flags[p] one byte that every lane of it reads
+    if (p >= m || (flags[p] & RV_MALFORMED)) return;
+    MillerPairs mp;
+    mp.p[0] = pair_pts[m + p]; mp.q[0] = G2Affine::inf(); mp.tab[0] = beta_h_c; mp.live[0] = !mp.p[0].is_inf() && beta_h_live;
+    mp.p[1] = pair_pts[p]; mp.q[1] = G2Affine::inf(); mp.tab[1] = h_c; mp.live[1] = !mp.p[1].is_inf() && h_live;
+    mp.p[2] = G1Affine::inf(); mp.q[2] = G2Affine::inf(); mp.tab[2] = nullptr; mp.live[2] = false;
+    team_miller_to<0>(sh, mp, f + p);
+}
+
+__global__ __launch_bounds__(TEAM_WIDTH) void k_rv_lone_final(const Fq12* __restrict__ f, const uint8_t* __restrict__ flags, uint64_t m,
+                                                            uint8_t* __restrict__ verdict) {
+    __shared__ TeamMem sh;
+    const uint64_t p = blockIdx.x;
+    if (p >= m) return;                          // uniform: the workgroup's index
+    WaveLane ln{(int)threadIdx.x};
+    const uint32_t fl = flags[p];
+    if (fl & RV_MALFORMED) {                     // uniform: one byte that every lane of the workgroup reads
+        if (ln.lane == 0) verdict[p] = CG_VERIFY_MALFORMED;
+        return;
+    }
+    const bool some = team_final_of(sh, ln, f + p);
+    const bool ok = some && team_is_one(ln, sh, tp::reg(0)) && (fl & RV_IDENTITY) && (fl & RV_EQ_POS);
+    if (ln.lane == 0) verdict[p] = ok ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
+}
+
 }  // namespace
 
 struct cg_range_vk : KeyHandle {
     uint32_t n_bits = 0;
+    bool latency = false;                  // the pairing stage's arrangement (cg_range_vk_set_latency_mode)
     StageTimer timer;                      // the group stage, the pairing
     RangeConsts kc;
     int h_live = 0, beta_h_live = 0;
@@ -250,6 +283,8 @@ extern "C" int cg_range_vk_add_bases(cg_range_vk* k, const uint8_t ped_bases[128
 
 extern "C" void cg_range_vk_free(cg_range_vk* k) { free_handle(k); }
 
+extern "C" int cg_range_vk_set_latency_mode(cg_range_vk* k, int32_t on) { return set_latency_mode(k, on); }
+
 // Diagnostic: what the kernels of the handle's last call took, by HIP events, summed over its chunks: the group stage
 // (k_rv_check, k_rv_terms, k_rv_sum) and the pairing (k_rv_miller, k_rv_final)
 extern "C" int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms) { return last_kernel_ms(k, group_ms, pairing_ms); }
@@ -306,9 +341,16 @@ extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_
             k_rv_sum<<<ceil_div(m * (pok ? 4 : 2), RVBLOCK), RVBLOCK, 0, k->st>>>(a, k->b_flags.bytes(), k->b_part.p, k->b_pair.p, k->b_k.words_mut());
             CG_KERNEL_CHECK();
             k->timer.mark(1, k->st);
-            k_rv_miller<<<grid, RVBLOCK, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live, k->h_live, k->b_miller.p);
-            CG_KERNEL_CHECK();
-            k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, k->b_verdict.bytes());
+            if (k->latency) {
+                k_rv_lone_miller<<<(uint32_t)m, TEAM_WIDTH, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live,
+                                                                       k->h_live, k->b_miller.p);
+                CG_KERNEL_CHECK();
+                k_rv_lone_final<<<(uint32_t)m, TEAM_WIDTH, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, k->b_verdict.bytes());
+            } else {
+                k_rv_miller<<<grid, RVBLOCK, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live, k->h_live, k->b_miller.p);
+                CG_KERNEL_CHECK();
+                k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, k->b_verdict.bytes());
+            }
             CG_KERNEL_CHECK();
             k->timer.mark(2, k->st);
             k->b_verdict.down(k->st, verdicts, off, m);

@@ -49,6 +49,7 @@
 #include "fixed_base.hpp"
 #include "key_handle.hpp"
 #include "pairing.hpp"
+#include "pairing_team.hpp"
 
 using namespace cg;
 
@@ -124,6 +125,8 @@ __global__ __launch_bounds__(VBLOCK) void k_vfy_inputs(const uint32_t* __restric
     part[t] = fixed_base_mul(tab + (uint64_t)i * FB_NWIN * FB_WIN, x);
 }
 
+// SUBGROUP = false leaves [r]B = O to k_lone_subgroup (the latency arrangement)
+template <bool SUBGROUP>
 __global__ __launch_bounds__(VBLOCK) void k_vfy_check(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ inputs,
                                                      uint64_t n, uint32_t ell, const G1XYZZ* __restrict__ part, G1Affine g0,
                                                      ParsedProof* __restrict__ out, uint8_t* __restrict__ status) {
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(VBLOCK) void k_vfy_check(const uint32_t* __restrict
     bool ok = true;
     ParsedProof pp;
     pp.a = dev_g1(w, ok);
-    pp.b = dev_g2(w + 16, ok);
+    pp.b = dev_g2<SUBGROUP>(w + 16, ok);
     pp.c = dev_g1(w + 48, ok);
     G1XYZZ acc = G1XYZZ::from_affine(g0);
     for (uint32_t i = 0; i < ell; ++i) {
@@ -169,6 +172,56 @@ __global__ __launch_bounds__(VBLOCK) void k_vfy_final(const Fq12* __restrict__ f
     Fq12 r;
     const bool some = final_exponentiation(f[p], r);
     verdict[p] = some && r == alpha_beta ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
+}
+
+// ---- the latency arrangement (cg_pvk_set_latency_mode): one workgroup per proof, pairing_team.hpp ------------------------
+// the 254-step [r]B = O chain of k_vfy_check, on the handle's second stream beside the pairing, which does not need it:
+// one lane per proof, B read as k_mk_check reads it.  A B that fails an earlier check is k_vfy_check<false>'s to report.
+__global__ __launch_bounds__(VBLOCK) void k_lone_subgroup(const uint32_t* __restrict__ proofs, uint64_t n, uint8_t* __restrict__ in_g2) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    bool ok = true;
+    const G2Affine b = dev_g2<false>(proofs + 64 * p + 16, ok);
+    in_g2[p] = !ok || b.is_inf() || g2_in_subgroup(b);
+}
+
+__global__ __launch_bounds__(TEAM_WIDTH) void k_lone_miller(const ParsedProof* __restrict__ in, const uint8_t* __restrict__ status,
+                                                          uint64_t n, const EllCoeff* gamma_c, const EllCoeff* delta_c,
+                                                          int gamma_live, int delta_live, Fq12* __restrict__ f) {
+    __shared__ TeamMem sh;
+    const uint64_t p = blockIdx.x;
+    // uniform: p is the workgroup's index and status[p] one byte that every lane of it reads
+    if (p >= n || status[p] != ST_OK) return;
+    const ParsedProof& pp = in[p];
+    MillerPairs mp;
+    mp.p[0] = pp.a; mp.q[0] = pp.b; mp.tab[0] = nullptr; mp.live[0] = !mp.p[0].is_inf() && !mp.q[0].is_inf();
+    mp.p[1] = pp.pi; mp.q[1] = G2Affine::inf(); mp.tab[1] = gamma_c; mp.live[1] = !mp.p[1].is_inf() && gamma_live;
+    mp.p[2] = pp.c; mp.q[2] = G2Affine::inf(); mp.tab[2] = delta_c; mp.live[2] = !mp.p[2].is_inf() && delta_live;
+    team_miller_to<1>(sh, mp, f + p);
+}
+
+__global__ __launch_bounds__(TEAM_WIDTH) void k_lone_final(const Fq12* __restrict__ f, const uint8_t* __restrict__ status, uint64_t n,
+                                                         Fq12 alpha_beta, uint8_t* __restrict__ verdict) {
+    __shared__ TeamMem sh;
+    const uint64_t p = blockIdx.x;
+    if (p >= n) return;                          // uniform: the workgroup's index
+    WaveLane ln{(int)threadIdx.x};
+    if (status[p] != ST_OK) {                    // uniform: one byte that every lane of the workgroup reads
+        if (ln.lane == 0) verdict[p] = CG_VERIFY_MALFORMED;
+        return;
+    }
+    const bool some = team_final_of(sh, ln, f + p);
+    const bool eq = some && team_equals(ln, sh, tp::reg(0), alpha_beta);
+    if (ln.lane == 0) verdict[p] = eq ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
+}
+
+// after the two streams have met: a B outside the r-torsion makes the proof malformed, as k_vfy_check<true> would have
+__global__ __launch_bounds__(VBLOCK) void k_lone_join(const uint8_t* __restrict__ in_g2, uint64_t n, uint8_t* __restrict__ status,
+                                                     uint8_t* __restrict__ verdict) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || in_g2[p]) return;
+    status[p] = ST_MALFORMED;
+    verdict[p] = CG_VERIFY_MALFORMED;
 }
 
 // ---- showings (ShowGroth16::verify, groth16rand.rs:232-306) ------------------------------------------------------------
@@ -410,7 +463,59 @@ struct cg_pvk : KeyHandle {
     DevBuf<ParsedProof> b_parsed;
     DevBuf<Fq12> b_miller;
     DevBuf<uint32_t> b_desc;               // the call's term descriptor: tab_of of k_show_terms, desc of k_mk_*
-    ~cg_pvk() { drain(); }                 // before the buffers above are freed (key_handle.hpp)
+    // the two arrangements of the pairing stage (cg_pvk_set_latency_mode); the latency one also runs [r]B = O on a second stream
+    bool latency = false;
+    StageTimer timer;                      // the group stage, the pairing
+    hipStream_t st2 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    RowBuf b_in_g2{1};
+    void open_second() {
+        CG_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
+        CG_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+        CG_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    }
+    ~cg_pvk() {                            // both streams are waited for before the buffers above are freed (key_handle.hpp)
+        if (st2) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); }
+        drain();
+        for (hipEvent_t e : {ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+    }
+
+    // the stages both verifying entries share, on a chunk of m proofs already in b_proofs; all under the handle's lock
+    // right after the proofs' copy: in the latency arrangement the subgroup chain starts on the second stream
+    void proofs_up(const uint8_t* proofs, uint64_t off, uint64_t m) {
+        b_proofs.up(st, proofs, off, m);
+        if (!latency) return;
+        CG_HIP(hipEventRecord(ev_fork, st));
+        CG_HIP(hipStreamWaitEvent(st2, ev_fork, 0));
+        k_lone_subgroup<<<ceil_div(m, VBLOCK), VBLOCK, 0, st2>>>(b_proofs.words(), m, b_in_g2.bytes());
+        CG_KERNEL_CHECK();
+        CG_HIP(hipEventRecord(ev_join, st2));
+    }
+    void check(uint64_t m, const uint32_t* d_inputs, uint32_t ell) {
+        const uint32_t grid = ceil_div(m, VBLOCK);
+        if (latency) k_vfy_check<false><<<grid, VBLOCK, 0, st>>>(b_proofs.words(), d_inputs, m, ell, b_part.p, g0, b_parsed.p, b_status.bytes());
+        else k_vfy_check<true><<<grid, VBLOCK, 0, st>>>(b_proofs.words(), d_inputs, m, ell, b_part.p, g0, b_parsed.p, b_status.bytes());
+        CG_KERNEL_CHECK();
+    }
+    // Miller loop and final exponentiation; in the latency arrangement then the meeting with the second stream, after
+    // which status and verdict are what the wide arrangement writes
+    void pairing(uint64_t m) {
+        if (latency) {
+            k_lone_miller<<<(uint32_t)m, TEAM_WIDTH, 0, st>>>(b_parsed.p, b_status.bytes(), m, gamma_c.p, delta_c.p, gamma_live, delta_live, b_miller.p);
+            CG_KERNEL_CHECK();
+            k_lone_final<<<(uint32_t)m, TEAM_WIDTH, 0, st>>>(b_miller.p, b_status.bytes(), m, alpha_beta, b_verdict.bytes());
+            CG_KERNEL_CHECK();
+            CG_HIP(hipStreamWaitEvent(st, ev_join, 0));
+            k_lone_join<<<ceil_div(m, VBLOCK), VBLOCK, 0, st>>>(b_in_g2.bytes(), m, b_status.bytes(), b_verdict.bytes());
+            CG_KERNEL_CHECK();
+            return;
+        }
+        const uint32_t grid = ceil_div(m, VBLOCK);
+        k_vfy_miller<<<grid, VBLOCK, 0, st>>>(b_parsed.p, b_status.bytes(), m, gamma_c.p, delta_c.p, gamma_live, delta_live, b_miller.p);
+        CG_KERNEL_CHECK();
+        k_vfy_final<<<grid, VBLOCK, 0, st>>>(b_miller.p, b_status.bytes(), m, alpha_beta, b_verdict.bytes());
+        CG_KERNEL_CHECK();
+    }
 };
 
 extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len, int32_t device) {
@@ -437,6 +542,8 @@ extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len,
         k->delta_live = hk.delta_live;
         k->gamma_is_one = hk.vk.gamma_g2.x == g2_gen.x && hk.vk.gamma_g2.y == g2_gen.y;       // generator.rs:28
         k->open(device);
+        k->open_second();
+        k->timer.create();
         k->tab.alloc(tab.size() ? tab.size() : 1);
         h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
         k->tab_g2.alloc(tab_g2.size());
@@ -458,6 +565,13 @@ extern "C" int cg_pvk_num_inputs(const cg_pvk* k, uint64_t* n) {
     return CG_OK;
 }
 
+extern "C" int cg_pvk_set_latency_mode(cg_pvk* k, int32_t on) { return set_latency_mode(k, on); }
+
+// Diagnostic: what the kernels of the handle's last verifying call took, by HIP events, summed over its chunks: the group
+// stage (tables, checks, sums) and the pairing (Miller loop and final exponentiation; in the latency arrangement with
+// the wait for the subgroup chain, and for a showing with k_show_k, which follows it there)
+extern "C" int cg_pvk_last_kernel_ms(cg_pvk* k, float* group_ms, float* pairing_ms) { return last_kernel_ms(k, group_ms, pairing_ms); }
+
 extern "C" int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inputs, const uint8_t* proofs, uint64_t n,
                                uint8_t* verdicts) {
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
@@ -472,29 +586,27 @@ extern "C" int cg_verify_batch(cg_pvk* k, const uint8_t* inputs, uint64_t n_inpu
         const uint64_t ell = n_inputs;
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
         k->b_inputs.reserve(chunk, ell * 32);
-        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict}) b->reserve(chunk);
+        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict, &k->b_in_g2}) b->reserve(chunk);
         grow(k->b_part, chunk * ell + 1);
         grow(k->b_parsed, chunk);
         grow(k->b_miller, chunk);
+        k->timer.reset();
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
             k->b_inputs.up(k->st, inputs, off, m);
-            k->b_proofs.up(k->st, proofs, off, m);
+            k->proofs_up(proofs, off, m);
+            k->timer.mark(0, k->st);
             if (ell) {
                 k_vfy_inputs<<<ceil_div(m * ell, VBLOCK), VBLOCK, 0, k->st>>>(k->b_inputs.words(), m, (uint32_t)ell, k->tab.p, k->b_part.p);
                 CG_KERNEL_CHECK();
             }
-            const uint32_t grid = ceil_div(m, VBLOCK);
-            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>(k->b_proofs.words(), k->b_inputs.words(), m, (uint32_t)ell, k->b_part.p, k->g0,
-                                                    k->b_parsed.p, k->b_status.bytes());
-            CG_KERNEL_CHECK();
-            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.bytes(), m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
-                                                     k->delta_live, k->b_miller.p);
-            CG_KERNEL_CHECK();
-            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.bytes(), m, k->alpha_beta, k->b_verdict.bytes());
-            CG_KERNEL_CHECK();
+            k->check(m, k->b_inputs.words(), (uint32_t)ell);
+            k->timer.mark(1, k->st);
+            k->pairing(m);
+            k->timer.mark(2, k->st);
             k->b_verdict.down(k->st, verdicts, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
+            k->timer.add();
         }
         return CG_OK;
     } catch (...) {
@@ -598,7 +710,7 @@ extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
         const uint32_t n_stmt = sh.n_com + 1;
-        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict, &k->b_comh, &k->b_chal}) b->reserve(chunk);
+        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict, &k->b_in_g2, &k->b_comh, &k->b_chal}) b->reserve(chunk);
         k->b_inputs.reserve(chunk, sh.n_rev * 32);
         k->b_comm.reserve(chunk, sh.n_com * 64);
         k->b_rows.reserve(chunk, sh.n_resp * 32);
@@ -608,9 +720,10 @@ extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
         grow(k->b_part, chunk * sh.n_terms + 1);
         grow(k->b_desc, tab_of.size() + 1);
         h2d_sync(k->b_desc.p, tab_of.data(), tab_of.size() * sizeof(uint32_t), k->st);
+        k->timer.reset();
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            k->b_proofs.up(k->st, rand_proofs, off, m);
+            k->proofs_up(rand_proofs, off, m);
             k->b_comh.up(k->st, com_hidden, off, m);
             k->b_inputs.up(k->st, revealed, off, m);
             k->b_comm.up(k->st, committed, off, m);
@@ -620,30 +733,33 @@ extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
             }
             const uint32_t *d_rev = k->b_inputs.words(), *d_s = k->b_rows.words(), *d_c = k->b_chal.words(), *d_comh = k->b_comh.words(),
                            *d_comm = k->b_comm.words();
+            k->timer.mark(0, k->st);
             if (sh.n_terms) {
                 const uint32_t blocks = ceil_div(m * sh.n_fixed, VBLOCK) + ceil_div(m * sh.n_var, VBLOCK);
                 k_show_terms<<<blocks, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_desc.p, k->tab.p, k->b_part.p);
                 CG_KERNEL_CHECK();
             }
             const uint32_t grid = ceil_div(m, VBLOCK);
-            k_vfy_check<<<grid, VBLOCK, 0, k->st>>>(k->b_proofs.words(), d_rev, m, 0u, k->b_part.p, k->g0, k->b_parsed.p,
-                                                    k->b_status.bytes());
-            CG_KERNEL_CHECK();
+            k->check(m, d_rev, 0u);
             k_show_check<<<grid, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_part.p, k->g0, k->b_parsed.p,
                                                      k->b_status.bytes());
             CG_KERNEL_CHECK();
-            if (pok) {
+            // k_show_k writes zeros for a malformed showing: in the latency arrangement the status is final only after the
+            // pairing has met the subgroup chain, so the k points follow it there
+            auto show_k = [&] {
+                if (!pok) return;
                 k_show_k<<<ceil_div(m * n_stmt, VBLOCK), VBLOCK, 0, k->st>>>(m, sh, k->b_part.p, k->b_status.bytes(), k->b_k.words_mut());
                 CG_KERNEL_CHECK();
-            }
-            k_vfy_miller<<<grid, VBLOCK, 0, k->st>>>(k->b_parsed.p, k->b_status.bytes(), m, k->gamma_c.p, k->delta_c.p, k->gamma_live,
-                                                     k->delta_live, k->b_miller.p);
-            CG_KERNEL_CHECK();
-            k_vfy_final<<<grid, VBLOCK, 0, k->st>>>(k->b_miller.p, k->b_status.bytes(), m, k->alpha_beta, k->b_verdict.bytes());
-            CG_KERNEL_CHECK();
+            };
+            if (!k->latency) show_k();
+            k->timer.mark(1, k->st);
+            k->pairing(m);
+            if (k->latency) show_k();
+            k->timer.mark(2, k->st);
             k->b_verdict.down(k->st, verdicts, off, m);
             if (pok) k->b_k.down(k->st, k_out, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
+            k->timer.add();
         }
         return CG_OK;
     } catch (...) {

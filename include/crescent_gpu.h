@@ -620,6 +620,19 @@ typedef struct cg_pvk cg_pvk;
 int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len, int32_t device);
 /* gamma_abc_g1.len() - 1: the public inputs a proof under this key carries */
 int cg_pvk_num_inputs(const cg_pvk* k, uint64_t* n);
+/* How a key handle arranges the pairing stage (Miller loop, final exponentiation) of its verifying calls.
+ * 0 (default) = one lane per proof: any batch up to the chunk (32768) costs what one proof costs, which suits batches.
+ * 1 = one workgroup per proof (csrc/pairing_team.hpp): a lone proof is answered sooner, large batches more slowly; on a
+ *     cg_pvk the [r]B = O chain then also runs beside the pairing on a second stream of the handle instead of before it.
+ * Measured on an MI355X (profiles/verify_lone.md): a lone Groth16 proof with 26 inputs takes 21 ms instead of 72 ms, a
+ * lone 32-bit range proof 24 ms instead of 50 ms; the latency arrangement stays ahead up to n = 1024 (33 against 65 ms,
+ * 32 against 45 ms) and the wide one overtakes it between n = 1024 and n = 4096, at about 3000 proofs.  Switch a handle
+ * on when it answers one request at a time.  The mode is a property of the handle, taken under its lock; with it on, every call on
+ * the handle uses it whatever its n.  Verdict and k_out bytes are identical in both modes for every input.  A value other
+ * than 0 or 1, or a null handle, is CG_ERR_INVALID_ARGUMENT.  (No counterpart in the reference.) */
+int cg_pvk_set_latency_mode(cg_pvk* k, int32_t on);
+/* as cg_range_vk_last_kernel_ms, for cg_verify_batch / cg_verify_show_batch: (group stage, pairing) of the last call */
+int cg_pvk_last_kernel_ms(cg_pvk* k, float* group_ms, float* pairing_ms);
 /* Replaces: `Groth16::verify_with_processed_vk` for n proofs under one key (forks/groth16/src/verifier.rs:25-65).
  * inputs: n x n_inputs x 32 B canonical Fr; proofs: n x 256 B (cg_prove's layout, ark-serialize uncompressed a ‖ b ‖ c);
  * verdicts: n bytes, CG_VERIFY_*.  n_inputs + 1 != gamma_abc_g1.len() is CG_ERR_MALFORMED_KEY
@@ -804,6 +817,9 @@ int cg_range_vk_add_bases(cg_range_vk* k, const uint8_t ped_bases[128], uint32_t
 /* Diagnostic: the HIP-event time of the handle's last call, summed over its chunks: the group stage (checks, scalar
  * multiplications, sums) and the pairing (Miller loop, final exponentiation).  (No counterpart in the reference.) */
 int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms);
+/* as cg_pvk_set_latency_mode, for cg_range_verify_batch: the pairing of each showing on one workgroup; the group stage
+ * stays as it is */
+int cg_range_vk_set_latency_mode(cg_range_vk* k, int32_t on);
 void cg_range_vk_free(cg_range_vk* k);
 /* Replaces: `verify_n_bits` between its transcripts, for n proofs whose commitment has the bases of `slot`.  The pieces
  *           of a `RangeProof` come in the layouts the cg_range_* creation calls write, so a round trip repacks nothing:

@@ -278,6 +278,8 @@ int main(int argc, char** argv) {
         const double tv = now_ms();
         cg_pvk* pvk = NULL;
         if (cg_pvk_load(&pvk, ppv.pvk_bytes, ppv.pvk_len, -1) != CG_OK) return die("cg_pvk_load");
+        /* one proof in hand: the latency arrangement of the pairing */
+        if (cg_pvk_set_latency_mode(pvk, 1) != CG_OK) { cg_pvk_free(pvk); return die("cg_pvk_set_latency_mode"); }
         uint8_t verdict = CG_VERIFY_REJECT;
         const int vrc = cg_verify_batch(pvk, witness + 32, hdr.num_inputs - 1, proof, 1, &verdict);
         cg_pvk_free(pvk);

@@ -731,6 +731,26 @@ impl GpuVerifyingKey {
         Ok(Self { h })
     }
 
+    /// `true`: one workgroup per proof, for an endpoint that answers one request at a time; `false` (the default): one
+    /// lane per proof, for batches (`cg_pvk_set_latency_mode`).  The verdicts are the same.
+    pub fn set_latency_mode(&self, on: bool) -> Result<(), SynthesisError> {
+        let rc = unsafe { sys::cg_pvk_set_latency_mode(self.h, on as i32) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(())
+    }
+
+    /// (group stage, pairing) HIP-event milliseconds of the last verifying call
+    pub fn last_kernel_ms(&self) -> Result<(f32, f32), SynthesisError> {
+        let (mut a, mut b) = (0f32, 0f32);
+        let rc = unsafe { sys::cg_pvk_last_kernel_ms(self.h, &mut a, &mut b) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((a, b))
+    }
+
     /// The GPU share of `ShowGroth16::verify` (groth16rand.rs:232-306) for showings of one proof spec: the Groth16 half
     /// whole, and the recomputed Schnorr commitments of the DLogPoK.  The Merlin transcript stays here on the host:
     /// absorb the bases, `k` and y exactly as dlog.rs:130-152 does, derive the challenge (:166-169) and compare it with
@@ -1048,6 +1068,15 @@ impl GpuRangeVerifyingKey {
             return Err(map_err(rc));
         }
         Ok(slot)
+    }
+
+    /// As `GpuVerifyingKey::set_latency_mode`, for the pairing of `verify_batch` (`cg_range_vk_set_latency_mode`)
+    pub fn set_latency_mode(&self, on: bool) -> Result<(), SynthesisError> {
+        let rc = unsafe { sys::cg_range_vk_set_latency_mode(self.h, on as i32) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(())
     }
 
     /// (group stage, pairing) HIP-event milliseconds of the last call

@@ -340,6 +340,8 @@ extern "C" {
     // verification: a PreparedVerifyingKey resident on a device, proofs and showings in batches
     pub fn cg_pvk_load(out: *mut *mut cg_pvk, pvk_bytes: *const u8, len: u64, device: i32) -> c_int;
     pub fn cg_pvk_num_inputs(k: *const cg_pvk, n: *mut u64) -> c_int;
+    pub fn cg_pvk_set_latency_mode(k: *mut cg_pvk, on: i32) -> c_int;
+    pub fn cg_pvk_last_kernel_ms(k: *mut cg_pvk, group_ms: *mut f32, pairing_ms: *mut f32) -> c_int;
     pub fn cg_verify_batch(k: *mut cg_pvk, inputs: *const u8, n_inputs: u64, proofs: *const u8, n: u64, verdicts: *mut u8) -> c_int;
     pub fn cg_verify_show_batch(
         k: *mut cg_pvk,
@@ -441,6 +443,7 @@ extern "C" {
     ) -> c_int;
     pub fn cg_range_vk_add_bases(k: *mut cg_range_vk, ped_bases: *const u8, slot: *mut u32) -> c_int;
     pub fn cg_range_vk_last_kernel_ms(k: *mut cg_range_vk, group_ms: *mut f32, pairing_ms: *mut f32) -> c_int;
+    pub fn cg_range_vk_set_latency_mode(k: *mut cg_range_vk, on: i32) -> c_int;
     pub fn cg_range_vk_free(k: *mut cg_range_vk);
     pub fn cg_range_verify_batch(
         k: *mut cg_range_vk,

@@ -61,6 +61,8 @@ def _groth16_yardstick(cc, ell, sizes, reps):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--latency", action="store_true", help="also time both arrangements of the pairing stage, alternated")
+    ap.add_argument("--no-groth16", action="store_true", help="leave the cg_verify_batch yardstick out")
     ap.add_argument("--n-bits", type=int, default=32)
     ap.add_argument("--sizes", default="1,256,4096,32768")
     ap.add_argument("--reps", type=int, default=5)
@@ -121,9 +123,27 @@ def main():
         med = statistics.median(r[0] for r in runs)
         res["sizes"][str(n)] = {"median_ms": med, "min_ms": runs[0][0], "group_kernel_ms": mid[1], "pairing_kernel_ms": mid[2],
                                 "ms_per_proof": med / n, "range_verifications_per_s": n / (med / 1e3)}
+        if a.latency:                                                  # both arrangements, alternated call by call
+            alt = {False: [], True: []}
+            for mode in (False, True):
+                vk.set_latency(mode)
+                assert (call()[0] == cc.CG_VERIFY_ACCEPT).all()
+            for _ in range(a.reps):
+                for mode in (False, True):
+                    vk.set_latency(mode)
+                    t = time.perf_counter()
+                    call()
+                    alt[mode].append(((time.perf_counter() - t) * 1e3,) + vk.last_kernel_ms())
+            vk.set_latency(False)
+            for mode, name in ((False, "wide"), (True, "latency")):
+                r = sorted(alt[mode])
+                res["sizes"][str(n)][name] = {"median_ms": statistics.median(x[0] for x in r), "min_ms": r[0][0],
+                                              "group_kernel_ms": r[len(r) // 2][1], "pairing_kernel_ms": r[len(r) // 2][2]}
+            res["sizes"][str(n)]["wide_over_latency"] = res["sizes"][str(n)]["wide"]["median_ms"] / res["sizes"][str(n)]["latency"]["median_ms"]
     pk.close()
     vk.close()
-    res["cg_verify_batch"] = {"ell": a.ell, "sizes": _groth16_yardstick(cc, a.ell, sizes, a.reps)}
+    if not a.no_groth16:
+        res["cg_verify_batch"] = {"ell": a.ell, "sizes": _groth16_yardstick(cc, a.ell, sizes, a.reps)}
     line = json.dumps(res)
     print(line)
     if a.out:

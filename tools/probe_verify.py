@@ -2,7 +2,9 @@
 inputs for several batch sizes: one valid proof duplicated n times, verdicts checked.  Prints one JSON line; run it under
 `rocprofv3 --kernel-trace --stats -- python tools/probe_verify.py` for the per-kernel times.
 
-    python tools/probe_verify.py [--ell 26] [--sizes 1,64,1024,16384] [--reps 5] [--out FILE]
+    python tools/probe_verify.py [--ell 26] [--sizes 1,64,1024,16384] [--reps 5] [--latency] [--out FILE]
+
+--latency adds, per size, both arrangements of the pairing stage (cg_pvk_set_latency_mode) alternated in this process.
 """
 import argparse
 import json
@@ -20,8 +22,32 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 import numpy as np  # noqa: E402
 
 
+def _alternated(cc, pvk, ib, pb, reps):
+    """--latency: the wide and the latency arrangement on the same handle, alternated call by call after a warm-up of each;
+    per arrangement the median wall time and that call's (group, pairing) HIP-event times"""
+    runs = {False: [], True: []}
+    for mode in (False, True):
+        pvk.set_latency(mode)
+        assert (cc.Groth16.verify_batch(pvk, ib, pb) == cc.CG_VERIFY_ACCEPT).all()
+    for _ in range(reps):
+        for mode in (False, True):
+            pvk.set_latency(mode)
+            t = time.perf_counter()
+            cc.Groth16.verify_batch(pvk, ib, pb)
+            runs[mode].append(((time.perf_counter() - t) * 1e3,) + pvk.last_kernel_ms())
+    pvk.set_latency(False)
+    out = {}
+    for mode, name in ((False, "wide"), (True, "latency")):
+        r = sorted(runs[mode])
+        mid = r[len(r) // 2]
+        out[name] = {"median_ms": statistics.median(x[0] for x in r), "min_ms": r[0][0], "group_kernel_ms": mid[1], "pairing_kernel_ms": mid[2]}
+    out["wide_over_latency"] = out["wide"]["median_ms"] / out["latency"]["median_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--latency", action="store_true", help="also time both arrangements of the pairing stage, alternated")
     ap.add_argument("--ell", type=int, default=26)
     ap.add_argument("--sizes", default="1,64,1024,16384")
     ap.add_argument("--reps", type=int, default=5)
@@ -55,6 +81,8 @@ def main():
             ts.append(time.perf_counter() - t)
         med = statistics.median(ts)
         res["sizes"][str(n)] = {"median_ms": med * 1e3, "min_ms": min(ts) * 1e3, "proofs_per_s": n / med}
+        if a.latency:
+            res["sizes"][str(n)].update(_alternated(cc, pvk, ib, pb, a.reps))
     s = res["sizes"]
     if "1" in s and "16384" in s:
         res["rate_16384_over_rate_1"] = s["16384"]["proofs_per_s"] / s["1"]["proofs_per_s"]
