@@ -269,6 +269,10 @@ _SIGNATURES = {
     "cg_range_vk_set_latency_mode": (C.c_int, [C.c_void_p, C.c_int32]),
     "cg_range_vk_free": (None, [C.c_void_p]),
     "cg_range_verify_batch": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 11 + [C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cg_range_prove_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 9),
+    "cg_range_verify_proofs_batch": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9 + [C.c_uint64, C.c_void_p]),
+    "cg_dlog_challenge_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
@@ -1200,14 +1204,18 @@ class Groth16:
         data = proof.data if isinstance(proof, Proof) else bytes(proof)
         return int(cls.verify_batch(pvk, [_inputs_array(public_inputs)], data)[0]) == CG_VERIFY_ACCEPT
 
+    NO_TRANSCRIPT = object()      # verify_show_batch's default `context`: the caller runs the transcript, as before
+
     @staticmethod
-    def verify_show_batch(pvk: "PreparedVerifyingKey", io_types, shows, with_pok: bool = True):
+    def verify_show_batch(pvk: "PreparedVerifyingKey", io_types, shows, with_pok: bool = True, context=NO_TRANSCRIPT):
         """`ShowGroth16::verify` (creds/src/groth16rand.rs:232-306) for n showings under one key and one io_types layout,
         up to the Merlin transcript.  io_types: one CG_IO_* per public input; shows: a sequence of (ShowGroth16, revealed
         inputs in input order).  Returns (verdicts, k_bytes): n verdict bytes of the Groth16 half, and per showing the
         n_committed + 1 recomputed Schnorr commitments k_i of `DLogPoK::verify` (creds/src/dlog.rs:137-145) as the 32
         compressed bytes each the transcript absorbs under b"k" - an n x (n_committed + 1) x 32 uint8 array, zero for a
-        malformed showing, None with with_pok=False.  The caller runs the transcript and compares the challenge with c."""
+        malformed showing, None with with_pok=False.  The caller runs the transcript and compares the challenge with c.
+        With context= (bytes, or None as the reference's `None`) the library's Merlin does that
+        (cg_dlog_challenge_batch), and the result is one bool per showing: `ShowGroth16::verify` whole."""
         io = np.ascontiguousarray(np.asarray(list(io_types), dtype=np.uint8))
         n = len(shows)
         n_rev, n_hid, n_com = (int((io == t).sum()) for t in (CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED))
@@ -1218,6 +1226,19 @@ class Groth16:
                 raise ValueError("a showing does not have the shape of io_types")
         cat = lambda parts, width: _u8(b"".join(parts), n * width)
         fr = lambda v: int(v).to_bytes(32, "little")          # as given: a value >= r must reach the range check
+        if context is not Groth16.NO_TRANSCRIPT:
+            if not with_pok:
+                raise ValueError("the challenge comparison needs the DLogPoK: with_pok=True")
+            verdicts, k = Groth16.verify_show_batch(pvk, io, shows)
+            # only the accepted showings reach the transcript: a malformed one may hold bytes that are no point at all
+            ok = [i for i in range(n) if verdicts[i] == CG_VERIFY_ACCEPT]
+            out = [False] * n
+            if ok:
+                cs = Groth16.show_dlog_challenges(pvk, io, k[ok], _u8(b"".join(b"".join(shows[i][0].commited_inputs) for i in ok)),
+                                                  _u8(b"".join(shows[i][0].com_hidden_inputs for i in ok)), context)
+                for j, i in enumerate(ok):
+                    out[i] = cs[j].tobytes() == fr(shows[i][0].pok_c)
+            return out
         return Groth16.verify_show_batch_packed(
             pvk, io, cat([_inputs_array(x).tobytes() for _, x in shows], 32 * n_rev), cat([sh.rand_proof for sh, _ in shows], 256),
             cat([sh.com_hidden_inputs for sh, _ in shows], 64), cat([b"".join(sh.commited_inputs) for sh, _ in shows], 64 * n_com),
@@ -1291,7 +1312,7 @@ class Groth16:
         return out[:n]
 
     @staticmethod
-    def show_batch(pvk: "PreparedVerifyingKey", io_types, states, challenge, rand=None) -> List["ShowGroth16"]:
+    def show_batch(pvk: "PreparedVerifyingKey", io_types, states, challenge=None, rand=None, context=None) -> List["ShowGroth16"]:
         """`ClientState::show_groth16` (creds/src/groth16rand.rs:100-187) for n client states of one layout: commit on the
         GPU, the caller's transcript, respond on the host.  states: a sequence of (proof bytes or Proof, inputs);
         rand: per state its show_rand_count scalars in the header's order (ints); None draws them with
@@ -1299,7 +1320,8 @@ class Groth16:
         (committed_input_openings = the r_i, input_com_randomness = z) draws them itself and passes them in;
         challenge(i, k_bytes, committed, com_hidden) -> int is the host's Merlin transcript (dlog.rs:56-99): it gets state
         i's (n_committed + 1) x 32 compressed k_i, its n_committed x 64 committed points and its 64-byte com_hidden, and
-        returns c.  This package ships no Merlin.  A malformed state (status CG_SHOW_MALFORMED) raises ValueError."""
+        returns c.  challenge=None is the library's Merlin (cg_dlog_challenge_batch) over `context` (bytes, or None as the
+        reference's `None`).  A malformed state (status CG_SHOW_MALFORMED) raises ValueError."""
         io = [int(t) for t in io_types]
         n = len(states)
         if n == 0:
@@ -1318,7 +1340,11 @@ class Groth16:
         bad = np.nonzero(status != CG_SHOW_MADE)[0]
         if bad.size:
             raise ValueError("client state %d is malformed (its proof, an input or a random scalar)" % int(bad[0]))
-        cs = [int(challenge(i, k[i], comm[i], comh[i])) for i in range(n)]
+        if challenge is None:
+            cb = Groth16.show_dlog_challenges(pvk, io, k, comm, comh, context)
+            cs = [int.from_bytes(cb[i].tobytes(), "little") for i in range(n)]
+        else:
+            cs = [int(challenge(i, k[i], comm[i], comh[i])) for i in range(n)]
         s = Groth16.show_respond_batch(io, inputs, rb, cs)
         out = []
         for i in range(n):
@@ -1387,7 +1413,8 @@ class Groth16:
         registered as `slot`: the three GPU calls with the caller's transcripts between them, then the responses.
         challenge(phase, i, data) -> int is the host's Merlin: phase "dleq" gets showing i's 4 x 32 compressed com_f,
         com_g, k_0, k_1 (creds/src/dlog.rs:56-99; the bases and y are the host's own), "c" the 2 x 32 com_f, com_g
-        (rangeproof.rs:250-257), "rho" the 32 bytes of com_q (:270-274).  This package ships no Merlin.  rand: per opening
+        (rangeproof.rs:250-257), "rho" the 32 bytes of com_q (:270-274).  prove_range_batch is the same proof in one call,
+        with the library's Merlin.  rand: per opening
         its 18 scalars in the header's order; None draws them with `secrets.randbelow`.  A malformed opening raises
         ValueError."""
         n = len(openings)
@@ -1474,6 +1501,131 @@ class Groth16:
         return [bool(verdicts[i] == CG_VERIFY_ACCEPT) and int(challenge("dleq", i, np.stack([cf[i], cg[i], k[i, 0], k[i, 1]]))) == int(proofs[i].dleq_c)
                 for i in range(n)]
 
+    @staticmethod
+    def range_prove_batch_packed(key: "RangeProofKey", slot: int, openings, ped_com, rand):
+        """cg_range_prove_batch on flat byte arrays laid out as include/crescent_gpu.h states: `RangeProof::prove_n_bits`
+        whole, the library's Merlin between the phases.  Returns (com_f n x 64, com_g n x 64, com_q n x 64, evals n x 3 x
+        32, proofs n x 3 x 96, pok_c n x 32, pok_s n x 6 x 32, challenges n x 3 x 32 (c_dleq, c, rho), status n) as uint8
+        arrays; a CG_SHOW_MALFORMED showing has zero bytes everywhere."""
+        n, ob, rb = Groth16._range_rows(openings, rand)
+        pb = _u8(ped_com, 64 * n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        com_f, com_g, com_q = (np.zeros((m, 64), np.uint8) for _ in range(3))
+        evals, proofs = np.zeros((m, 3, 32), np.uint8), np.zeros((m, 3, 96), np.uint8)
+        pok_c, pok_s, chal = np.zeros((m, 32), np.uint8), np.zeros((m, CG_RANGE_N_RESP, 32), np.uint8), np.zeros((m, 3, 32), np.uint8)
+        status = np.zeros(m, np.uint8)
+        _check(lib().cg_range_prove_batch(key._h, slot, ptr(ob), ptr(pb), ptr(rb), n, _ptr(com_f), _ptr(com_g), _ptr(com_q), _ptr(evals),
+                                          _ptr(proofs), _ptr(pok_c), _ptr(pok_s), _ptr(chal), _ptr(status)))
+        return com_f[:n], com_g[:n], com_q[:n], evals[:n], proofs[:n], pok_c[:n], pok_s[:n], chal[:n], status[:n]
+
+    @staticmethod
+    def prove_range_batch(key: "RangeProofKey", slot: int, openings, ped_coms, rand=None) -> List["RangeProof"]:
+        """`ClientState::show_range` (creds/src/groth16rand.rs:193-229) for n Pedersen openings (m, r) (ints) of the
+        commitments ped_coms (64 B ark-serialize uncompressed each) whose bases are registered as `slot`, in ONE call: the
+        transcripts are the library's Merlin, on the GPU (cg_range_prove_batch).  rand: per opening its 18 scalars in the
+        header's order; None draws them with `secrets.randbelow`.  A malformed opening raises ValueError."""
+        n = len(openings)
+        if len(ped_coms) != n:
+            raise ValueError("one Pedersen commitment per opening")
+        if n == 0:
+            return []
+        if rand is None:
+            import secrets
+            rand = [[secrets.randbelow(FR_MODULUS) for _ in range(CG_RANGE_N_RAND)] for _ in range(n)]
+        fr = lambda v: int(v).to_bytes(32, "little")
+        com_f, com_g, com_q, evals, proofs, pok_c, s, _, status = Groth16.range_prove_batch_packed(
+            key, slot, _u8(b"".join(fr(m) + fr(r) for m, r in openings)), _u8(b"".join(bytes(y) for y in ped_coms)),
+            _u8(b"".join(fr(v) for row in rand for v in row)))
+        bad = np.nonzero(status != CG_SHOW_MADE)[0]
+        if bad.size:
+            raise ValueError("opening %d is malformed (m, r, a random scalar or its commitment)" % int(bad[0]))
+        val = lambda a: int.from_bytes(a.tobytes(), "little")
+        return [RangeProof(com_f[i].tobytes(), com_g[i].tobytes(), val(evals[i, 0]), proofs[i, 0].tobytes(), val(evals[i, 1]),
+                           proofs[i, 1].tobytes(), com_q[i].tobytes(), val(evals[i, 2]), proofs[i, 2].tobytes(), val(pok_c[i]),
+                           [[val(s[i, j]) for j in range(2)], [val(s[i, j]) for j in range(2, 6)]]) for i in range(n)]
+
+    @staticmethod
+    def range_verify_proofs_batch_packed(vk: "RangeVerifyingKey", slot: int, ped_com, com_f, com_g, com_q, evals, proofs, randomizers,
+                                         pok_c, pok_s) -> np.ndarray:
+        """cg_range_verify_proofs_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = com_f / 64):
+        `RangeProof::verify_n_bits` whole.  Returns the n verdict bytes."""
+        fb = _u8(com_f)
+        if fb.size % 64:
+            raise ValueError("com_f must be n x 64 bytes")
+        n = fb.size // 64
+        arrays = [_u8(ped_com, 64 * n), fb, _u8(com_g, 64 * n), _u8(com_q, 64 * n), _u8(evals, 96 * n), _u8(proofs, 288 * n),
+                  _u8(randomizers, 32 * n), _u8(pok_c, 32 * n), _u8(pok_s, 32 * CG_RANGE_N_RESP * n)]
+        verdicts = np.zeros(max(n, 1), np.uint8)
+        _check(lib().cg_range_verify_proofs_batch(vk._h, slot, *[_ptr(a) if a.size else None for a in arrays], n, _ptr(verdicts)))
+        return verdicts[:n]
+
+    @staticmethod
+    def verify_range_proofs(vk: "RangeVerifyingKey", slot: int, ped_coms, proofs: List["RangeProof"], randomizers=None) -> List[bool]:
+        """`ShowRange::verify` for n range proofs about the Pedersen commitments ped_coms whose bases are registered as
+        `slot`, in ONE call: both transcripts and the comparison of the DLEQ's challenge run on the GPU
+        (cg_range_verify_proofs_batch).  randomizers: per proof (r_1, r_2) below 2^128; None draws them with `secrets`.
+        True exactly where `verify_n_bits` returns true."""
+        n = len(proofs)
+        if len(ped_coms) != n:
+            raise ValueError("one Pedersen commitment per proof")
+        if n == 0:
+            return []
+        if randomizers is None:
+            import secrets
+            randomizers = [(secrets.randbits(128), secrets.randbits(128)) for _ in range(n)]
+        fr = lambda v: int(v).to_bytes(32, "little")
+        join = lambda f: _u8(b"".join(f(p) for p in proofs))
+        verdicts = Groth16.range_verify_proofs_batch_packed(
+            vk, slot, _u8(b"".join(bytes(y) for y in ped_coms)), join(lambda p: bytes(p.com_f)), join(lambda p: bytes(p.com_g)),
+            join(lambda p: bytes(p.com_q)), join(lambda p: fr(p.eval_g) + fr(p.eval_gw) + fr(p.eval_w_hat)),
+            join(lambda p: bytes(p.proof_g) + bytes(p.proof_gw) + bytes(p.proof_w_hat)),
+            _u8(b"".join(int(r).to_bytes(16, "little") for row in randomizers for r in row)), join(lambda p: fr(p.dleq_c)),
+            join(lambda p: b"".join(fr(x) for si in p.dleq_s for x in si)))
+        return [bool(v == CG_VERIFY_ACCEPT) for v in verdicts]
+
+    @staticmethod
+    def dlog_challenge_batch(n_bases, bases, k, y_head, y_last, context=None, context_len: Optional[int] = None,
+                             context_stride: int = 0) -> np.ndarray:
+        """cg_dlog_challenge_batch (host only, no GPU needed): `DLogPoK`'s Merlin transcript (creds/src/dlog.rs:56-99) for n
+        showings of one shape.  n_bases: the number of bases per statement; bases: their 64-byte uncompressed points,
+        statement by statement, shared by the batch; k: n x n_statements x 32 compressed (the k_bytes the commit and
+        verify calls return); y_head: n x (n_statements - 1) x 64 uncompressed, or None with one statement; y_last: n x 64.
+        context: bytes or None (`None` and b"" are the same transcript), one for the batch; with context_stride > 0 it
+        holds one context of context_len bytes (default: the stride) per showing, context_stride bytes apart.  Returns
+        the n x 32 challenge bytes (canonical scalars)."""
+        nb = np.ascontiguousarray(np.asarray(list(n_bases), dtype=np.uint32))
+        yl = _u8(y_last)
+        if yl.size % 64:
+            raise ValueError("y_last must be n x 64 bytes")
+        n = yl.size // 64
+        bb, kb = _u8(bases, 64 * int(nb.sum())), _u8(k, 32 * nb.size * n)
+        yh = None if y_head is None or nb.size <= 1 else _u8(y_head, 64 * (nb.size - 1) * n)
+        cb = _u8(context if context is not None else b"")
+        if context_len is None:
+            context_len = context_stride if context_stride else cb.size
+        if cb.size < (context_stride * (n - 1) + context_len if context_stride and n else context_len):
+            raise ValueError("context is shorter than its length and stride say")
+        ptr = lambda a: _ptr(a) if a is not None and a.size else None
+        out = np.zeros((max(n, 1), 32), np.uint8)
+        _check(lib().cg_dlog_challenge_batch(ptr(cb), context_len, context_stride, nb.size, nb.ctypes.data_as(C.POINTER(C.c_uint32)), ptr(bb),
+                                             ptr(kb), ptr(yh), ptr(yl), n, _ptr(out)))
+        return out[:n]
+
+    @staticmethod
+    def show_dlog_challenges(pvk: "PreparedVerifyingKey", io_types, k, committed, com_hidden, context=None) -> np.ndarray:
+        """the DLogPoK challenge of n showings under pvk and one io_types layout, by the library's Merlin
+        (cg_dlog_challenge_batch): per committed input the statement (gamma_abc_g1[i + 1], delta_g1), then the hidden
+        inputs' gamma_abc_g1[j + 1] ..., delta_g1 (creds/src/groth16rand.rs:133-174, :246-300).  k, committed, com_hidden:
+        as show_commit_batch_packed and verify_show_batch return them.  Returns n x 32 bytes."""
+        io = [int(t) for t in io_types]
+        com = [i for i, t in enumerate(io) if t == CG_IO_COMMITTED]
+        hid = [j for j, t in enumerate(io) if t == CG_IO_HIDDEN]
+        abc, delta = pvk.gamma_abc_g1, pvk.delta_g1
+        bases = [b for i in com for b in (abc[i + 1], delta)] + [abc[j + 1] for j in hid] + [delta]
+        return Groth16.dlog_challenge_batch([2] * len(com) + [len(hid) + 1], np.concatenate(bases), k, committed if com else None,
+                                            com_hidden, context)
+
     @classmethod
     def clear_cache(cls):
         cls._cache.clear()
@@ -1490,6 +1642,11 @@ class PreparedVerifyingKey(_LatencyMode, _Handle):
         b = _u8(pvk_bytes)
         self._h = C.c_void_p()
         _check(lib().cg_pvk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, device))
+        # the bases of a showing's DLogPoK as its transcript absorbs them (Groth16.show_dlog_challenges): the key starts with
+        # its VerifyingKey: alpha_g1 | beta_g2 | gamma_g2 | delta_g1 | delta_g2 | u64 count | gamma_abc_g1
+        n_abc = int.from_bytes(b[512:520].tobytes(), "little")
+        self.delta_g1 = b[320:384].copy()
+        self.gamma_abc_g1 = b[520:520 + 64 * n_abc].reshape(n_abc, 64).copy()
         if latency:
             self.set_latency(True)
 

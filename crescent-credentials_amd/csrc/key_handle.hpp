@@ -6,6 +6,7 @@
 #pragma once
 #include "ark_codec.hpp"
 #include "fixed_base.hpp"
+#include "merlin.hpp"
 
 namespace cg {
 namespace {
@@ -75,10 +76,12 @@ int set_latency_mode(K* k, int32_t on) {
     return CG_OK;
 }
 
-// The Pedersen bases registered on a range key: per slot the fixed-base tables of one pair (2 x 1 MB on the device).
+// The Pedersen bases registered on a range key: per slot the fixed-base tables of one pair (2 x 1 MB on the device) and
+// the pair's 2 x 32 compressed bytes, which the DLEQ's transcript absorbs under b"base".
 struct PedersenSlots {
     static constexpr uint32_t MAX_SLOTS = 64;
     std::vector<DevBuf<G1Affine>> tabs;
+    std::vector<DevBuf<uint8_t>> cmps;
     // cg_range_pk_add_bases / cg_range_vk_add_bases after their null check
     int add(KeyHandle& k, const uint8_t ped_bases[128], uint32_t* slot) {
         std::vector<G1Affine> bases(3, G1Affine::inf()), tab;    // build_tables skips the first entry
@@ -91,7 +94,17 @@ struct PedersenSlots {
             CG_HIP(hipSetDevice(k.device));
             DevBuf<G1Affine> d(tab.size());
             h2d_sync(d.p, tab.data(), tab.size() * sizeof(G1Affine), k.st);
+            uint32_t w[16], cmp[16];
+            for (int i = 0; i < 2; ++i) {
+                memcpy(w, ped_bases + 64 * i, 64);
+                ml_compress_g1(w, cmp + 8 * i);
+            }
+            DevBuf<uint8_t> dc(sizeof(cmp));
+            h2d_sync(dc.p, cmp, sizeof(cmp), k.st);
+            tabs.reserve(tabs.size() + 1);
+            cmps.reserve(cmps.size() + 1);
             tabs.push_back(std::move(d));
+            cmps.push_back(std::move(dc));
             *slot = (uint32_t)tabs.size() - 1;
             return CG_OK;
         } catch (...) {
@@ -106,6 +119,7 @@ struct PedersenSlots {
         snprintf(b, sizeof(b), "slot %u was not registered on this key (%s)", slot, entry);
         throw HipError(CG_ERR_INVALID_ARGUMENT, b);
     }
+    const uint8_t* compressed(uint32_t slot) const { return cmps[slot].p; }      // after table(slot, ..) has accepted the slot
 };
 // the domain sizes of a range key; `fn` is prove_n_bits or verify_n_bits.  CG_OK, or the failure already recorded
 [[maybe_unused]] int check_range_bits(uint32_t n_bits, const char* fn) {

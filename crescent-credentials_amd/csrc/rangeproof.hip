@@ -20,6 +20,8 @@
 //   quotient  com_q                           2n + 7 terms     (rangeproof.rs:260-268)
 //   open      W of proof_g, proof_gw, proof_w^   4n + 15 terms (KZG10::open, kzg10/mod.rs:247-331)
 // cg_range_respond_batch, the DLEQ's responses once the host's transcript has produced its challenge, is host arithmetic.
+// cg_range_prove_batch is the three phases in one call with the transcripts on the device (merlin.hpp): the same kernels,
+// k_range_challenge_c and k_range_challenge_rho between them and k_range_finish (the responses) behind them.
 // The handle's device, stream and lock, the timing of the two stages, the slots and the per-call arrays are key_handle.hpp's
 // (KeyHandle, StageTimer, PedersenSlots, RowBuf), shared with cg_pvk and cg_range_vk; so are the responses (dlog_respond).
 #include <memory>
@@ -60,7 +62,7 @@ template <int PHASE>
 __global__ __launch_bounds__(RWAVE) void k_range_poly(RangeConsts kc, const uint32_t* __restrict__ open, const uint32_t* __restrict__ rand,
                                                      const uint32_t* __restrict__ c, const uint32_t* __restrict__ rho, uint64_t n,
                                                      uint32_t n_terms, uint32_t* __restrict__ terms, uint32_t* __restrict__ evals,
-                                                     uint32_t* __restrict__ proofs, uint8_t* __restrict__ status) {
+                                                     uint32_t* __restrict__ proofs, uint8_t* __restrict__ status, int chained) {
     __shared__ RangeWork W;
     const uint64_t p = blockIdx.x;
     if (p >= n) return;
@@ -68,7 +70,10 @@ __global__ __launch_bounds__(RWAVE) void k_range_poly(RangeConsts kc, const uint
     const RangeIn in{open + 16 * p, rand + 8 * RP_N_RAND * p, PHASE >= PH_QUOTIENT ? c + 8 * p : nullptr, PHASE == PH_OPEN ? rho + 8 * p : nullptr};
     uint32_t* t = terms + 8 * p * n_terms;
     bool made;                                                    // the same in every lane: it depends on the inputs alone
-    if (PHASE == PH_COMMIT) made = rp_commit(kc, in, W, t, ln);
+    // chained (cg_range_prove_batch): a showing that an earlier phase of the same call refused stays refused.  One byte
+    // that every lane of the workgroup reads, and that only lane 0 writes, at the end
+    if (chained && status[p] != CG_SHOW_MADE) made = false;
+    else if (PHASE == PH_COMMIT) made = rp_commit(kc, in, W, t, ln);
     else if (PHASE == PH_QUOTIENT) made = rp_quotient_call(kc, in, W, t, ln);
     else made = rp_open(kc, in, W, t, evals + 24 * p, proofs + 72 * p, ln);
     if (ln.lane == 0) status[p] = made ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
@@ -116,6 +121,89 @@ __global__ __launch_bounds__(RWAVE) void k_range_sum(const RpShape* __restrict__
     if (cw) dev_put_g1(a, cw, true);
 }
 
+// ---- cg_range_prove_batch: the transcripts between the phases, and the end ---------------------------------------------
+// One lane per showing runs its Merlin transcripts (merlin.hpp), the sponge in LDS at 200 bytes per lane.  Both kernels do
+// arithmetic on bytes only - no field multiplication, whose call would bring a stack - and declare no private segment.
+// A showing that is not CG_SHOW_MADE gets zero challenges; the phases after it skip it.
+//
+// After the commit phase: c from the range transcript over com_f, com_g (ts: the phase's four compressed points) and
+// c_dleq from the DLEQ's over the slot's and the key's compressed bases, k_0, k_1, ped_com and com_f.  ped_com is
+// compressed here as its bytes stand; k_range_finish refuses a showing whose ped_com is no valid point.
+__global__ __launch_bounds__(RWAVE) void k_range_challenge_c(const uint32_t* __restrict__ ts, const uint32_t* __restrict__ ped,
+                                                            const uint8_t* __restrict__ slot_bases, const uint8_t* __restrict__ key_bases,
+                                                            const uint8_t* __restrict__ status, uint64_t n, uint32_t* __restrict__ ped_c,
+                                                            uint32_t* __restrict__ c, uint32_t* __restrict__ c_dleq) {
+    __shared__ __attribute__((aligned(8))) uint8_t sponge[RWAVE * ML_STATE];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (status[p] != CG_SHOW_MADE) {
+        for (int l = 0; l < 8; ++l) c[8 * p + l] = c_dleq[8 * p + l] = 0;
+        return;
+    }
+    uint8_t* st = sponge + ML_STATE * threadIdx.x;
+    const uint8_t* t = (const uint8_t*)(ts + 32 * p);
+    ml_compress_g1(ped + 16 * p, ped_c + 8 * p);
+    ml_range_challenges(st, t, t + 32, nullptr, (uint8_t*)(c + 8 * p), nullptr);
+    ml_range_dleq_challenge(st, slot_bases, key_bases, t + 64, (const uint8_t*)(ped_c + 8 * p), t, (uint8_t*)(c_dleq + 8 * p));
+}
+// After the quotient phase: rho, the range transcript replayed from its start with com_q (ts_q) appended.
+__global__ __launch_bounds__(RWAVE) void k_range_challenge_rho(const uint32_t* __restrict__ ts, const uint32_t* __restrict__ ts_q,
+                                                              const uint8_t* __restrict__ status, uint64_t n, uint32_t* __restrict__ rho) {
+    __shared__ __attribute__((aligned(8))) uint8_t sponge[RWAVE * ML_STATE];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    if (status[p] != CG_SHOW_MADE) {
+        for (int l = 0; l < 8; ++l) rho[8 * p + l] = 0;
+        return;
+    }
+    const uint8_t* t = (const uint8_t*)(ts + 32 * p);
+    ml_range_challenges(sponge + ML_STATE * threadIdx.x, t, t + 32, (const uint8_t*)(ts_q + 8 * p), nullptr, (uint8_t*)(rho + 8 * p));
+}
+
+// what cg_range_prove_batch hands back, one row per showing in each array
+struct RpProof {
+    uint32_t *com_f, *com_g, *com_q;       // 16 words
+    uint32_t *evals, *proofs;              // 24, 72
+    uint32_t *pok_c, *pok_s;               // 8, 48
+    uint32_t* challenges;                  // 24: c_dleq, c, rho
+};
+// The end of a proof, one lane per showing: ped_com's checked deserialisation, the DLEQ's responses s = nonce - c_dleq *
+// secret (dlog.rs:101-109; every scalar was found below r by the commit phase) and the three challenges side by side.
+// A showing that any phase refused, or whose ped_com is refused here, has EVERY output row zeroed, those that earlier
+// phases wrote included.  The one condition that can first appear after the commit phase is rho^n_bits = 1 for the rho
+// the transcript gave: no input is known that provokes it through the hash, so no test reaches it, and it is right by
+// construction: the open phase sets the status, and the status alone decides here.
+__global__ __launch_bounds__(RWAVE) void k_range_finish(const uint32_t* __restrict__ open, const uint32_t* __restrict__ rand,
+                                                       const uint32_t* __restrict__ ped, const uint32_t* __restrict__ c,
+                                                       const uint32_t* __restrict__ rho, uint64_t n, RpProof o, uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    bool made = status[p] == CG_SHOW_MADE;
+    (void)dev_g1(ped + 16 * p, made);
+    if (!made) {
+        status[p] = CG_SHOW_MALFORMED;
+        for (int l = 0; l < 16; ++l) o.com_f[16 * p + l] = o.com_g[16 * p + l] = o.com_q[16 * p + l] = 0;
+        for (int l = 0; l < 24; ++l) o.evals[24 * p + l] = o.challenges[24 * p + l] = 0;
+        for (int l = 0; l < 72; ++l) o.proofs[72 * p + l] = 0;
+        for (int l = 0; l < 8; ++l) o.pok_c[8 * p + l] = 0;
+        for (int l = 0; l < 48; ++l) o.pok_s[48 * p + l] = 0;
+        return;
+    }
+    static constexpr int8_t SECRET[RP_N_RESP] = {-1, -2, RP_F, RP_F + 1, RP_F + 2, -1};     // -1: m, -2: r, else a rand index
+    static constexpr int8_t NONCE[RP_N_RESP] = {RP_TM, RP_TR, RP_TF, RP_TF + 1, RP_TF + 2, RP_TM};
+    const uint32_t* rd = rand + 8 * RP_N_RAND * p;
+    const Fr cm = to_mont(dev_fr(o.pok_c + 8 * p));                // c·R times a canonical x is c·x, canonical
+    for (int t = 0; t < RP_N_RESP; ++t) {
+        const Fr secret = dev_fr(SECRET[t] < 0 ? open + 16 * p + 8 * (-1 - SECRET[t]) : rd + 8 * SECRET[t]);
+        rp_store(o.pok_s + 48 * p + 8 * t, sub(dev_fr(rd + 8 * NONCE[t]), mul(cm, secret)));
+    }
+    for (int l = 0; l < 8; ++l) {
+        o.challenges[24 * p + l] = o.pok_c[8 * p + l];
+        o.challenges[24 * p + 8 + l] = c[8 * p + l];
+        o.challenges[24 * p + 16 + l] = rho[8 * p + l];
+    }
+}
+
 // the three calls' layouts for a domain of n: which table every term walks (the order rangepoly.hpp writes the scalars
 // in) and which terms make which point.  Tables 0..2n+3 are powers_of_g's, 2n+4..2n+7 powers_of_gamma_g's.
 void range_shapes(uint32_t n, RpShape sh[3], std::vector<uint32_t> tab_of[3]) {
@@ -159,6 +247,11 @@ struct cg_range_pk : KeyHandle {
     // the caller's
     RowBuf b_open{64}, b_rand{32 * RP_N_RAND}, b_c{32}, b_rho{32}, b_terms, b_unc0, b_unc1, b_cmp, b_evals, b_status{1};
     DevBuf<G1XYZZ> b_part;                 // one partial per (showing, term)
+    // cg_range_prove_batch: com_f_basis (gamma_g[0..2], g[0]) as the DLEQ's transcript absorbs it, 4 x 32 compressed bytes,
+    // and the call's own arrays, which hold a chunk's proofs from the phase that writes them to the one copy down
+    DevBuf<uint8_t> key_cmp;
+    RowBuf o_ped{64}, o_pedc{32}, o_comf{64}, o_comg{64}, o_ts{128}, o_comq{64}, o_tsq{32}, o_evals{96}, o_proofs{288}, o_pokc{32},
+        o_poks{32 * RP_N_RESP}, o_chal{96};
     ~cg_range_pk() { drain(); }            // before the buffers above are freed (key_handle.hpp)
 };
 
@@ -182,6 +275,12 @@ extern "C" int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes
         bases.insert(bases.end(), pgam.begin(), pgam.begin() + 4);
         std::vector<G1Affine> tab;
         build_tables(bases, tab);
+        uint32_t key_cmp[4 * 8];                                               // gamma_g[0..2], then g[0]: com_f_basis
+        for (int i = 0; i < 4; ++i) {
+            uint32_t w[16];
+            memcpy(w, range_pk_bytes + (i < 3 ? 16 + 64 * pg.size() + 64 * i : 8), 64);
+            ml_compress_g1(w, key_cmp + 8 * i);
+        }
         std::unique_ptr<cg_range_pk> k(new cg_range_pk());
         k->n_bits = n;
         k->kc = range_consts((uint32_t)ilog2_ceil(n));
@@ -191,6 +290,8 @@ extern "C" int cg_range_pk_load(cg_range_pk** out, const uint8_t* range_pk_bytes
         k->timer.create();
         k->tab.alloc(tab.size());
         h2d_sync(k->tab.p, tab.data(), tab.size() * sizeof(G1Affine), k->st);
+        k->key_cmp.alloc(sizeof(key_cmp));
+        h2d_sync(k->key_cmp.p, key_cmp, sizeof(key_cmp), k->st);
         k->d_shape.alloc(3);
         h2d_sync(k->d_shape.p, k->shape, 3 * sizeof(RpShape), k->st);
         for (int ph = 0; ph < 3; ++ph) {
@@ -252,11 +353,11 @@ int run_range(cg_range_pk* k, const RpCall& a) {
             uint32_t *d_terms = k->b_terms.words_mut(), *d_ev = k->b_evals.words_mut(), *d_u0 = k->b_unc0.words_mut();
             k->timer.mark(0, k->st);
             if (a.phase == PH_COMMIT)
-                k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes());
+                k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes(), 0);
             else if (a.phase == PH_QUOTIENT)
-                k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes());
+                k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes(), 0);
             else
-                k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes());
+                k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, sh.n_terms, d_terms, d_ev, d_u0, k->b_status.bytes(), 0);
             CG_KERNEL_CHECK();
             k->timer.mark(1, k->st);
             k_range_terms<<<ceil_div(m * sh.n_terms, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + a.phase, k->d_tab_of[a.phase].p, d_terms, k->tab.p,
@@ -310,4 +411,85 @@ extern "C" int cg_range_respond_batch(const uint8_t* openings, const uint8_t* ra
     auto secret = [&](uint64_t p, uint32_t t) { return SECRET[t] < 0 ? openings + 64 * p + 32 * (-1 - SECRET[t]) : rand + 32 * (p * RP_N_RAND + SECRET[t]); };
     auto nonce = [&](uint64_t p, uint32_t t) { return rand + 32 * (p * RP_N_RAND + NONCE[t]); };
     return dlog_respond(n, RP_N_RESP, status, c_dleq, secret, nonce, pok_s, "an opening");
+}
+
+// `prove_n_bits` whole: the three phases above with the library's Merlin (merlin.hpp) between them.  Per chunk the inputs
+// go up once, twelve kernels run back to back on the handle's stream - commit, the challenges c and c_dleq, quotient, the
+// challenge rho, open, the responses - and the proof comes down once; the host waits once, for that copy.  The phases'
+// kernels are the three calls' own, so the two paths give the same bytes.  The two stages are not timed apart here:
+// cg_range_pk_last_kernel_ms reads zeros after this call.
+extern "C" int cg_range_prove_batch(cg_range_pk* k, uint32_t slot, const uint8_t* openings, const uint8_t* ped_com, const uint8_t* rand,
+                                    uint64_t n, uint8_t* com_f, uint8_t* com_g, uint8_t* com_q, uint8_t* evals, uint8_t* proofs,
+                                    uint8_t* pok_c, uint8_t* pok_s, uint8_t* challenges_out, uint8_t* status) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        const G1Affine* tab_slot = k->slots.table(slot, "cg_range_pk_add_bases");
+        if (n == 0) return CG_OK;
+        if (!openings || !ped_com || !rand || !com_f || !com_g || !com_q || !evals || !proofs || !pok_c || !pok_s || !status)
+            return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t chunk = n < RCHUNK ? n : RCHUNK;
+        for (RowBuf* b : {&k->b_open, &k->b_rand, &k->b_c, &k->b_rho, &k->b_status, &k->o_ped, &k->o_pedc, &k->o_comf, &k->o_comg, &k->o_ts,
+                          &k->o_comq, &k->o_tsq, &k->o_evals, &k->o_proofs, &k->o_pokc, &k->o_poks, &k->o_chal})
+            b->reserve(chunk);
+        const uint32_t max_terms = k->shape[PH_OPEN].n_terms;                  // the most of the three phases
+        k->b_terms.reserve(chunk, 32 * max_terms);
+        grow(k->b_part, chunk * max_terms);
+        k->timer.reset();
+        const uint8_t* slot_cmp = k->slots.compressed(slot);
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            k->b_open.up(k->st, openings, off, m);
+            k->b_rand.up(k->st, rand, off, m);
+            k->o_ped.up(k->st, ped_com, off, m);
+            const uint32_t *d_open = k->b_open.words(), *d_rand = k->b_rand.words(), *d_ped = k->o_ped.words();
+            uint32_t *d_c = k->b_c.words_mut(), *d_rho = k->b_rho.words_mut(), *d_terms = k->b_terms.words_mut();
+            uint32_t *d_ev = k->o_evals.words_mut(), *d_pr = k->o_proofs.words_mut();
+            uint8_t* d_status = k->b_status.bytes();
+            const uint32_t lanes = ceil_div(m, RWAVE);
+            auto points = [&](int ph, uint32_t* unc0, uint32_t* unc1, uint32_t* cmp) {
+                const RpShape& sh = k->shape[ph];
+                k_range_terms<<<ceil_div(m * sh.n_terms, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + ph, k->d_tab_of[ph].p, d_terms, k->tab.p, tab_slot,
+                                                                                     d_status, m, k->b_part.p);
+                CG_KERNEL_CHECK();
+                k_range_sum<<<ceil_div(m * sh.n_pts, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + ph, d_status, m, k->b_part.p, unc0, unc1, cmp);
+                CG_KERNEL_CHECK();
+            };
+            k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_COMMIT].n_terms, d_terms, d_ev,
+                                                                      d_pr, d_status, 0);
+            CG_KERNEL_CHECK();
+            points(PH_COMMIT, k->o_comf.words_mut(), k->o_comg.words_mut(), k->o_ts.words_mut());
+            k_range_challenge_c<<<lanes, RWAVE, 0, k->st>>>(k->o_ts.words(), d_ped, slot_cmp, k->key_cmp.p, d_status, m, k->o_pedc.words_mut(), d_c,
+                                                           k->o_pokc.words_mut());
+            CG_KERNEL_CHECK();
+            k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_QUOTIENT].n_terms, d_terms,
+                                                                        d_ev, d_pr, d_status, 1);
+            CG_KERNEL_CHECK();
+            points(PH_QUOTIENT, k->o_comq.words_mut(), nullptr, k->o_tsq.words_mut());
+            k_range_challenge_rho<<<lanes, RWAVE, 0, k->st>>>(k->o_ts.words(), k->o_tsq.words(), d_status, m, d_rho);
+            CG_KERNEL_CHECK();
+            k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_OPEN].n_terms, d_terms, d_ev, d_pr,
+                                                                    d_status, 1);
+            CG_KERNEL_CHECK();
+            points(PH_OPEN, d_pr, nullptr, nullptr);
+            const RpProof o{k->o_comf.words_mut(), k->o_comg.words_mut(), k->o_comq.words_mut(), d_ev, d_pr, k->o_pokc.words_mut(),
+                            k->o_poks.words_mut(), k->o_chal.words_mut()};
+            k_range_finish<<<lanes, RWAVE, 0, k->st>>>(d_open, d_rand, d_ped, d_c, d_rho, m, o, d_status);
+            CG_KERNEL_CHECK();
+            k->o_comf.down(k->st, com_f, off, m);
+            k->o_comg.down(k->st, com_g, off, m);
+            k->o_comq.down(k->st, com_q, off, m);
+            k->o_evals.down(k->st, evals, off, m);
+            k->o_proofs.down(k->st, proofs, off, m);
+            k->o_pokc.down(k->st, pok_c, off, m);
+            k->o_poks.down(k->st, pok_s, off, m);
+            k->o_chal.down(k->st, challenges_out, off, m);
+            k->b_status.down(k->st, status, off, m);
+            CG_HIP(hipStreamSynchronize(k->st));
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
 }

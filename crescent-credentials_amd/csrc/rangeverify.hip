@@ -22,6 +22,8 @@
 //                 whose G1 point is O, or whose key point is, is dropped as ark's multi_miller_loop drops it
 //   k_rv_final    one lane per showing: final exponentiation, == one, and the two bits               -> one verdict byte
 // A malformed showing costs nothing after k_rv_check: every later lane of it returns at once.
+// cg_range_verify_proofs_batch is the same call with the transcripts on the device (merlin.hpp): k_rv_challenges in front
+// derives c and rho, k_rv_challenge_dleq behind recomputes the DLEQ's challenge and compares it with pok_c.
 // The handle's device, stream and lock, the timing of the two stages, the slots and the per-call arrays are key_handle.hpp's
 // (KeyHandle, StageTimer, PedersenSlots, RowBuf), shared with cg_pvk and cg_range_pk; the chains are scalar_mul_mixed.
 #include <memory>
@@ -184,6 +186,39 @@ __global__ __launch_bounds__(RVBLOCK) void k_rv_final(const Fq12* __restrict__ f
     verdict[p] = ok ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
 }
 
+// ---- cg_range_verify_proofs_batch: the transcripts either side of the five kernels above --------------------------------
+// One lane per showing runs its Merlin transcripts (merlin.hpp), the sponge in LDS at 200 bytes per lane.  Both kernels do
+// arithmetic on bytes only and declare no private segment.
+//
+// In front of k_rv_check: com_f, com_g and com_q compressed as their bytes stand (pts: 3 x 8 words per showing) and the
+// range transcript over them -> c, rho.  A point that k_rv_check will refuse gives some c and rho that nothing uses.
+__global__ __launch_bounds__(RVBLOCK) void k_rv_challenges(RvArgs a, uint32_t* __restrict__ pts, uint32_t* __restrict__ c, uint32_t* __restrict__ rho) {
+    __shared__ __attribute__((aligned(8))) uint8_t sponge[RVBLOCK * ML_STATE];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.m) return;
+    uint32_t* t = pts + 24 * p;
+    ml_compress_g1(a.com_f + 16 * p, t);
+    ml_compress_g1(a.com_g + 16 * p, t + 8);
+    ml_compress_g1(a.com_q + 16 * p, t + 16);
+    const uint8_t* b = (const uint8_t*)t;
+    ml_range_challenges(sponge + ML_STATE * threadIdx.x, b, b + 32, b + 64, (uint8_t*)(c + 8 * p), (uint8_t*)(rho + 8 * p));
+}
+// Behind the final exponentiation: the DLEQ's transcript over the slot's bases, k_0, ped_com, com_f_basis, k_1 and com_f
+// (dlog.rs:130-169), and `c == self.c` (:171-174): a showing stays CG_VERIFY_ACCEPT only where the challenge equals pok_c.
+__global__ __launch_bounds__(RVBLOCK) void k_rv_challenge_dleq(RvArgs a, const uint32_t* __restrict__ pts, const uint32_t* __restrict__ k_pts,
+                                                              const uint8_t* __restrict__ slot_bases, const uint8_t* __restrict__ key_bases,
+                                                              uint32_t* __restrict__ ped_c, uint32_t* __restrict__ c_dleq, uint8_t* __restrict__ verdict) {
+    __shared__ __attribute__((aligned(8))) uint8_t sponge[RVBLOCK * ML_STATE];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.m || verdict[p] != CG_VERIFY_ACCEPT) return;
+    ml_compress_g1(a.ped_com + 16 * p, ped_c + 8 * p);
+    ml_range_dleq_challenge(sponge + ML_STATE * threadIdx.x, slot_bases, key_bases, (const uint8_t*)(k_pts + 16 * p),
+                            (const uint8_t*)(ped_c + 8 * p), (const uint8_t*)(pts + 24 * p), (uint8_t*)(c_dleq + 8 * p));
+    uint32_t differ = 0;
+    for (int l = 0; l < 8; ++l) differ |= c_dleq[8 * p + l] ^ a.pok_c[8 * p + l];
+    if (differ) verdict[p] = CG_VERIFY_REJECT;
+}
+
 // the latency arrangement of the two kernels above (cg_range_vk_set_latency_mode): one workgroup per showing, pairing_team.hpp
 __global__ __launch_bounds__(TEAM_WIDTH) void k_rv_lone_miller(const G1Affine* __restrict__ pair_pts, const uint8_t* __restrict__ flags, uint64_t m,
                                                              const EllCoeff* beta_h_c, const EllCoeff* h_c, int beta_h_live, int h_live,
@@ -233,7 +268,11 @@ struct cg_range_vk : KeyHandle {
     DevBuf<G1XYZZ> b_part;                 // one partial per (term, showing)
     DevBuf<G1Affine> b_pair;               // total_c, then -total_w
     DevBuf<Fq12> b_miller;
-    ~cg_range_vk() { drain(); }            // before the buffers above are freed (key_handle.hpp)
+    // cg_range_verify_proofs_batch: com_f_basis as the DLEQ's transcript absorbs it, 4 x 32 compressed bytes; per showing
+    // com_f, com_g, com_q compressed, ped_com compressed and the recomputed c_dleq
+    DevBuf<uint8_t> key_cmp;
+    RowBuf b_pts{96}, b_pedc{32}, b_cd{32};
+    ~cg_range_vk() { drain(); }           // before the buffers above are freed (key_handle.hpp)
 };
 
 extern "C" int cg_range_vk_load(cg_range_vk** out, const uint8_t* range_vk_bytes, uint64_t len, uint32_t n_bits, int32_t device) {
@@ -269,6 +308,14 @@ extern "C" int cg_range_vk_load(cg_range_vk** out, const uint8_t* range_vk_bytes
         k->beta_h_c.alloc(NC);
         h2d_sync(k->h_c.p, h_c.data(), NC * sizeof(EllCoeff), k->st);
         h2d_sync(k->beta_h_c.p, beta_h_c.data(), NC * sizeof(EllCoeff), k->st);
+        uint32_t key_cmp[4 * 8];
+        for (int i = 0; i < 4; ++i) {
+            uint32_t w[16];
+            memcpy(w, range_vk_bytes + RV_VK_BYTES - 256 + 64 * i, 64);
+            ml_compress_g1(w, key_cmp + 8 * i);
+        }
+        k->key_cmp.alloc(sizeof(key_cmp));
+        h2d_sync(k->key_cmp.p, key_cmp, sizeof(key_cmp), k->st);
         *out = k.release();
         return CG_OK;
     } catch (...) {
@@ -289,24 +336,26 @@ extern "C" int cg_range_vk_set_latency_mode(cg_range_vk* k, int32_t on) { return
 // (k_rv_check, k_rv_terms, k_rv_sum) and the pairing (k_rv_miller, k_rv_final)
 extern "C" int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms) { return last_kernel_ms(k, group_ms, pairing_ms); }
 
-extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
-                                     const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c,
-                                     const uint8_t* rho, const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s,
-                                     uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
+namespace {
+// Both verifying entries.  own_transcripts (cg_range_verify_proofs_batch): c and rho are derived in front of the five
+// kernels and the DLEQ's challenge is recomputed and compared behind them, so neither comes in and k_0, k_1 do not go out.
+int run_range_verify(cg_range_vk* k, bool own_transcripts, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
+                     const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c, const uint8_t* rho,
+                     const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     try {
         std::lock_guard<std::mutex> lk(k->mu);
         const G1Affine* tab_slot = k->slots.table(slot, "cg_range_vk_add_bases");
         if (n == 0) return CG_OK;
         const bool pok = pok_c != nullptr;
-        if (!com_f || !com_g || !com_q || !evals || !proofs || !c || !rho || !randomizers || !verdicts ||
-            (pok && (!ped_com || !pok_s || !k_out)))
+        if (!com_f || !com_g || !com_q || !evals || !proofs || !randomizers || !verdicts || (pok && (!ped_com || !pok_s)) ||
+            (own_transcripts ? !pok : !c || !rho || (pok && !k_out)))
             return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < RVCHUNK ? n : RVCHUNK;
         const uint32_t n_fixed = RV_N_FIX_KZG + (pok ? N_FIX_DLEQ : 0), n_var = RV_N_VAR_KZG + (pok ? N_VAR_DLEQ : 0);
         for (RowBuf* b : {&k->b_ped, &k->b_comf, &k->b_comg, &k->b_comq, &k->b_evals, &k->b_proofs, &k->b_c, &k->b_rho, &k->b_rz, &k->b_pokc,
-                          &k->b_poks, &k->b_k, &k->b_flags, &k->b_verdict})
+                          &k->b_poks, &k->b_k, &k->b_flags, &k->b_verdict, &k->b_pts, &k->b_pedc, &k->b_cd})
             b->reserve(chunk);
         grow(k->b_scal, chunk * 8 * RV_N_SCALARS);
         grow(k->b_part, chunk * (uint64_t)(RV_N_FIX_KZG + N_FIX_DLEQ + RV_N_VAR_KZG + N_VAR_DLEQ));
@@ -325,14 +374,20 @@ extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_
             k->b_comq.up(k->st, com_q, off, m);
             k->b_evals.up(k->st, evals, off, m);
             k->b_proofs.up(k->st, proofs, off, m);
-            k->b_c.up(k->st, c, off, m);
-            k->b_rho.up(k->st, rho, off, m);
+            if (!own_transcripts) {
+                k->b_c.up(k->st, c, off, m);
+                k->b_rho.up(k->st, rho, off, m);
+            }
             k->b_rz.up(k->st, randomizers, off, m);
             const RvArgs a{k->b_ped.words(), k->b_comf.words(), k->b_comg.words(), k->b_comq.words(), k->b_evals.words(), k->b_proofs.words(),
                            k->b_c.words(), k->b_rho.words(), k->b_rz.words(), pok ? k->b_pokc.words() : nullptr,
                            pok ? k->b_poks.words() : nullptr, m, n_fixed, n_var};
             const uint32_t grid = ceil_div(m, RVBLOCK);
             k->timer.mark(0, k->st);
+            if (own_transcripts) {
+                k_rv_challenges<<<grid, RVBLOCK, 0, k->st>>>(a, k->b_pts.words_mut(), k->b_c.words_mut(), k->b_rho.words_mut());
+                CG_KERNEL_CHECK();
+            }
             k_rv_check<<<grid, RVBLOCK, 0, k->st>>>(k->kc, a, k->b_scal.p, k->b_flags.bytes());
             CG_KERNEL_CHECK();
             k_rv_terms<<<ceil_div(m * n_fixed, RVBLOCK) + ceil_div(m * n_var, RVBLOCK), RVBLOCK, 0, k->st>>>(
@@ -352,9 +407,14 @@ extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_
                 k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, k->b_verdict.bytes());
             }
             CG_KERNEL_CHECK();
+            if (own_transcripts) {
+                k_rv_challenge_dleq<<<grid, RVBLOCK, 0, k->st>>>(a, k->b_pts.words(), k->b_k.words(), k->slots.compressed(slot), k->key_cmp.p,
+                                                                 k->b_pedc.words_mut(), k->b_cd.words_mut(), k->b_verdict.bytes());
+                CG_KERNEL_CHECK();
+            }
             k->timer.mark(2, k->st);
             k->b_verdict.down(k->st, verdicts, off, m);
-            if (pok) k->b_k.down(k->st, k_out, off, m);
+            if (pok && !own_transcripts) k->b_k.down(k->st, k_out, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
             k->timer.add();
         }
@@ -362,4 +422,20 @@ extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_
     } catch (...) {
         return translate_current_exception();
     }
+}
+}  // namespace
+
+extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
+                                     const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c,
+                                     const uint8_t* rho, const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s,
+                                     uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
+    return run_range_verify(k, false, slot, ped_com, com_f, com_g, com_q, evals, proofs, c, rho, randomizers, pok_c, pok_s, n, verdicts, k_out);
+}
+
+// `verify_n_bits` whole: CG_VERIFY_ACCEPT is exactly `verify_n_bits(..) == true`
+extern "C" int cg_range_verify_proofs_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
+                                            const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* randomizers,
+                                            const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts) {
+    return run_range_verify(k, true, slot, ped_com, com_f, com_g, com_q, evals, proofs, nullptr, nullptr, randomizers, pok_c, pok_s, n, verdicts,
+                            nullptr);
 }

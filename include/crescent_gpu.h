@@ -849,6 +849,65 @@ int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com,
                           const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts,
                           uint8_t* k_out);
 
+/* Range proofs in one call each way, with the library's own Merlin.  The transcripts of `prove_n_bits` and
+ * `verify_n_bits` - STROBE-128 over Keccak-f[1600] as the `merlin` crate computes them, every message the value's
+ * ark-serialize compressed bytes (creds/src/utils.rs:29-37), every challenge 31 bytes read little-endian - run on the
+ * device between the kernels of the calls above, so a proof is made, or checked, without a host step in between
+ * ("Range proofs in one call").  The multi-call entries above stay for hosts that run their own
+ * transcripts.
+ *
+ * Replaces: `RangeProof::prove_n_bits` (rangeproof.rs:114-339) whole, for n openings whose commitment has the bases of
+ *           `slot`: per chunk of showings the inputs go up once, the commit, quotient and open phases run back to back with
+ *           the range transcript's c and rho and the DLEQ transcript's c_dleq derived between them, the responses
+ *           s = nonce - c_dleq * secret follow, and the proof comes down once.
+ * openings, rand: as for cg_range_commit_batch; the randomness is the caller's, in the same order.
+ * ped_com:  n x 64 B ark-serialize uncompressed: `ped_open.c` (dlog.rs:24-29), which the reference takes as given and the
+ *           DLEQ's transcript absorbs as y_0.  One that fails ark's checked G1 deserialisation makes its showing
+ *           CG_SHOW_MALFORMED.
+ * com_f, com_g, com_q, evals, proofs, pok_c, pok_s: the fields of a `RangeProof` in the layouts cg_range_verify_batch
+ *           takes, which are the layouts the three calls and cg_range_respond_batch write: the same bytes as that path
+ *           gives for the same openings, rand and challenges.
+ * challenges_out: n x 3 x 32 B canonical Fr: c_dleq, c, rho; may be NULL.
+ * status:   n x CG_SHOW_MADE / CG_SHOW_MALFORMED.  CG_SHOW_MADE only if every phase made the showing; a malformed
+ *           showing (the conditions of the three calls, or a bad ped_com) has zero bytes in EVERY output row and leaves
+ *           its neighbours alone.
+ * Argument errors are reported before any HIP call; n = 0 is CG_OK; calls on one handle serialise.
+ * cg_range_pk_last_kernel_ms reads zeros after this call: its stages interleave. */
+int cg_range_prove_batch(cg_range_pk* k, uint32_t slot, const uint8_t* openings, const uint8_t* ped_com, const uint8_t* rand,
+                         uint64_t n, uint8_t* com_f, uint8_t* com_g, uint8_t* com_q, uint8_t* evals, uint8_t* proofs,
+                         uint8_t* pok_c, uint8_t* pok_s, uint8_t* challenges_out, uint8_t* status);
+/* Replaces: `RangeProof::verify_n_bits` (rangeproof.rs:342-424) whole: cg_range_verify_batch without c, rho and k_out.
+ *           c and rho are derived on the device from com_f, com_g, com_q as their bytes compress; behind the pairing the
+ *           DLEQ's challenge is recomputed from the slot's bases, k_0, ped_com, com_f_basis, k_1 and com_f and compared
+ *           with pok_c (dlog.rs:130-174).
+ * pok_c is required.  verdicts: CG_VERIFY_ACCEPT exactly where `verify_n_bits(..) == true`: where cg_range_verify_batch
+ * accepts AND the recomputed challenge equals pok_c; CG_VERIFY_MALFORMED as there, per showing; else CG_VERIFY_REJECT.
+ * The handle's latency mode is honoured, with identical verdicts.  Argument errors, n = 0, chunking and the lock are as
+ * for cg_range_verify_batch. */
+int cg_range_verify_proofs_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
+                                 const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* randomizers,
+                                 const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts);
+/* Replaces: the transcript of `DLogPoK::prove` / `DLogPoK::verify` (dlog.rs:56-58, 77-99; :130-132, 147-169) for n
+ *           showings of one shape: `Transcript::new(&[0u8])`, b"context string", then per statement b"num_bases", its
+ *           bases under b"base", b"k" and b"y", and the 31-byte challenge.  For hosts without Merlin (INTEGRATION.md,
+ *           "Hosts without Merlin"): between cg_show_commit_batch and cg_show_respond_batch, behind cg_verify_show_batch
+ *           and cg_range_verify_batch, and for the DLEQ of the three-call range path.  Host only, on the library's worker
+ *           threads: no handle, no HIP call, usable in a process without a GPU.
+ * Operands come in the forms the other entries hand them out:
+ * context:  context_len bytes; context_stride = 0: one context for the whole batch, otherwise showing i's starts at
+ *           context + i * context_stride; NULL with length 0 is `None`, which the reference absorbs as the empty string.
+ * n_bases:  n_statements counts; bases: the sum of them points, shared by the batch, 64 B ark-serialize uncompressed each
+ *           as they lie in a verifying key, statement by statement.
+ * k:        n x n_statements x 32 B ark-serialize COMPRESSED, the k_out / ts_out layout.
+ * y_head:   n x (n_statements - 1) x 64 B uncompressed: `committed` of a showing, ped_com of a range proof; may be NULL
+ *           with one statement.  y_last: n x 64 B: com_hidden of a showing, com_f of a range proof.
+ * c_out:    n x 32 B canonical Fr (the top byte is 0).
+ * The points are compressed here.  A coordinate >= q or invalid point flags are CG_ERR_INVALID_ARGUMENT naming the base
+ * or the showing, and nothing is written; whether a point is on the curve is for the verifying calls to say. */
+int cg_dlog_challenge_batch(const uint8_t* context, uint64_t context_len, uint64_t context_stride, uint32_t n_statements,
+                            const uint32_t* n_bases, const uint8_t* bases, const uint8_t* k, const uint8_t* y_head,
+                            const uint8_t* y_last, uint64_t n, uint8_t* c_out);
+
 /* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
  * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the
  * PreparedVerifyingKey bytes (*len of them; pvk_out = NULL only reports *len).  A buffer shorter than *len is

@@ -1009,6 +1009,71 @@ impl GpuRangeKey {
         }
         Ok(s)
     }
+
+    /// `RangeProof::prove_n_bits` in one call (`cg_range_prove_batch`): the three phases with the library's Merlin between
+    /// them, on the GPU.  `ped_com`: n x 64 B uncompressed, the commitments the openings open.
+    pub fn prove_batch(&self, slot: u32, openings: &[Fr], ped_com: &[u8], rand: &[Fr]) -> Result<RangeProofsMade, SynthesisError> {
+        let n = openings.len() / 2;
+        if openings.len() != 2 * n || ped_com.len() != n * 64 || rand.len() != n * sys::CG_RANGE_N_RAND {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (ob, rb) = (canonical_bytes(openings), canonical_bytes(rand));
+        let mut out = RangeProofsMade {
+            com_f: vec![0u8; n * 64],
+            com_g: vec![0u8; n * 64],
+            com_q: vec![0u8; n * 64],
+            evals: vec![0u8; n * 96],
+            proofs: vec![0u8; n * 288],
+            pok_c: vec![0u8; n * 32],
+            pok_s: vec![0u8; n * sys::CG_RANGE_N_RESP * 32],
+            challenges: vec![0u8; n * 96],
+            status: vec![0u8; n],
+        };
+        let rc = unsafe {
+            sys::cg_range_prove_batch(self.h, slot, ob.as_ptr(), ped_com.as_ptr(), rb.as_ptr(), n as u64, out.com_f.as_mut_ptr(),
+                                      out.com_g.as_mut_ptr(), out.com_q.as_mut_ptr(), out.evals.as_mut_ptr(), out.proofs.as_mut_ptr(),
+                                      out.pok_c.as_mut_ptr(), out.pok_s.as_mut_ptr(), out.challenges.as_mut_ptr(), out.status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(out)
+    }
+}
+
+/// What `GpuRangeKey::prove_batch` returns: the fields of n `RangeProof`s in the layouts `RangeProofRows` takes, the three
+/// challenges (c_dleq, c, rho; n x 3 x 32 B) and one CG_SHOW_* byte per opening; a malformed opening has zero bytes throughout
+pub struct RangeProofsMade {
+    pub com_f: Vec<u8>,
+    pub com_g: Vec<u8>,
+    pub com_q: Vec<u8>,
+    pub evals: Vec<u8>,
+    pub proofs: Vec<u8>,
+    pub pok_c: Vec<u8>,
+    pub pok_s: Vec<u8>,
+    pub challenges: Vec<u8>,
+    pub status: Vec<u8>,
+}
+
+/// `DLogPoK`'s Merlin transcript for n showings of one shape (`cg_dlog_challenge_batch`, host only): `n_bases` per
+/// statement, `bases` 64 B uncompressed each and shared by the batch, `k` n x n_statements x 32 B compressed, `y_head`
+/// n x (n_statements - 1) x 64 B, `y_last` n x 64 B; one `context` for the batch.  Returns n x 32 B canonical challenges.
+pub fn dlog_challenge_batch(context: Option<&[u8]>, n_bases: &[u32], bases: &[u8], k: &[u8], y_head: &[u8], y_last: &[u8]) -> Result<Vec<u8>, SynthesisError> {
+    let n = y_last.len() / 64;
+    let total: usize = n_bases.iter().map(|&b| b as usize).sum();
+    if n_bases.is_empty() || y_last.len() != n * 64 || bases.len() != total * 64 || k.len() != n * n_bases.len() * 32 || y_head.len() != n * (n_bases.len() - 1) * 64 {
+        return Err(SynthesisError::MalformedVerifyingKey);
+    }
+    let ctx = context.unwrap_or(&[]);
+    let mut c = vec![0u8; n * 32];
+    let rc = unsafe {
+        sys::cg_dlog_challenge_batch(if ctx.is_empty() { std::ptr::null() } else { ctx.as_ptr() }, ctx.len() as u64, 0, n_bases.len() as u32,
+                                     n_bases.as_ptr(), bases.as_ptr(), k.as_ptr(), y_head.as_ptr(), y_last.as_ptr(), n as u64, c.as_mut_ptr())
+    };
+    if rc != 0 {
+        return Err(map_err(rc));
+    }
+    Ok(c)
 }
 
 impl Drop for GpuRangeKey {
@@ -1111,6 +1176,31 @@ impl GpuRangeVerifyingKey {
             return Err(map_err(rc));
         }
         Ok((verdicts, k))
+    }
+
+    /// `RangeProof::verify_n_bits` in one call (`cg_range_verify_proofs_batch`): c and rho are derived and the DLEQ's
+    /// challenge is recomputed and compared on the GPU, so `rows.c` and `rows.rho` are not read (pass empty slices).
+    /// CG_VERIFY_ACCEPT exactly where `verify_n_bits` returns true.
+    pub fn verify_proofs_batch(&self, slot: u32, rows: &RangeProofRows) -> Result<Vec<u8>, SynthesisError> {
+        let n = rows.pok_c.len();
+        if rows.ped_com.len() != n * 64 || rows.com_f.len() != n * 64 || rows.com_g.len() != n * 64 || rows.com_q.len() != n * 64
+            || rows.evals.len() != n * 96 || rows.proofs.len() != n * 288 || rows.randomizers.len() != 2 * n
+            || rows.pok_s.len() != n * sys::CG_RANGE_N_RESP
+        {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (pc, ps) = (canonical_bytes(rows.pok_c), canonical_bytes(rows.pok_s));
+        let zb: Vec<u8> = rows.randomizers.iter().flat_map(|r| r.to_le_bytes()).collect();
+        let mut verdicts = vec![0u8; n];
+        let rc = unsafe {
+            sys::cg_range_verify_proofs_batch(self.h, slot, rows.ped_com.as_ptr(), rows.com_f.as_ptr(), rows.com_g.as_ptr(), rows.com_q.as_ptr(),
+                                              rows.evals.as_ptr(), rows.proofs.as_ptr(), zb.as_ptr(), pc.as_ptr(), ps.as_ptr(), n as u64,
+                                              verdicts.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(verdicts)
     }
 }
 

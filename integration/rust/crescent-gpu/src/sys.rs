@@ -463,4 +463,49 @@ extern "C" {
         verdicts: *mut u8,
         k_out: *mut u8,
     ) -> c_int;
+    pub fn cg_range_prove_batch(
+        k: *mut cg_range_pk,
+        slot: u32,
+        openings: *const u8,
+        ped_com: *const u8,
+        rand: *const u8,
+        n: u64,
+        com_f: *mut u8,
+        com_g: *mut u8,
+        com_q: *mut u8,
+        evals: *mut u8,
+        proofs: *mut u8,
+        pok_c: *mut u8,
+        pok_s: *mut u8,
+        challenges_out: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_range_verify_proofs_batch(
+        k: *mut cg_range_vk,
+        slot: u32,
+        ped_com: *const u8,
+        com_f: *const u8,
+        com_g: *const u8,
+        com_q: *const u8,
+        evals: *const u8,
+        proofs: *const u8,
+        randomizers: *const u8,
+        pok_c: *const u8,
+        pok_s: *const u8,
+        n: u64,
+        verdicts: *mut u8,
+    ) -> c_int;
+    pub fn cg_dlog_challenge_batch(
+        context: *const u8,
+        context_len: u64,
+        context_stride: u64,
+        n_statements: u32,
+        n_bases: *const u32,
+        bases: *const u8,
+        k: *const u8,
+        y_head: *const u8,
+        y_last: *const u8,
+        n: u64,
+        c_out: *mut u8,
+    ) -> c_int;
 }
