@@ -161,6 +161,14 @@ class _CgClientStateView(C.Structure):
                 ("credtype", C.c_void_p), ("credtype_len", C.c_uint64), ("config_str", C.c_void_p), ("config_len", C.c_uint64)]
 
 
+class _CgShowRangeLink(C.Structure):
+    _fields_ = [("committed_index", C.c_uint32), ("slot", C.c_uint32)]
+
+
+class _CgRangeRows(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("com_f", "com_g", "com_q", "evals", "proofs", "randomizers", "pok_c", "pok_s")]
+
+
 class _CgR1csHeader(C.Structure):
     _fields_ = [("field_size", C.c_uint32), ("n_wires", C.c_uint32), ("n_pub_out", C.c_uint32),
                 ("n_pub_in", C.c_uint32), ("n_prv_in", C.c_uint32), ("n_constraints", C.c_uint32),
@@ -273,6 +281,10 @@ _SIGNATURES = {
     "cg_range_verify_proofs_batch": (C.c_int, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9 + [C.c_uint64, C.c_void_p]),
     "cg_dlog_challenge_batch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "cg_verify_showings_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6
+                                 + [C.c_uint32, C.POINTER(_CgShowRangeLink), C.c_void_p, C.POINTER(_CgRangeRows), C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cg_pvk_set_showings_overlap": (C.c_int, [C.c_void_p, C.c_int32]),
+    "cg_show_shift_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
@@ -1585,6 +1597,111 @@ class Groth16:
         return [bool(v == CG_VERIFY_ACCEPT) for v in verdicts]
 
     @staticmethod
+    def verify_showings_batch_packed(pvk: "PreparedVerifyingKey", range_vk, io_types, revealed, rand_proofs, com_hidden, committed, pok_c,
+                                     pok_s, links, shifts, ranges, context=None, context_len: Optional[int] = None, context_stride: int = 0):
+        """cg_verify_showings_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = rand_proofs / 256):
+        the cryptographic checks of `verify_show` (creds/src/lib.rs:630-658, :832-890) in one call.  links: one
+        (committed_index, slot) per range proof of a showing; shifts: n x n_ranges x 32 B; ranges: per link the tuple
+        (com_f, com_g, com_q, evals, proofs, randomizers, pok_c, pok_s) of n rows each, as range_verify_proofs_batch_packed
+        takes them.  context: as dlog_challenge_batch takes it.  range_vk may be None without links.  Returns (verdicts n,
+        part_verdicts n x (1 + n_ranges): the Groth16 part, then the range parts)."""
+        io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+        n_rev, n_hid, n_com = (int((io == t).sum()) for t in (CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED))
+        pb = _u8(rand_proofs)
+        if pb.size % 256:
+            raise ValueError("rand_proofs must be n x 256 bytes")
+        n = pb.size // 256
+        links = list(links)
+        if len(ranges) != len(links):
+            raise ValueError("one set of range proof rows per link")
+        n_ranges = len(links)
+        rev, comh, comm = _u8(revealed, 32 * n_rev * n), _u8(com_hidden, 64 * n), _u8(committed, 64 * n_com * n)
+        pc, ps = _u8(pok_c, 32 * n), _u8(pok_s, 32 * (2 * n_com + n_hid + 1) * n)
+        sb = _u8(shifts, 32 * n_ranges * n)
+        cb = _u8(context if context is not None else b"")
+        if context_len is None:
+            context_len = context_stride if context_stride else cb.size
+        if cb.size < (context_stride * (n - 1) + context_len if context_stride and n else context_len):
+            raise ValueError("context is shorter than its length and stride say")
+        ptr = lambda a: _ptr(a) if a.size else None
+        widths = (64, 64, 64, 96, 288, 32, 32, 32 * CG_RANGE_N_RESP)
+        keep = [[_u8(a, w * n) for a, w in zip(rows, widths)] for rows in ranges]
+        c_links = (_CgShowRangeLink * max(n_ranges, 1))(*[_CgShowRangeLink(int(ci), int(slot)) for ci, slot in links])
+        c_rows = (_CgRangeRows * max(n_ranges, 1))(*[_CgRangeRows(*[ptr(a) for a in rows]) for rows in keep])
+        verdicts, parts = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 1 + n_ranges), np.uint8)
+        _check(lib().cg_verify_showings_batch(pvk._h, None if range_vk is None else range_vk._h, ptr(io), io.size, ptr(cb), context_len,
+                                              context_stride, ptr(rev), ptr(pb), ptr(comh), ptr(comm), ptr(pc), ptr(ps), n_ranges,
+                                              c_links if n_ranges else None, ptr(sb), c_rows if n_ranges else None, n, _ptr(verdicts),
+                                              _ptr(parts)))
+        return verdicts[:n], parts[:n]
+
+    @staticmethod
+    def verify_showings_batch(pvk: "PreparedVerifyingKey", range_vk, io_types, shows, links, shifts, range_proofs, context,
+                              randomizers=None) -> List[bool]:
+        """The cryptographic checks of `verify_show` / `verify_show_mdl` (creds/src/lib.rs:630-658, :832-890) for n showings
+        of one layout in one call: `ShowGroth16::verify`, per link ped_com = commited_inputs[committed_index] - t *
+        gamma_abc_g1[pos] and `ShowRange::verify` about it, all on the GPU (cg_verify_showings_batch).  shows: a sequence of
+        (ShowGroth16, revealed inputs); links: (committed_index, slot of range_vk) per range proof of a showing; shifts[i][j]:
+        the public value t of showing i's link j (ints); range_proofs[i][j]: its RangeProof; context: bytes, or None as the
+        reference's `None`; randomizers[i][j]: (r_1, r_2) below 2^128, None draws them with `secrets`.  True exactly
+        where every check of the reference passes."""
+        io = [int(t) for t in io_types]
+        n, links = len(shows), list(links)
+        if n == 0:
+            return []
+        n_rev, n_hid, n_com = io.count(CG_IO_REVEALED), io.count(CG_IO_HIDDEN), io.count(CG_IO_COMMITTED)
+        shapes = [2] * n_com + [n_hid + 1]
+        for sh, x in shows:
+            if [len(si) for si in sh.pok_s] != shapes or len(sh.commited_inputs) != n_com or len(_inputs_array(x)) != 32 * n_rev:
+                raise ValueError("a showing does not have the shape of io_types")
+        if len(shifts) != n or len(range_proofs) != n or any(len(a) != len(links) or len(b) != len(links) for a, b in zip(shifts, range_proofs)):
+            raise ValueError("one shift and one range proof per showing and link")
+        if randomizers is None:
+            import secrets
+            randomizers = [[(secrets.randbits(128), secrets.randbits(128)) for _ in links] for _ in range(n)]
+        fr = lambda v: int(v).to_bytes(32, "little")
+        cat = lambda parts: _u8(b"".join(parts))
+        ranges = []
+        for j in range(len(links)):
+            ps = [range_proofs[i][j] for i in range(n)]
+            ranges.append((cat(bytes(p.com_f) for p in ps), cat(bytes(p.com_g) for p in ps), cat(bytes(p.com_q) for p in ps),
+                           cat(fr(p.eval_g) + fr(p.eval_gw) + fr(p.eval_w_hat) for p in ps),
+                           cat(bytes(p.proof_g) + bytes(p.proof_gw) + bytes(p.proof_w_hat) for p in ps),
+                           cat(int(r).to_bytes(16, "little") for i in range(n) for r in randomizers[i][j]),
+                           cat(fr(p.dleq_c) for p in ps), cat(b"".join(fr(x) for si in p.dleq_s for x in si) for p in ps)))
+        verdicts, _ = Groth16.verify_showings_batch_packed(
+            pvk, range_vk, io, cat(_inputs_array(x).tobytes() for _, x in shows), cat(sh.rand_proof for sh, _ in shows),
+            cat(sh.com_hidden_inputs for sh, _ in shows), cat(b"".join(sh.commited_inputs) for sh, _ in shows),
+            cat(fr(sh.pok_c) for sh, _ in shows), cat(b"".join(fr(s) for si in sh.pok_s for s in si) for sh, _ in shows), links,
+            cat(fr(t) for row in shifts for t in row), ranges, context)
+        return [bool(v == CG_VERIFY_ACCEPT) for v in verdicts]
+
+    @staticmethod
+    def show_shift_batch(pvk: "PreparedVerifyingKey", input_index: int, openings, commitments, shifts):
+        """cg_show_shift_batch: the creating side's link `com.m -= t; com.c -= bases[0] * t` (creds/src/lib.rs:370-372,
+        :468-470, :505-507) for n openings of the committed input `input_index` (an index into io_types).  openings: n x 64
+        B (m, r) or a sequence of (m, r) ints; commitments: n x 64 B or a sequence of 64-byte points; shifts: n x 32 B or a
+        sequence of ints.  Returns (openings_out n x 2 x 32, ped_com n x 64, status n) as uint8 arrays, in the layouts
+        range_prove_batch_packed takes; a CG_SHOW_MALFORMED row is zero bytes."""
+        fr = lambda v: int(v).to_bytes(32, "little")
+        if isinstance(openings, (list, tuple)):
+            openings = b"".join(fr(m) + fr(r) for m, r in openings)
+        if isinstance(commitments, (list, tuple)):
+            commitments = b"".join(bytes(c) for c in commitments)
+        if isinstance(shifts, (list, tuple)):
+            shifts = b"".join(fr(t) for t in shifts)
+        ob = _u8(openings)
+        if ob.size % 64:
+            raise ValueError("openings must be n x 64 bytes (m, r)")
+        n = ob.size // 64
+        cb, sb = _u8(commitments, 64 * n), _u8(shifts, 32 * n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        out, ped, status = np.zeros((m, 2, 32), np.uint8), np.zeros((m, 64), np.uint8), np.zeros(m, np.uint8)
+        _check(lib().cg_show_shift_batch(pvk._h, int(input_index), ptr(ob), ptr(cb), ptr(sb), n, _ptr(out), _ptr(ped), _ptr(status)))
+        return out[:n], ped[:n], status[:n]
+
+    @staticmethod
     def dlog_challenge_batch(n_bases, bases, k, y_head, y_last, context=None, context_len: Optional[int] = None,
                              context_stride: int = 0) -> np.ndarray:
         """cg_dlog_challenge_batch (host only, no GPU needed): `DLogPoK`'s Merlin transcript (creds/src/dlog.rs:56-99) for n
@@ -1649,6 +1766,11 @@ class PreparedVerifyingKey(_LatencyMode, _Handle):
         self.gamma_abc_g1 = b[520:520 + 64 * n_abc].reshape(n_abc, 64).copy()
         if latency:
             self.set_latency(True)
+
+    def set_showings_overlap(self, on: bool) -> None:
+        """cg_pvk_set_showings_overlap: whether verify_showings_batch starts the range half beside the Groth16 half (the
+        default) or behind it; the bytes are the same"""
+        _check(lib().cg_pvk_set_showings_overlap(self._h, 1 if on else 0))
 
     def last_kernel_ms(self) -> Tuple[float, float]:
         """HIP-event milliseconds of the last verifying call on this key: (group stage, pairing)"""

@@ -77,11 +77,13 @@ int set_latency_mode(K* k, int32_t on) {
 }
 
 // The Pedersen bases registered on a range key: per slot the fixed-base tables of one pair (2 x 1 MB on the device) and
-// the pair's 2 x 32 compressed bytes, which the DLEQ's transcript absorbs under b"base".
+// the pair's 2 x 32 compressed bytes, which the DLEQ's transcript absorbs under b"base"; on the host the pair's 128 bytes
+// as registered, which cg_verify_showings_batch compares with the bases of the Groth16 key it is called with.
 struct PedersenSlots {
     static constexpr uint32_t MAX_SLOTS = 64;
     std::vector<DevBuf<G1Affine>> tabs;
     std::vector<DevBuf<uint8_t>> cmps;
+    std::vector<std::vector<uint8_t>> registered;
     // cg_range_pk_add_bases / cg_range_vk_add_bases after their null check
     int add(KeyHandle& k, const uint8_t ped_bases[128], uint32_t* slot) {
         std::vector<G1Affine> bases(3, G1Affine::inf()), tab;    // build_tables skips the first entry
@@ -103,6 +105,8 @@ struct PedersenSlots {
             h2d_sync(dc.p, cmp, sizeof(cmp), k.st);
             tabs.reserve(tabs.size() + 1);
             cmps.reserve(cmps.size() + 1);
+            registered.reserve(registered.size() + 1);
+            registered.emplace_back(ped_bases, ped_bases + 128);
             tabs.push_back(std::move(d));
             cmps.push_back(std::move(dc));
             *slot = (uint32_t)tabs.size() - 1;

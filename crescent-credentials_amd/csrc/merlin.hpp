@@ -2,6 +2,7 @@
 // Keccak-f[1600] - and the two transcript shapes the reference builds on them (creds/src/utils.rs:29-37):
 //   range     com_f, com_g -> c; com_q -> rho                                   (creds/src/rangeproof.rs:250-274, 352-366)
 //   DLogPoK   context, then per statement its bases, k and y -> c               (creds/src/dlog.rs:56-58, 77-99, 130-169)
+//             as the fixed shape of a range proof's DLEQ, and for any shape (ml_dlog_shape_challenge: a showing's)
 // Every message is the value's ark-serialize COMPRESSED bytes, every transcript is Transcript::new(&[0u8]) and every
 // challenge 31 bytes under the label [0u8], read little-endian: a canonical scalar whose top byte is 0.
 //
@@ -196,7 +197,16 @@ CG_HD void ml_transcript(uint8_t* st, int n, ItemFn item) {
     });
 }
 
-// ---- the two shapes: every point a pointer to its 32 compressed bytes, every challenge written as 32 bytes (top byte 0) ----
+// add_to_transcript of a &[u8] (utils.rs:29-37): the message is u64le(len) ‖ bytes, absorbed as ONE AD operation in two
+// parts, so a slice is four segments where an item is three
+CG_HD MlSeg ml_slice_seg(MlLit label, const uint8_t* bytes, uint64_t len, int part) {
+    if (part == 0) return MlSeg{ML_META_AD, false, label.len, nullptr, label, nullptr};
+    if (part == 1) return MlSeg{ML_META_AD, true, 4, nullptr, ml_u32((uint32_t)(8 + len)), nullptr};
+    if (part == 2) return MlSeg{ML_AD, false, 8, nullptr, ml_u64(len), nullptr};
+    return MlSeg{ML_AD, true, (uint32_t)len, bytes, MlLit{0, 0, 0}, nullptr};
+}
+
+// ---- the shapes: every point a pointer to its 32 compressed bytes, every challenge written as 32 bytes (top byte 0) -------
 
 // The range transcript up to c (com_q null) or up to rho; a null destination is drawn and dropped.
 CG_HD void ml_range_challenges(uint8_t* st, const uint8_t* com_f, const uint8_t* com_g, const uint8_t* com_q, uint8_t* c, uint8_t* rho) {
@@ -231,6 +241,36 @@ CG_HD void ml_range_dleq_challenge(uint8_t* st, const uint8_t* slot_bases, const
             case 12: return ml_append(ml_lit("y"), com_f, 32);
             default: return ml_challenge(c);
         }
+    });
+}
+
+// DLogPoK's transcript for any shape (dlog.rs:56-58, 77-99; :130-132, 147-169), one text for host and device: the context
+// as a slice (null with length 0 is `None`), then per statement i its n_bases(i) bases - taken in order from `bases` -
+// under b"num_bases" and b"base", k + 32 i under b"k" and y + 32 i under b"y", then the challenge.  Which statement an
+// item belongs to is found by walking the counts: a showing has a handful of statements.  c: 32 bytes.
+template <class CountFn>
+CG_HD void ml_dlog_shape_challenge(uint8_t* st, const uint8_t* context, uint64_t context_len, uint32_t n_statements, CountFn n_bases,
+                                   const uint8_t* bases, const uint8_t* k, const uint8_t* y, uint8_t* c) {
+    c[ML_CHALLENGE] = 0;
+    uint32_t n_items = 1;
+    for (uint32_t i = 0; i < n_statements; ++i) n_items += n_bases(i) + 3;
+    Strobe s = ml_strobe(st);
+    ml_run(s, 7 + 3 * (int)n_items, [&](int seg) {
+        if (seg < 3) return ml_item_seg(ml_append(ml_lit("dom-sep"), ml_zero_byte()), seg);
+        if (seg < 7) return ml_slice_seg(ml_lit("context string"), context, context_len, seg - 3);
+        const int part = (seg - 7) % 3;
+        uint32_t j = (uint32_t)(seg - 7) / 3, i = 0, first = 0;
+        if (j + 1 == n_items) return ml_item_seg(ml_challenge(c), part);
+        while (j >= n_bases(i) + 3) {
+            j -= n_bases(i) + 3;
+            first += n_bases(i);
+            ++i;
+        }
+        const uint32_t nb = n_bases(i);
+        if (j == 0) return ml_item_seg(ml_append(ml_lit("num_bases"), ml_u64(nb)), part);
+        if (j <= nb) return ml_item_seg(ml_append(ml_lit("base"), bases + 32 * (uint64_t)(first + j - 1), 32), part);
+        if (j == nb + 1) return ml_item_seg(ml_append(ml_lit("k"), k + 32 * (uint64_t)i, 32), part);
+        return ml_item_seg(ml_append(ml_lit("y"), y + 32 * (uint64_t)i, 32), part);
     });
 }
 
@@ -279,13 +319,8 @@ struct MerlinTranscript {
     }
     void append_message(const uint8_t* label, uint32_t label_len, const uint8_t* msg, uint32_t len) { op(label, label_len, ML_AD, msg, len, nullptr); }
     void challenge_bytes(const uint8_t* label, uint32_t label_len, uint8_t* out, uint32_t n) { op(label, label_len, ML_PRF, nullptr, n, out); }
-    // add_to_transcript of a &[u8]: the message is u64le(len) ‖ bytes, absorbed as one AD operation in two parts
     void append_slice(MlLit label, const uint8_t* bytes, uint64_t len) {
-        const MlSeg g[4] = {{ML_META_AD, false, label.len, nullptr, label, nullptr},
-                            {ML_META_AD, true, 4, nullptr, ml_u32((uint32_t)(8 + len)), nullptr},
-                            {ML_AD, false, 8, nullptr, ml_u64(len), nullptr},
-                            {ML_AD, true, (uint32_t)len, bytes, MlLit{0, 0, 0}, nullptr}};
-        ml_run(s, 4, [&](int i) { return g[i]; });
+        ml_run(s, 4, [&](int i) { return ml_slice_seg(label, bytes, len, i); });
     }
     void append(const MlItem& it) {
         ml_run(s, 3, [&](int i) { return ml_item_seg(it, i); });

@@ -24,6 +24,8 @@
 // A malformed showing costs nothing after k_rv_check: every later lane of it returns at once.
 // cg_range_verify_proofs_batch is the same call with the transcripts on the device (merlin.hpp): k_rv_challenges in front
 // derives c and rho, k_rv_challenge_dleq behind recomputes the DLEQ's challenge and compares it with pok_c.
+// Both entries are run_range_verify over rv_chunk, one chunk's copies and kernels; rangeverify.hpp's internal entry hands the
+// same rv_chunk to cg_verify_showings_batch (verify.hip) with ped_com and the verdicts as device pointers.
 // The handle's device, stream and lock, the timing of the two stages, the slots and the per-call arrays are key_handle.hpp's
 // (KeyHandle, StageTimer, PedersenSlots, RowBuf), shared with cg_pvk and cg_range_pk; the chains are scalar_mul_mixed.
 #include <memory>
@@ -337,82 +339,99 @@ extern "C" int cg_range_vk_set_latency_mode(cg_range_vk* k, int32_t on) { return
 extern "C" int cg_range_vk_last_kernel_ms(cg_range_vk* k, float* group_ms, float* pairing_ms) { return last_kernel_ms(k, group_ms, pairing_ms); }
 
 namespace {
-// Both verifying entries.  own_transcripts (cg_range_verify_proofs_batch): c and rho are derived in front of the five
-// kernels and the DLEQ's challenge is recomputed and compared behind them, so neither comes in and k_0, k_1 do not go out.
-int run_range_verify(cg_range_vk* k, bool own_transcripts, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
-                     const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c, const uint8_t* rho,
-                     const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
+// one call's arrays on the host, as the caller laid them out; which of them may be null depends on the entry
+struct RvHost {
+    const uint8_t *ped_com, *com_f, *com_g, *com_q, *evals, *proofs, *c, *rho, *randomizers, *pok_c, *pok_s;
+};
+
+void rv_reserve(cg_range_vk* k, uint64_t chunk) {
+    for (RowBuf* b : {&k->b_ped, &k->b_comf, &k->b_comg, &k->b_comq, &k->b_evals, &k->b_proofs, &k->b_c, &k->b_rho, &k->b_rz, &k->b_pokc,
+                      &k->b_poks, &k->b_k, &k->b_flags, &k->b_verdict, &k->b_pts, &k->b_pedc, &k->b_cd})
+        b->reserve(chunk);
+    grow(k->b_scal, chunk * 8 * RV_N_SCALARS);
+    grow(k->b_part, chunk * (uint64_t)(RV_N_FIX_KZG + N_FIX_DLEQ + RV_N_VAR_KZG + N_VAR_DLEQ));
+    grow(k->b_pair, chunk * 2);
+    grow(k->b_miller, chunk);
+}
+
+// One chunk of either verifying entry on the key's stream: rows [off, off + m) go up, the kernels follow; nothing comes
+// down and nothing waits.  own_transcripts (cg_range_verify_proofs_batch): c and rho are derived in front of the five
+// kernels and the DLEQ's challenge is recomputed and compared behind them.  d_ped_com, where given, is ped_com on the
+// device already, and d_verdicts, where given, takes the verdict bytes instead of the key's own array.
+void rv_chunk(cg_range_vk* k, bool own_transcripts, uint32_t slot, const G1Affine* tab_slot, const RvHost& h, uint64_t off, uint64_t m,
+              const uint32_t* d_ped_com, uint8_t* d_verdicts) {
+    const bool pok = h.pok_c != nullptr;
+    const uint32_t n_fixed = RV_N_FIX_KZG + (pok ? N_FIX_DLEQ : 0), n_var = RV_N_VAR_KZG + (pok ? N_VAR_DLEQ : 0);
+    uint8_t* verdict = d_verdicts ? d_verdicts : k->b_verdict.bytes();
+    if (pok) {
+        if (!d_ped_com) k->b_ped.up(k->st, h.ped_com, off, m);
+        k->b_pokc.up(k->st, h.pok_c, off, m);
+        k->b_poks.up(k->st, h.pok_s, off, m);
+    }
+    k->b_comf.up(k->st, h.com_f, off, m);
+    k->b_comg.up(k->st, h.com_g, off, m);
+    k->b_comq.up(k->st, h.com_q, off, m);
+    k->b_evals.up(k->st, h.evals, off, m);
+    k->b_proofs.up(k->st, h.proofs, off, m);
+    if (!own_transcripts) {
+        k->b_c.up(k->st, h.c, off, m);
+        k->b_rho.up(k->st, h.rho, off, m);
+    }
+    k->b_rz.up(k->st, h.randomizers, off, m);
+    const RvArgs a{d_ped_com ? d_ped_com : k->b_ped.words(), k->b_comf.words(), k->b_comg.words(), k->b_comq.words(), k->b_evals.words(),
+                   k->b_proofs.words(), k->b_c.words(), k->b_rho.words(), k->b_rz.words(), pok ? k->b_pokc.words() : nullptr,
+                   pok ? k->b_poks.words() : nullptr, m, n_fixed, n_var};
+    const uint32_t grid = ceil_div(m, RVBLOCK);
+    k->timer.mark(0, k->st);
+    if (own_transcripts) {
+        k_rv_challenges<<<grid, RVBLOCK, 0, k->st>>>(a, k->b_pts.words_mut(), k->b_c.words_mut(), k->b_rho.words_mut());
+        CG_KERNEL_CHECK();
+    }
+    k_rv_check<<<grid, RVBLOCK, 0, k->st>>>(k->kc, a, k->b_scal.p, k->b_flags.bytes());
+    CG_KERNEL_CHECK();
+    k_rv_terms<<<ceil_div(m * n_fixed, RVBLOCK) + ceil_div(m * n_var, RVBLOCK), RVBLOCK, 0, k->st>>>(
+        a, k->b_scal.p, k->b_flags.bytes(), k->tab.p, tab_slot, k->b_part.p);
+    CG_KERNEL_CHECK();
+    k_rv_sum<<<ceil_div(m * (pok ? 4 : 2), RVBLOCK), RVBLOCK, 0, k->st>>>(a, k->b_flags.bytes(), k->b_part.p, k->b_pair.p, k->b_k.words_mut());
+    CG_KERNEL_CHECK();
+    k->timer.mark(1, k->st);
+    if (k->latency) {
+        k_rv_lone_miller<<<(uint32_t)m, TEAM_WIDTH, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live,
+                                                               k->h_live, k->b_miller.p);
+        CG_KERNEL_CHECK();
+        k_rv_lone_final<<<(uint32_t)m, TEAM_WIDTH, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, verdict);
+    } else {
+        k_rv_miller<<<grid, RVBLOCK, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live, k->h_live, k->b_miller.p);
+        CG_KERNEL_CHECK();
+        k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, verdict);
+    }
+    CG_KERNEL_CHECK();
+    if (own_transcripts) {
+        k_rv_challenge_dleq<<<grid, RVBLOCK, 0, k->st>>>(a, k->b_pts.words(), k->b_k.words(), k->slots.compressed(slot), k->key_cmp.p,
+                                                         k->b_pedc.words_mut(), k->b_cd.words_mut(), verdict);
+        CG_KERNEL_CHECK();
+    }
+    k->timer.mark(2, k->st);
+}
+
+// Both public verifying entries: the chunks one after the other, each waited for before its verdicts are the caller's
+int run_range_verify(cg_range_vk* k, bool own_transcripts, uint32_t slot, const RvHost& h, uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     try {
         std::lock_guard<std::mutex> lk(k->mu);
         const G1Affine* tab_slot = k->slots.table(slot, "cg_range_vk_add_bases");
         if (n == 0) return CG_OK;
-        const bool pok = pok_c != nullptr;
-        if (!com_f || !com_g || !com_q || !evals || !proofs || !randomizers || !verdicts || (pok && (!ped_com || !pok_s)) ||
-            (own_transcripts ? !pok : !c || !rho || (pok && !k_out)))
+        const bool pok = h.pok_c != nullptr;
+        if (!h.com_f || !h.com_g || !h.com_q || !h.evals || !h.proofs || !h.randomizers || !verdicts || (pok && (!h.ped_com || !h.pok_s)) ||
+            (own_transcripts ? !pok : !h.c || !h.rho || (pok && !k_out)))
             return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < RVCHUNK ? n : RVCHUNK;
-        const uint32_t n_fixed = RV_N_FIX_KZG + (pok ? N_FIX_DLEQ : 0), n_var = RV_N_VAR_KZG + (pok ? N_VAR_DLEQ : 0);
-        for (RowBuf* b : {&k->b_ped, &k->b_comf, &k->b_comg, &k->b_comq, &k->b_evals, &k->b_proofs, &k->b_c, &k->b_rho, &k->b_rz, &k->b_pokc,
-                          &k->b_poks, &k->b_k, &k->b_flags, &k->b_verdict, &k->b_pts, &k->b_pedc, &k->b_cd})
-            b->reserve(chunk);
-        grow(k->b_scal, chunk * 8 * RV_N_SCALARS);
-        grow(k->b_part, chunk * (uint64_t)(RV_N_FIX_KZG + N_FIX_DLEQ + RV_N_VAR_KZG + N_VAR_DLEQ));
-        grow(k->b_pair, chunk * 2);
-        grow(k->b_miller, chunk);
+        rv_reserve(k, chunk);
         k->timer.reset();
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
-            if (pok) {
-                k->b_ped.up(k->st, ped_com, off, m);
-                k->b_pokc.up(k->st, pok_c, off, m);
-                k->b_poks.up(k->st, pok_s, off, m);
-            }
-            k->b_comf.up(k->st, com_f, off, m);
-            k->b_comg.up(k->st, com_g, off, m);
-            k->b_comq.up(k->st, com_q, off, m);
-            k->b_evals.up(k->st, evals, off, m);
-            k->b_proofs.up(k->st, proofs, off, m);
-            if (!own_transcripts) {
-                k->b_c.up(k->st, c, off, m);
-                k->b_rho.up(k->st, rho, off, m);
-            }
-            k->b_rz.up(k->st, randomizers, off, m);
-            const RvArgs a{k->b_ped.words(), k->b_comf.words(), k->b_comg.words(), k->b_comq.words(), k->b_evals.words(), k->b_proofs.words(),
-                           k->b_c.words(), k->b_rho.words(), k->b_rz.words(), pok ? k->b_pokc.words() : nullptr,
-                           pok ? k->b_poks.words() : nullptr, m, n_fixed, n_var};
-            const uint32_t grid = ceil_div(m, RVBLOCK);
-            k->timer.mark(0, k->st);
-            if (own_transcripts) {
-                k_rv_challenges<<<grid, RVBLOCK, 0, k->st>>>(a, k->b_pts.words_mut(), k->b_c.words_mut(), k->b_rho.words_mut());
-                CG_KERNEL_CHECK();
-            }
-            k_rv_check<<<grid, RVBLOCK, 0, k->st>>>(k->kc, a, k->b_scal.p, k->b_flags.bytes());
-            CG_KERNEL_CHECK();
-            k_rv_terms<<<ceil_div(m * n_fixed, RVBLOCK) + ceil_div(m * n_var, RVBLOCK), RVBLOCK, 0, k->st>>>(
-                a, k->b_scal.p, k->b_flags.bytes(), k->tab.p, tab_slot, k->b_part.p);
-            CG_KERNEL_CHECK();
-            k_rv_sum<<<ceil_div(m * (pok ? 4 : 2), RVBLOCK), RVBLOCK, 0, k->st>>>(a, k->b_flags.bytes(), k->b_part.p, k->b_pair.p, k->b_k.words_mut());
-            CG_KERNEL_CHECK();
-            k->timer.mark(1, k->st);
-            if (k->latency) {
-                k_rv_lone_miller<<<(uint32_t)m, TEAM_WIDTH, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live,
-                                                                       k->h_live, k->b_miller.p);
-                CG_KERNEL_CHECK();
-                k_rv_lone_final<<<(uint32_t)m, TEAM_WIDTH, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, k->b_verdict.bytes());
-            } else {
-                k_rv_miller<<<grid, RVBLOCK, 0, k->st>>>(k->b_pair.p, k->b_flags.bytes(), m, k->beta_h_c.p, k->h_c.p, k->beta_h_live, k->h_live, k->b_miller.p);
-                CG_KERNEL_CHECK();
-                k_rv_final<<<grid, RVBLOCK, 0, k->st>>>(k->b_miller.p, k->b_flags.bytes(), m, k->b_verdict.bytes());
-            }
-            CG_KERNEL_CHECK();
-            if (own_transcripts) {
-                k_rv_challenge_dleq<<<grid, RVBLOCK, 0, k->st>>>(a, k->b_pts.words(), k->b_k.words(), k->slots.compressed(slot), k->key_cmp.p,
-                                                                 k->b_pedc.words_mut(), k->b_cd.words_mut(), k->b_verdict.bytes());
-                CG_KERNEL_CHECK();
-            }
-            k->timer.mark(2, k->st);
+            rv_chunk(k, own_transcripts, slot, tab_slot, h, off, m, nullptr, nullptr);
             k->b_verdict.down(k->st, verdicts, off, m);
             if (pok && !own_transcripts) k->b_k.down(k->st, k_out, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
@@ -425,17 +444,36 @@ int run_range_verify(cg_range_vk* k, bool own_transcripts, uint32_t slot, const 
 }
 }  // namespace
 
+// ---- the internal entry (rangeverify.hpp): what cg_verify_showings_batch needs of a range key it did not load ------------
+namespace cg {
+std::mutex& range_vk_lock(cg_range_vk* k) { return k->mu; }
+int range_vk_device(const cg_range_vk* k) { return k->device; }
+hipStream_t range_vk_stream(cg_range_vk* k) { return k->st; }
+const uint8_t* range_vk_slot_bytes(const cg_range_vk* k, uint32_t slot) {
+    return slot < k->slots.registered.size() ? k->slots.registered[slot].data() : nullptr;
+}
+void range_vk_reserve(cg_range_vk* k, uint64_t chunk) {
+    rv_reserve(k, chunk);
+    k->timer.reset();                     // the stages of such a call interleave with another handle's: nothing is timed
+}
+void range_vk_enqueue(cg_range_vk* k, uint32_t slot, const cg_range_rows& rows, uint64_t off, uint64_t m, const uint32_t* d_ped_com,
+                      uint8_t* d_verdicts) {
+    const RvHost h{nullptr, rows.com_f, rows.com_g, rows.com_q, rows.evals, rows.proofs, nullptr, nullptr, rows.randomizers, rows.pok_c, rows.pok_s};
+    rv_chunk(k, true, slot, k->slots.table(slot, "cg_range_vk_add_bases"), h, off, m, d_ped_com, d_verdicts);
+}
+}  // namespace cg
+
 extern "C" int cg_range_verify_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
                                      const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* c,
                                      const uint8_t* rho, const uint8_t* randomizers, const uint8_t* pok_c, const uint8_t* pok_s,
                                      uint64_t n, uint8_t* verdicts, uint8_t* k_out) {
-    return run_range_verify(k, false, slot, ped_com, com_f, com_g, com_q, evals, proofs, c, rho, randomizers, pok_c, pok_s, n, verdicts, k_out);
+    return run_range_verify(k, false, slot, RvHost{ped_com, com_f, com_g, com_q, evals, proofs, c, rho, randomizers, pok_c, pok_s}, n, verdicts, k_out);
 }
 
 // `verify_n_bits` whole: CG_VERIFY_ACCEPT is exactly `verify_n_bits(..) == true`
 extern "C" int cg_range_verify_proofs_batch(cg_range_vk* k, uint32_t slot, const uint8_t* ped_com, const uint8_t* com_f, const uint8_t* com_g,
                                             const uint8_t* com_q, const uint8_t* evals, const uint8_t* proofs, const uint8_t* randomizers,
                                             const uint8_t* pok_c, const uint8_t* pok_s, uint64_t n, uint8_t* verdicts) {
-    return run_range_verify(k, true, slot, ped_com, com_f, com_g, com_q, evals, proofs, nullptr, nullptr, randomizers, pok_c, pok_s, n, verdicts,
-                            nullptr);
+    return run_range_verify(k, true, slot, RvHost{ped_com, com_f, com_g, com_q, evals, proofs, nullptr, nullptr, randomizers, pok_c, pok_s}, n,
+                            verdicts, nullptr);
 }

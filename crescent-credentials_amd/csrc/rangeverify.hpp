@@ -116,3 +116,25 @@ CG_HD uint32_t rv_scalars(const RangeConsts& k, const RvIn& in, uint32_t* out, u
 }
 
 }  // namespace cg
+
+#ifdef __HIPCC__
+// ---- the internal entry of rangeverify.hip, for a caller that owns a second handle (cg_verify_showings_batch in verify.hip):
+// `verify_n_bits` whole for a chunk of showings whose ped_com is ALREADY ON THE DEVICE and whose verdicts stay there.
+// The caller holds the range key's lock for the whole call and orders the range key's stream against its own with events;
+// nothing here waits on the host.  The public cg_range_verify_proofs_batch is a thin caller of the same code.
+#include "common.hpp"
+
+namespace cg {
+std::mutex& range_vk_lock(cg_range_vk* k);
+int range_vk_device(const cg_range_vk* k);
+hipStream_t range_vk_stream(cg_range_vk* k);
+// the 128 bytes registered for `slot`, or null for an unknown slot; under the lock
+const uint8_t* range_vk_slot_bytes(const cg_range_vk* k, uint32_t slot);
+// room for chunks of `chunk` showings in every per-call array; under the lock, with the key's device current
+void range_vk_reserve(cg_range_vk* k, uint64_t chunk);
+// rows [off, off + m) of `rows` go up and the kernels of cg_range_verify_proofs_batch are put on the key's stream: ped_com is
+// read from d_ped_com (m x 16 words) and the m verdict bytes are written to d_verdicts.  m is at most the chunk reserved.
+void range_vk_enqueue(cg_range_vk* k, uint32_t slot, const cg_range_rows& rows, uint64_t off, uint64_t m, const uint32_t* d_ped_com,
+                      uint8_t* d_verdicts);
+}  // namespace cg
+#endif

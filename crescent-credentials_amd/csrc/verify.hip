@@ -39,6 +39,18 @@
 //                 points and the k_i of DLogPoK::prove (creds/src/dlog.rs:60-75), affine, as ark-serialize writes them
 // cg_show_respond_batch, the responses once the host's transcript has produced c, is host arithmetic.
 //
+// cg_verify_showings_batch verifies a showing whole: the cryptographic checks of `verify_show` (creds/src/lib.rs:630-658,
+// :832-890) for a batch of showings of one layout, each with its range proofs.  It owns a cg_range_vk beside the cg_pvk and a
+// chunk of showings runs, with nothing coming down in between,
+//   k_show_link       one lane per (range, showing): ped_com = committed - t·gamma_abc[pos] (show_link.hpp) -> 64 B rows
+//   the kernels of cg_verify_show_batch, unchanged
+//   k_show_challenge  one lane per showing: the DLogPoK's Merlin transcript (merlin.hpp) over the compressed bases, the k_i of
+//                     k_show_k and the y_i as their bytes stand; c' == pok_c keeps a showing accepted
+//   the kernels of cg_range_verify_proofs_batch per range, on the range key's stream behind an event, reading ped_com where
+//                     k_show_link wrote it (rangeverify.hpp's internal entry)
+//   k_show_verdict    one lane per showing: the parts side by side and their conjunction
+// cg_show_shift_batch is the creating side's link (lib.rs:370-372): k_show_shift, the same row routine with the opening.
+//
 // Shared by the three entries: the double-and-add chains are fixed_base.hpp's scalar_mul_254_mixed; ark_codec.hpp reads and
 // writes every point on the device; io_layout parses a call's io_types once, for the verifier's and the creator's shapes
 // alike; and the handle has one set of per-call arrays, named by what they hold.  Shared with the range keys, in
@@ -50,6 +62,8 @@
 #include "key_handle.hpp"
 #include "pairing.hpp"
 #include "pairing_team.hpp"
+#include "rangeverify.hpp"
+#include "show_link.hpp"
 
 using namespace cg;
 
@@ -301,6 +315,104 @@ __global__ __launch_bounds__(VBLOCK) void k_show_k(uint64_t n, ShowShape sh, con
     dev_put_g1(to_affine(acc), out, true);
 }
 
+// ---- whole showings (verify_show, creds/src/lib.rs:531-700): the challenge, the link, the conjunction --------------------
+// The DLogPoK's transcript of a showing (dlog.rs:130-132, 147-169) and `c == self.c` (:171-174), one lane per showing, the
+// sponge in LDS at ML_STATE bytes per lane as in k_rv_challenge*.  The bases come compressed, once per call, in the order
+// the responses meet them (IoLayout::resp_tab); y_i is compressed here from committed / com_hidden as its bytes stand
+// (y_cmp: n_com + 1 points of 8 words per showing); k_i is k_show_k's output, on the device already.  A showing whose status
+// is not ST_OK has k_i of zero bytes and a verdict that says so: it is skipped.  c' goes out, with a byte c' == pok_c, and
+// a showing stays CG_VERIFY_ACCEPT only where that byte is set.  Arithmetic on bytes only: no private segment.
+__global__ __launch_bounds__(VBLOCK) void k_show_challenge(const uint32_t* __restrict__ com_hidden, const uint32_t* __restrict__ committed,
+                                                          const uint32_t* __restrict__ pok_c, uint64_t n, ShowShape sh,
+                                                          const uint8_t* __restrict__ bases_cmp, const uint32_t* __restrict__ k_pts,
+                                                          const uint8_t* __restrict__ context, uint64_t context_len, uint64_t context_stride,
+                                                          const uint8_t* __restrict__ status, uint32_t* __restrict__ y_cmp,
+                                                          uint32_t* __restrict__ c_out, uint8_t* __restrict__ same, uint8_t* __restrict__ verdict) {
+    __shared__ __attribute__((aligned(8))) uint8_t sponge[VBLOCK * ML_STATE];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    uint32_t* c = c_out + 8 * p;
+    if (status[p] != ST_OK) {
+        for (int l = 0; l < 8; ++l) c[l] = 0;
+        same[p] = 0;
+        return;
+    }
+    const uint32_t n_stmt = sh.n_com + 1, n_last = sh.n_resp - 2 * sh.n_com;
+    uint32_t* y = y_cmp + 8 * p * n_stmt;
+    for (uint32_t i = 0; i < sh.n_com; ++i) ml_compress_g1(committed + 16 * (p * sh.n_com + i), y + 8 * i);
+    ml_compress_g1(com_hidden + 16 * p, y + 8 * sh.n_com);
+    const uint32_t n_com = sh.n_com;
+    ml_dlog_shape_challenge(sponge + ML_STATE * threadIdx.x, context + p * context_stride, context_len, n_stmt,
+                            [=](uint32_t i) { return i < n_com ? 2u : n_last; }, bases_cmp, (const uint8_t*)(k_pts + 8 * p * n_stmt),
+                            (const uint8_t*)y, (uint8_t*)c);
+    uint32_t differ = 0;
+    for (int l = 0; l < 8; ++l) differ |= c[l] ^ pok_c[8 * p + l];
+    same[p] = differ == 0;
+    if (differ && verdict[p] == CG_VERIFY_ACCEPT) verdict[p] = CG_VERIFY_REJECT;
+}
+
+// One row of the link (show_link.hpp): false where the commitment fails ark's checked deserialisation or the shift is >= r
+__device__ __forceinline__ bool link_row(const uint32_t* __restrict__ commitment, const uint32_t* __restrict__ shift,
+                                         const G1Affine* __restrict__ tab_of_input, G1Affine& ped_com) {
+    bool ok = true;
+    const G1Affine c = dev_g1(commitment, ok);
+    ok = ok && link_below_r(shift);
+    if (ok) ped_com = to_affine(shift_commitment(tab_of_input, c, shift));
+    return ok;
+}
+// The verifying side: one lane per (range, showing), range-major so that a wave walks one table.  link: per range the
+// committed index, then per range the table.  ped_com goes out as 64 B ark-uncompressed rows, range j's m rows at j·m, where
+// the range key's kernels read them.  A malformed row is written with both flag bits set, which k_rv_check's checked
+// deserialisation refuses as it refuses any such row: that range part is CG_VERIFY_MALFORMED.
+__global__ __launch_bounds__(VBLOCK) void k_show_link(const uint32_t* __restrict__ committed, const uint32_t* __restrict__ shifts, uint64_t n,
+                                                     uint32_t n_com, uint32_t n_ranges, const uint32_t* __restrict__ link,
+                                                     const G1Affine* __restrict__ tab, uint32_t* __restrict__ ped_com) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * n_ranges) return;
+    const uint32_t j = (uint32_t)(g / n);
+    const uint64_t p = g % n;
+    uint32_t* out = ped_com + 16 * g;
+    G1Affine pc;
+    if (link_row(committed + 16 * (p * n_com + link[j]), shifts + 8 * (p * n_ranges + j), tab + (uint64_t)link[n_ranges + j] * FB_NWIN * FB_WIN, pc))
+        dev_put_g1(pc, out, false);
+    else
+        for (int l = 0; l < 16; ++l) out[l] = 0xFFFFFFFFu;
+}
+// The creating side (cg_show_shift_batch): one lane per opening of one input; m' = m - t, r as it is, c' = c - t·base
+__global__ __launch_bounds__(VBLOCK) void k_show_shift(const uint32_t* __restrict__ openings, const uint32_t* __restrict__ commitments,
+                                                      const uint32_t* __restrict__ shifts, uint64_t n, const G1Affine* __restrict__ tab_of_input,
+                                                      uint32_t* __restrict__ openings_out, uint32_t* __restrict__ ped_com, uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t *op = openings + 16 * p, *t = shifts + 8 * p;
+    G1Affine pc;
+    const bool ok = link_below_r(op) && link_below_r(op + 8) && link_row(commitments + 16 * p, t, tab_of_input, pc);
+    status[p] = ok ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+    if (!ok) {
+        for (int l = 0; l < 16; ++l) openings_out[16 * p + l] = ped_com[16 * p + l] = 0;
+        return;
+    }
+    shift_opening(op, t, openings_out + 16 * p);
+    for (int l = 0; l < 8; ++l) openings_out[16 * p + 8 + l] = op[8 + l];
+    dev_put_g1(pc, ped_com + 16 * p, false);
+}
+
+// The conjunction, one lane per showing: the Groth16 part, then the range parts (range j's m bytes at j·m) -> parts, row per
+// showing, and the showing's verdict: MALFORMED if any part is, ACCEPT if every part is, else REJECT
+__global__ __launch_bounds__(VBLOCK) void k_show_verdict(const uint8_t* __restrict__ groth, const uint8_t* __restrict__ range, uint64_t n,
+                                                        uint32_t n_ranges, uint8_t* __restrict__ parts, uint8_t* __restrict__ verdict) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    bool malformed = false, accept = true;
+    for (uint32_t j = 0; j <= n_ranges; ++j) {
+        const uint8_t v = j ? range[(j - 1) * n + p] : groth[p];
+        parts[p * (n_ranges + 1) + j] = v;
+        malformed = malformed || v == CG_VERIFY_MALFORMED;
+        accept = accept && v == CG_VERIFY_ACCEPT;
+    }
+    verdict[p] = malformed ? CG_VERIFY_MALFORMED : accept ? CG_VERIFY_ACCEPT : CG_VERIFY_REJECT;
+}
+
 // ---- creating showings (ClientState::show_groth16, groth16rand.rs:100-187) ---------------------------------------------
 // One call's layout.  A showing's G1 partials are [n_fix fixed-base terms | r1^-1·A | r2·A]; the fixed-base terms are the
 // n_resp secrets times their bases in the order dlog.rs:60-67 meets them (x_i·gamma_abc[i+1], r_i·delta_g1 per committed
@@ -469,15 +581,24 @@ struct cg_pvk : KeyHandle {
     hipStream_t st2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     RowBuf b_in_g2{1};
+    // whole showings (cg_verify_showings_batch, cg_show_shift_batch).  On the host the 64 bytes of gamma_abc_g1[1..] and of
+    // delta_g1 (the last one) as the key holds them: what a range key's slot must have registered, and what the DLogPoK's
+    // transcript absorbs once compressed.  On the device per call the compressed bases and the contexts, per showing the
+    // compressed y_i, c' and the byte c' == pok_c, per (showing, range) the shift and ped_com - read there by the range
+    // key's kernels, whose verdicts come back into b_rverd -, then the parts and the verdict.
+    std::vector<uint8_t> base_bytes;
+    bool overlap = true;                   // cg_pvk_set_showings_overlap
+    DevBuf<uint8_t> b_bases_cmp;
+    RowBuf b_ctx, b_ycmp, b_cprime{32}, b_same{1}, b_shift, b_link, b_rverd, b_parts, b_final{1};
+    hipEvent_t ev_link = nullptr, ev_ranges = nullptr;      // the range key's stream behind the link, ours behind its last kernel
     void open_second() {
         CG_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-        CG_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        CG_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+        for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_link, &ev_ranges}) CG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     ~cg_pvk() {                            // both streams are waited for before the buffers above are freed (key_handle.hpp)
         if (st2) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); }
         drain();
-        for (hipEvent_t e : {ev_fork, ev_join}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_fork, ev_join, ev_link, ev_ranges}) if (e) (void)hipEventDestroy(e);
     }
 
     // the stages both verifying entries share, on a chunk of m proofs already in b_proofs; all under the handle's lock
@@ -541,6 +662,9 @@ extern "C" int cg_pvk_load(cg_pvk** out, const uint8_t* pvk_bytes, uint64_t len,
         k->gamma_live = hk.gamma_live;
         k->delta_live = hk.delta_live;
         k->gamma_is_one = hk.vk.gamma_g2.x == g2_gen.x && hk.vk.gamma_g2.y == g2_gen.y;       // generator.rs:28
+        // the key starts with its VerifyingKey: alpha_g1 64 | beta_g2 128 | gamma_g2 128 | delta_g1 64 | delta_g2 128 | u64 | gamma_abc_g1
+        k->base_bytes.assign(pvk_bytes + 520 + 64, pvk_bytes + 520 + 64 * hk.vk.gamma_abc.size());
+        k->base_bytes.insert(k->base_bytes.end(), pvk_bytes + 320, pvk_bytes + 384);
         k->open(device);
         k->open_second();
         k->timer.create();
@@ -760,6 +884,192 @@ extern "C" int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
             if (pok) k->b_k.down(k->st, k_out, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
             k->timer.add();
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+extern "C" int cg_pvk_set_showings_overlap(cg_pvk* k, int32_t on) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (on != 0 && on != 1) return fail(CG_ERR_INVALID_ARGUMENT, "overlap is 0 or 1, not %d", on);
+    std::lock_guard<std::mutex> lk(k->mu);
+    k->overlap = on != 0;
+    return CG_OK;
+}
+
+// `verify_show`'s cryptographic checks (creds/src/lib.rs:630-658, :832-890) for a batch of showings of one layout: the
+// kernels of cg_verify_show_batch, k_show_challenge behind k_show_k, k_show_link into memory the range key's kernels read
+// (rangeverify.hpp's internal entry, on the range key's stream behind an event), k_show_verdict.  Per chunk nothing comes
+// down between the steps.  The locks are taken in the order cg_pvk, cg_range_vk.
+extern "C" int cg_verify_showings_batch(cg_pvk* k, cg_range_vk* rk, const uint8_t* io_types, uint64_t n_io, const uint8_t* context,
+                                        uint64_t context_len, uint64_t context_stride, const uint8_t* revealed, const uint8_t* rand_proofs,
+                                        const uint8_t* com_hidden, const uint8_t* committed, const uint8_t* pok_c, const uint8_t* pok_s,
+                                        uint32_t n_ranges, const cg_show_range_link* links, const uint8_t* shifts, const cg_range_rows* ranges,
+                                        uint64_t n, uint8_t* verdicts, uint8_t* part_verdicts) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    IoLayout L;
+    if (int rc = io_layout(k, io_types, n_io, L)) return rc;
+    if (n == 0) return CG_OK;
+    std::vector<uint32_t> desc;              // tab_of of k_show_terms, then k_show_link's: the committed index and the table per range
+    const ShowShape sh = show_shape(L, true, desc);
+    const uint32_t n_tab_of = (uint32_t)desc.size(), n_stmt = sh.n_com + 1;
+    if (!rand_proofs || !com_hidden || !verdicts || !pok_c || !pok_s || (sh.n_rev && !revealed) || (sh.n_com && !committed) ||
+        (context_len && !context) || (n_ranges && (!rk || !links || !shifts || !ranges)))
+        return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (context_stride && context_stride < context_len)
+        return fail(CG_ERR_INVALID_ARGUMENT, "a context stride of %llu is shorter than the context's %llu bytes", (unsigned long long)context_stride,
+                    (unsigned long long)context_len);
+    if (context_len > 0xffffffffull - 8) return fail(CG_ERR_INVALID_ARGUMENT, "a context of %llu bytes is longer than a Merlin message", (unsigned long long)context_len);
+    for (uint32_t j = 0; j < n_ranges; ++j) {
+        const cg_range_rows& r = ranges[j];
+        if (!r.com_f || !r.com_g || !r.com_q || !r.evals || !r.proofs || !r.randomizers || !r.pok_c || !r.pok_s)
+            return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+        if (links[j].committed_index >= sh.n_com)
+            return fail(CG_ERR_INVALID_ARGUMENT, "link %u: committed_index %u of %u committed inputs", j, links[j].committed_index, sh.n_com);
+    }
+    for (uint32_t j = 0; j < n_ranges; ++j) desc.push_back(links[j].committed_index);
+    for (uint32_t j = 0; j < n_ranges; ++j) desc.push_back(L.com[links[j].committed_index]);
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        std::unique_lock<std::mutex> lr;
+        if (n_ranges) {
+            lr = std::unique_lock<std::mutex>(range_vk_lock(rk));
+            if (range_vk_device(rk) != k->device)
+                return fail(CG_ERR_INVALID_ARGUMENT, "the Groth16 key is on device %d and the range key on device %d", k->device, range_vk_device(rk));
+        }
+        const uint8_t* delta = k->base_bytes.data() + 64 * n_io;
+        for (uint32_t j = 0; j < n_ranges; ++j) {
+            const uint8_t* reg = range_vk_slot_bytes(rk, links[j].slot);
+            if (!reg) return fail(CG_ERR_INVALID_ARGUMENT, "link %u: slot %u was not registered on the range key (cg_range_vk_add_bases)", j, links[j].slot);
+            const uint32_t input = L.com[links[j].committed_index];
+            if (memcmp(reg, k->base_bytes.data() + 64 * (uint64_t)input, 64) || memcmp(reg + 64, delta, 64))
+                return fail(CG_ERR_INVALID_ARGUMENT, "link %u: slot %u does not hold gamma_abc_g1[%u] and delta_g1 of this key", j, links[j].slot, input + 1);
+        }
+        // the bases as the transcript absorbs them, in the order the responses meet them
+        std::vector<uint32_t> bases_cmp(8 * (size_t)sh.n_resp);
+        for (uint32_t t = 0; t < sh.n_resp; ++t) {
+            uint32_t w[16];
+            memcpy(w, k->base_bytes.data() + 64 * (uint64_t)L.resp_tab[t], 64);
+            ml_compress_g1(w, bases_cmp.data() + 8 * t);
+        }
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
+        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict, &k->b_in_g2, &k->b_comh, &k->b_chal, &k->b_cprime, &k->b_same, &k->b_final})
+            b->reserve(chunk);
+        k->b_inputs.reserve(chunk, sh.n_rev * 32);
+        k->b_comm.reserve(chunk, sh.n_com * 64);
+        k->b_rows.reserve(chunk, sh.n_resp * 32);
+        k->b_k.reserve(chunk, n_stmt * 32);
+        k->b_ycmp.reserve(chunk, n_stmt * 32);
+        k->b_shift.reserve(chunk, n_ranges * 32);
+        k->b_link.reserve(chunk, n_ranges * 64);
+        k->b_rverd.reserve(chunk, n_ranges);
+        k->b_parts.reserve(chunk, n_ranges + 1);
+        if (context_stride) k->b_ctx.reserve(chunk, context_stride);
+        else k->b_ctx.reserve(1, context_len);
+        grow(k->b_parsed, chunk);
+        grow(k->b_miller, chunk);
+        grow(k->b_part, chunk * sh.n_terms + 1);
+        grow(k->b_desc, desc.size() + 1);
+        grow(k->b_bases_cmp, bases_cmp.size() * sizeof(uint32_t));
+        h2d_sync(k->b_desc.p, desc.data(), desc.size() * sizeof(uint32_t), k->st);
+        h2d_sync(k->b_bases_cmp.p, bases_cmp.data(), bases_cmp.size() * sizeof(uint32_t), k->st);
+        if (!context_stride) k->b_ctx.up(k->st, context, 0, 1);
+        if (n_ranges) range_vk_reserve(rk, chunk);
+        k->timer.reset();
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            k->proofs_up(rand_proofs, off, m);
+            k->b_comh.up(k->st, com_hidden, off, m);
+            k->b_inputs.up(k->st, revealed, off, m);
+            k->b_comm.up(k->st, committed, off, m);
+            k->b_chal.up(k->st, pok_c, off, m);
+            k->b_rows.up(k->st, pok_s, off, m);
+            k->b_shift.up(k->st, shifts, off, m);
+            if (context_stride && context_len)    // the caller's last context ends with its bytes, not with its stride
+                CG_HIP(hipMemcpyAsync(k->b_ctx.bytes(), context + off * context_stride, (m - 1) * context_stride + context_len,
+                                      hipMemcpyHostToDevice, k->st));
+            const uint32_t *d_rev = k->b_inputs.words(), *d_s = k->b_rows.words(), *d_c = k->b_chal.words(), *d_comh = k->b_comh.words(),
+                           *d_comm = k->b_comm.words();
+            const uint32_t grid = ceil_div(m, VBLOCK);
+            // the range half: every range on the range key's stream, behind the event recorded on ours
+            auto range_half = [&] {
+                if (!n_ranges) return;
+                CG_HIP(hipEventRecord(k->ev_link, k->st));
+                CG_HIP(hipStreamWaitEvent(range_vk_stream(rk), k->ev_link, 0));
+                for (uint32_t j = 0; j < n_ranges; ++j)
+                    range_vk_enqueue(rk, links[j].slot, ranges[j], off, m, k->b_link.words() + 16 * (uint64_t)j * m, k->b_rverd.bytes() + (uint64_t)j * m);
+                CG_HIP(hipEventRecord(k->ev_ranges, range_vk_stream(rk)));
+            };
+            if (n_ranges) {
+                k_show_link<<<ceil_div(m * n_ranges, VBLOCK), VBLOCK, 0, k->st>>>(d_comm, k->b_shift.words(), m, sh.n_com, n_ranges, k->b_desc.p + n_tab_of,
+                                                                                 k->tab.p, k->b_link.words_mut());
+                CG_KERNEL_CHECK();
+            }
+            if (k->overlap) range_half();
+            // the Groth16 half, as cg_verify_show_batch runs it
+            const uint32_t blocks = ceil_div(m * sh.n_fixed, VBLOCK) + ceil_div(m * sh.n_var, VBLOCK);
+            k_show_terms<<<blocks, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_desc.p, k->tab.p, k->b_part.p);
+            CG_KERNEL_CHECK();
+            k->check(m, d_rev, 0u);
+            k_show_check<<<grid, VBLOCK, 0, k->st>>>(d_rev, d_s, d_c, d_comh, d_comm, m, sh, k->b_part.p, k->g0, k->b_parsed.p, k->b_status.bytes());
+            CG_KERNEL_CHECK();
+            auto show_k = [&] {
+                k_show_k<<<ceil_div(m * n_stmt, VBLOCK), VBLOCK, 0, k->st>>>(m, sh, k->b_part.p, k->b_status.bytes(), k->b_k.words_mut());
+                CG_KERNEL_CHECK();
+            };
+            if (!k->latency) show_k();
+            k->pairing(m);
+            if (k->latency) show_k();             // the status is final only behind the pairing there (cg_verify_show_batch)
+            k_show_challenge<<<grid, VBLOCK, 0, k->st>>>(d_comh, d_comm, d_c, m, sh, k->b_bases_cmp.p, k->b_k.words(), k->b_ctx.bytes(), context_len,
+                                                        context_stride, k->b_status.bytes(), k->b_ycmp.words_mut(), k->b_cprime.words_mut(),
+                                                        k->b_same.bytes(), k->b_verdict.bytes());
+            CG_KERNEL_CHECK();
+            if (!k->overlap) range_half();
+            if (n_ranges) CG_HIP(hipStreamWaitEvent(k->st, k->ev_ranges, 0));
+            k_show_verdict<<<grid, VBLOCK, 0, k->st>>>(k->b_verdict.bytes(), k->b_rverd.bytes(), m, n_ranges, k->b_parts.bytes(), k->b_final.bytes());
+            CG_KERNEL_CHECK();
+            k->b_final.down(k->st, verdicts, off, m);
+            k->b_parts.down(k->st, part_verdicts, off, m);
+            CG_HIP(hipStreamSynchronize(k->st));
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+// The creating side's link (creds/src/lib.rs:370-372, :468-470, :505-507): k_show_shift over the table of one input
+extern "C" int cg_show_shift_batch(cg_pvk* k, uint32_t input_index, const uint8_t* openings, const uint8_t* commitments, const uint8_t* shifts,
+                                   uint64_t n, uint8_t* openings_out, uint8_t* ped_com_out, uint8_t* status) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (input_index >= k->n_inputs)
+        return fail(CG_ERR_INVALID_ARGUMENT, "input %u of a key with %llu public inputs", input_index, (unsigned long long)k->n_inputs);
+    if (n == 0) return CG_OK;
+    if (!openings || !commitments || !shifts || !openings_out || !ped_com_out || !status) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
+        for (RowBuf* b : {&k->b_comh, &k->b_chal, &k->b_status}) b->reserve(chunk);
+        k->b_rows.reserve(chunk, 64);
+        k->b_inputs.reserve(chunk, 64);
+        k->b_link.reserve(chunk, 64);
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            k->b_rows.up(k->st, openings, off, m);
+            k->b_comh.up(k->st, commitments, off, m);
+            k->b_chal.up(k->st, shifts, off, m);
+            k_show_shift<<<ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(k->b_rows.words(), k->b_comh.words(), k->b_chal.words(), m,
+                                                                   k->tab.p + (uint64_t)input_index * FB_NWIN * FB_WIN, k->b_inputs.words_mut(),
+                                                                   k->b_link.words_mut(), k->b_status.bytes());
+            CG_KERNEL_CHECK();
+            k->b_inputs.down(k->st, openings_out, off, m);
+            k->b_link.down(k->st, ped_com_out, off, m);
+            k->b_status.down(k->st, status, off, m);
+            CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
     } catch (...) {

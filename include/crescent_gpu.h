@@ -908,6 +908,79 @@ int cg_dlog_challenge_batch(const uint8_t* context, uint64_t context_len, uint64
                             const uint32_t* n_bases, const uint8_t* bases, const uint8_t* k, const uint8_t* y_head,
                             const uint8_t* y_last, uint64_t n, uint8_t* c_out);
 
+/* Verifying whole showings.  The reference's `verify_show` (creds/src/lib.rs:531-700; `verify_show_mdl`, :723-) is more
+ * than `ShowGroth16::verify` and `ShowRange::verify`: a range proof is checked against a committed input of the showing
+ * SHIFTED by a public value (lib.rs:645-646, :847-848, :868-876),
+ *     ped_com = show_groth16.commited_inputs[j] - gamma_abc_g1[pos] * t        (t = cur_time, or days_to_be_age(age)),
+ * and the showing is sound only if the range proof speaks about that point.  The two entries below compute the link on
+ * the GPU, on the verifying and on the creating side ("Verifying whole showings").
+ *
+ * One range proof of a showing: which committed input it is about, and the slot of `rk` registered for
+ * (gamma_abc_g1[pos], delta_g1) of that input - the vk's entry of the input, i.e. gamma_abc_g1[input index + 1]. */
+typedef struct cg_show_range_link {
+    uint32_t committed_index;  /* which committed input, counted in committed order (0 = first) */
+    uint32_t slot;             /* cg_range_vk_add_bases' slot for that input's bases */
+} cg_show_range_link;
+/* One range proof per showing, n rows each, in the layouts of cg_range_verify_proofs_batch. */
+typedef struct cg_range_rows {
+    const uint8_t *com_f, *com_g, *com_q, *evals, *proofs, *randomizers, *pok_c, *pok_s;
+} cg_range_rows;
+/* Replaces: the cryptographic checks of `verify_show` / `verify_show_mdl` for n showings of one layout in ONE call:
+ *           `ShowGroth16::verify` whole (lib.rs:630, :832; groth16rand.rs:232-306 with the DLogPoK's transcript and
+ *           `c == self.c`, dlog.rs:130-174), the link above per range proof (lib.rs:645-646, :847-848, :868-876) and
+ *           `ShowRange::verify` whole per range proof (lib.rs:650, :852, :881).  Per chunk of showings everything runs
+ *           on the device and nothing comes down between the steps: the kernels of cg_verify_show_batch; the DLogPoK's
+ *           Merlin transcript over the compressed bases, the recomputed k_i and y_i as their bytes stand, compared with
+ *           pok_c; ped_com per (showing, range) from the key's tables, written to device memory that the kernels of
+ *           cg_range_verify_proofs_batch then read on the range key's stream, ordered behind the link by an event.
+ * NOT done here (they are no curve arithmetic): the SHA-256 of revealed preimages (lib.rs:560-605), the freshness test on
+ * cur_time (:637-643) and the device proof (ECDSA / Spartan over T-256).
+ * io_types .. pok_s: as for cg_verify_show_batch; pok_c and pok_s are required.
+ * context: the DLogPoK's context string as cg_dlog_challenge_batch takes it: context_len bytes, context_stride = 0 for one
+ *          context shared by the batch, otherwise showing i's starts at context + i * context_stride; NULL with length 0 is
+ *          `None`.
+ * links:   n_ranges of them, shared by the batch.  shifts: n x n_ranges x 32 B canonical Fr, the t of each link.
+ * ranges:  n_ranges cg_range_rows of n rows each.  n_ranges = 0 is `ShowGroth16::verify` whole (rk may then be NULL).
+ * verdicts:      n x CG_VERIFY_*: MALFORMED if any part is MALFORMED, ACCEPT if every part is ACCEPT, else REJECT.
+ * part_verdicts: n x (1 + n_ranges), may be NULL: the Groth16 part first - ACCEPT only where the pairing accepts AND the
+ *          recomputed challenge equals pok_c, i.e. `ShowGroth16::verify == true` -, then each range part as
+ *          cg_range_verify_proofs_batch answers for the linked ped_com.  A shift >= r or a committed point that fails
+ *          the checked deserialisation makes that range part MALFORMED (the latter also the Groth16 part).  ped_com = O is
+ *          legal.  A bad showing leaves its neighbours untouched.
+ * Errors, all reported before any HIP call and with no output touched: a null array; n_io != cg_pvk_num_inputs
+ * (CG_ERR_MALFORMED_KEY); the two handles on different devices; a committed_index >= n_committed; an unknown slot; a slot
+ * whose registered 128 bytes are not byte for byte gamma_abc_g1[pos] ‖ delta_g1 of this key for the linked input; a
+ * context_stride shorter than context_len.  n = 0 is CG_OK.
+ * Locks: both handles' locks are held for the call, always taken in the order cg_pvk, then cg_range_vk.  The latency mode of
+ * each handle is honoured, with identical verdicts.  The two halves of a chunk run side by side on the two handles' streams
+ * (cg_pvk_set_showings_overlap), which takes about the longer half instead of the sum.  Measured on an MI355X at 26 inputs
+ * with one 32-bit range proof (profiles/showing_verify.md): 70 ms for 1024 whole showings and 84 ms for 16384, against 116
+ * and 133 ms for cg_verify_show_batch, cg_dlog_challenge_batch and cg_range_verify_proofs_batch in turn; a lone showing
+ * with both handles in latency mode 27 ms against 52 ms.  cg_pvk_last_kernel_ms and cg_range_vk_last_kernel_ms read zeros
+ * after this call. */
+int cg_verify_showings_batch(cg_pvk* k, cg_range_vk* rk, const uint8_t* io_types, uint64_t n_io, const uint8_t* context,
+                             uint64_t context_len, uint64_t context_stride, const uint8_t* revealed, const uint8_t* rand_proofs,
+                             const uint8_t* com_hidden, const uint8_t* committed, const uint8_t* pok_c, const uint8_t* pok_s,
+                             uint32_t n_ranges, const cg_show_range_link* links, const uint8_t* shifts, const cg_range_rows* ranges,
+                             uint64_t n, uint8_t* verdicts, uint8_t* part_verdicts);
+/* Diagnostic: how cg_verify_showings_batch orders the two halves of a chunk.  1 = the range half starts on the range key's
+ * stream as soon as the link is written, beside the Groth16 half; 0 = it starts when the Groth16 half has finished.  The
+ * bytes are the same either way (profiles/showing_verify.md has both timings).  A value other than 0 or 1, or a null handle,
+ * is CG_ERR_INVALID_ARGUMENT.  (No counterpart in the reference.) */
+int cg_pvk_set_showings_overlap(cg_pvk* k, int32_t on);
+/* Replaces: the creating side's link, `com.m -= t; com.c -= bases[0] * t` before `show_range` (lib.rs:370-372, :468-470,
+ *           :505-507), for n openings of the committed input `input_index` (an index into io_types; its base is
+ *           gamma_abc_g1[input_index + 1]).
+ * openings:    n x 2 x 32 B canonical Fr: m and r (dlog.rs:24-29);  commitments: n x 64 B ark-serialize uncompressed, the
+ *              committed point of each showing;  shifts: n x 32 B canonical Fr.
+ * openings_out: n x 2 x 32 B: m - t mod r (m < t wraps), and r unchanged;  ped_com_out: n x 64 B: c - t * base (O where
+ *              they cancel), both in the layouts cg_range_prove_batch takes.  m - t >= 2^n_bits stays that call's to refuse.
+ * status:      n x CG_SHOW_MADE / CG_SHOW_MALFORMED (that row only, its output rows zero bytes): m, r or t >= r, or a
+ *              commitment that fails ark's checked G1 deserialisation.
+ * input_index >= cg_pvk_num_inputs or a null array is CG_ERR_INVALID_ARGUMENT, reported before any HIP call; n = 0 is CG_OK. */
+int cg_show_shift_batch(cg_pvk* k, uint32_t input_index, const uint8_t* openings, const uint8_t* commitments, const uint8_t* shifts,
+                        uint64_t n, uint8_t* openings_out, uint8_t* ped_com_out, uint8_t* status);
+
 /* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
  * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the
  * PreparedVerifyingKey bytes (*len of them; pvk_out = NULL only reports *len).  A buffer shorter than *len is

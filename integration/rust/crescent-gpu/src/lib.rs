@@ -756,32 +756,8 @@ impl GpuVerifyingKey {
     /// absorb the bases, `k` and y exactly as dlog.rs:130-152 does, derive the challenge (:166-169) and compare it with
     /// `pok_inputs.c`; a showing is valid when that holds and `groth16_valid` is true ("Verifying showings").
     pub fn verify_show_batch(&self, io_types: &[u8], shows: &[ShowRef]) -> Result<Vec<ShowOutcome>, SynthesisError> {
-        let n_com = io_types.iter().filter(|t| **t == sys::CG_IO_COMMITTED).count();
-        let n_hid = io_types.iter().filter(|t| **t == sys::CG_IO_HIDDEN).count();
-        let n_rev = io_types.iter().filter(|t| **t == sys::CG_IO_REVEALED).count();
         let n = shows.len();
-        let (mut rev, mut proofs, mut comh, mut comm, mut c, mut s) = (Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new());
-        for sh in shows {
-            let shape_ok = sh.revealed.len() == n_rev
-                && sh.commited_inputs.len() == n_com
-                && sh.pok_s.len() == n_com + 1
-                && sh.pok_s.iter().take(n_com).all(|v| v.len() == 2)
-                && sh.pok_s[n_com].len() == n_hid + 1;
-            if !shape_ok {
-                return Err(SynthesisError::MalformedVerifyingKey);
-            }
-            rev.extend(canonical_bytes(sh.revealed));
-            // ark-serialize uncompressed, the layout cg_prove writes and cg_verify_show_batch reads
-            sh.rand_proof.serialize_uncompressed(&mut proofs).map_err(|_| SynthesisError::AssignmentMissing)?;
-            sh.com_hidden_inputs.serialize_uncompressed(&mut comh).map_err(|_| SynthesisError::AssignmentMissing)?;
-            for p in sh.commited_inputs {
-                p.serialize_uncompressed(&mut comm).map_err(|_| SynthesisError::AssignmentMissing)?;
-            }
-            c.extend(canonical_bytes(std::slice::from_ref(sh.pok_c)));
-            for si in sh.pok_s {
-                s.extend(canonical_bytes(si));
-            }
-        }
+        let ShowArrays { n_com, rev, proofs, comh, comm, c, s } = pack_shows(io_types, shows)?;
         let mut verdicts = vec![0u8; n];
         let mut k = vec![0u8; n * (n_com + 1) * 32];
         let rc = unsafe {
@@ -797,6 +773,142 @@ impl GpuVerifyingKey {
                 k: k[i * (n_com + 1) * 32..(i + 1) * (n_com + 1) * 32].chunks(32).map(|b| b.try_into().unwrap()).collect(),
             })
             .collect())
+    }
+}
+
+/// The flat arrays of the showing-verifying calls, one row per showing, in the layouts include/crescent_gpu.h states
+struct ShowArrays {
+    n_com: usize,
+    rev: Vec<u8>,
+    proofs: Vec<u8>,
+    comh: Vec<u8>,
+    comm: Vec<u8>,
+    c: Vec<u8>,
+    s: Vec<u8>,
+}
+
+fn pack_shows(io_types: &[u8], shows: &[ShowRef]) -> Result<ShowArrays, SynthesisError> {
+    let n_com = io_types.iter().filter(|t| **t == sys::CG_IO_COMMITTED).count();
+    let n_hid = io_types.iter().filter(|t| **t == sys::CG_IO_HIDDEN).count();
+    let n_rev = io_types.iter().filter(|t| **t == sys::CG_IO_REVEALED).count();
+    let (mut rev, mut proofs, mut comh, mut comm, mut c, mut s) = (Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new(), Vec::new());
+    for sh in shows {
+        let shape_ok = sh.revealed.len() == n_rev
+            && sh.commited_inputs.len() == n_com
+            && sh.pok_s.len() == n_com + 1
+            && sh.pok_s.iter().take(n_com).all(|v| v.len() == 2)
+            && sh.pok_s[n_com].len() == n_hid + 1;
+        if !shape_ok {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        rev.extend(canonical_bytes(sh.revealed));
+        // ark-serialize uncompressed, the layout cg_prove writes and cg_verify_show_batch reads
+        sh.rand_proof.serialize_uncompressed(&mut proofs).map_err(|_| SynthesisError::AssignmentMissing)?;
+        sh.com_hidden_inputs.serialize_uncompressed(&mut comh).map_err(|_| SynthesisError::AssignmentMissing)?;
+        for p in sh.commited_inputs {
+            p.serialize_uncompressed(&mut comm).map_err(|_| SynthesisError::AssignmentMissing)?;
+        }
+        c.extend(canonical_bytes(std::slice::from_ref(sh.pok_c)));
+        for si in sh.pok_s {
+            s.extend(canonical_bytes(si));
+        }
+    }
+    Ok(ShowArrays { n_com, rev, proofs, comh, comm, c, s })
+}
+
+/// One range proof of every showing for `GpuVerifyingKey::verify_showings_batch`: the committed input it is about (counted
+/// in committed order), the range key's slot registered for (gamma_abc_g1[pos], delta_g1) of that input, the public value
+/// t of each showing (cur_time, or days_to_be_age(age)) and the proofs' rows; `rows.ped_com`, `rows.c` and `rows.rho` are
+/// not read: ped_com = commited_inputs[committed_index] - gamma_abc_g1[pos] * t is formed on the GPU.
+pub struct ShowRangeLink<'a> {
+    pub committed_index: u32,
+    pub slot: u32,
+    pub shifts: &'a [Fr],
+    pub rows: &'a RangeProofRows<'a>,
+}
+
+impl GpuVerifyingKey {
+    /// The cryptographic checks of `verify_show` / `verify_show_mdl` (creds/src/lib.rs:630-658, :832-890) in one call
+    /// (`cg_verify_showings_batch`): `ShowGroth16::verify` whole, its Merlin transcript over `context` included, the link
+    /// and `ShowRange::verify` per range proof.  Returns per showing its 1 + links.len() part verdicts (CG_VERIFY_*), the
+    /// Groth16 part first; a showing is valid when all of them are CG_VERIFY_ACCEPT.  Not covered: the SHA-256 of revealed
+    /// preimages, the freshness test on cur_time and the device proof ("Verifying whole showings").
+    pub fn verify_showings_batch(&self, range_key: Option<&GpuRangeVerifyingKey>, io_types: &[u8], context: Option<&[u8]>, shows: &[ShowRef],
+                                 links: &[ShowRangeLink]) -> Result<Vec<Vec<u8>>, SynthesisError> {
+        let n = shows.len();
+        let a = pack_shows(io_types, shows)?;
+        if !links.is_empty() && range_key.is_none() {
+            return Err(SynthesisError::AssignmentMissing);
+        }
+        let mut shifts = vec![0u8; n * links.len() * 32];
+        let (mut c_links, mut c_rows, mut keep) = (Vec::new(), Vec::new(), Vec::new());
+        for (j, l) in links.iter().enumerate() {
+            let r = l.rows;
+            if l.shifts.len() != n || r.com_f.len() != n * 64 || r.com_g.len() != n * 64 || r.com_q.len() != n * 64 || r.evals.len() != n * 96
+                || r.proofs.len() != n * 288 || r.randomizers.len() != 2 * n || r.pok_c.len() != n || r.pok_s.len() != n * sys::CG_RANGE_N_RESP
+            {
+                return Err(SynthesisError::MalformedVerifyingKey);
+            }
+            for (i, t) in canonical_bytes(l.shifts).chunks(32).enumerate() {
+                shifts[(i * links.len() + j) * 32..(i * links.len() + j + 1) * 32].copy_from_slice(t);
+            }
+            let zb: Vec<u8> = r.randomizers.iter().flat_map(|z| z.to_le_bytes()).collect();
+            keep.push((zb, canonical_bytes(r.pok_c), canonical_bytes(r.pok_s)));
+            c_links.push(sys::cg_show_range_link { committed_index: l.committed_index, slot: l.slot });
+        }
+        for (l, (zb, pc, ps)) in links.iter().zip(keep.iter()) {
+            let r = l.rows;
+            c_rows.push(sys::cg_range_rows { com_f: r.com_f.as_ptr(), com_g: r.com_g.as_ptr(), com_q: r.com_q.as_ptr(), evals: r.evals.as_ptr(),
+                                             proofs: r.proofs.as_ptr(), randomizers: zb.as_ptr(), pok_c: pc.as_ptr(), pok_s: ps.as_ptr() });
+        }
+        let ctx = context.unwrap_or(&[]);
+        let width = 1 + links.len();
+        let (mut verdicts, mut parts) = (vec![0u8; n], vec![0u8; n * width]);
+        let rc = unsafe {
+            sys::cg_verify_showings_batch(self.h, range_key.map_or(std::ptr::null_mut(), |k| k.h), io_types.as_ptr(), io_types.len() as u64,
+                                          if ctx.is_empty() { std::ptr::null() } else { ctx.as_ptr() }, ctx.len() as u64, 0, a.rev.as_ptr(),
+                                          a.proofs.as_ptr(), a.comh.as_ptr(), a.comm.as_ptr(), a.c.as_ptr(), a.s.as_ptr(), links.len() as u32,
+                                          c_links.as_ptr(), shifts.as_ptr(), c_rows.as_ptr(), n as u64, verdicts.as_mut_ptr(), parts.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(parts.chunks(width).map(|p| p.to_vec()).collect())
+    }
+
+    /// The creating side's link, `com.m -= t; com.c -= bases[0] * t` before `show_range` (creds/src/lib.rs:370-372, :468-470,
+    /// :505-507), for n openings (m, r) of the committed input `input_index` (`cg_show_shift_batch`).  Returns (openings n x
+    /// 2 x 32 B, ped_com n x 64 B, status n x CG_SHOW_*) in the layouts `GpuRangeKey::prove_batch` takes.
+    pub fn show_shift_batch(&self, input_index: u32, openings: &[(Fr, Fr)], commitments: &[G1Affine], shifts: &[Fr]) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = openings.len();
+        if commitments.len() != n || shifts.len() != n {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let flat: Vec<Fr> = openings.iter().flat_map(|(m, r)| [*m, *r]).collect();
+        let (ob, sb) = (canonical_bytes(&flat), canonical_bytes(shifts));
+        let mut cb = Vec::with_capacity(n * 64);
+        for p in commitments {
+            p.serialize_uncompressed(&mut cb).map_err(|_| SynthesisError::AssignmentMissing)?;
+        }
+        let (mut out, mut ped, mut status) = (vec![0u8; n * 64], vec![0u8; n * 64], vec![0u8; n]);
+        let rc = unsafe {
+            sys::cg_show_shift_batch(self.h, input_index, ob.as_ptr(), cb.as_ptr(), sb.as_ptr(), n as u64, out.as_mut_ptr(), ped.as_mut_ptr(),
+                                     status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((out, ped, status))
+    }
+
+    /// Diagnostic (`cg_pvk_set_showings_overlap`): whether `verify_showings_batch` starts the range half beside the Groth16
+    /// half (the default) or behind it
+    pub fn set_showings_overlap(&self, on: bool) -> Result<(), SynthesisError> {
+        let rc = unsafe { sys::cg_pvk_set_showings_overlap(self.h, on as i32) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(())
     }
 }
 

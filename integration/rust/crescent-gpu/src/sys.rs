@@ -156,6 +156,28 @@ pub struct cg_witness_report {
     pub reserved: [i32; 7],
 }
 
+/// one range proof of a showing for `cg_verify_showings_batch`: which committed input, and the range key's slot for its bases
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct cg_show_range_link {
+    pub committed_index: u32,
+    pub slot: u32,
+}
+
+/// one range proof per showing, n rows each, in the layouts of `cg_range_verify_proofs_batch`
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct cg_range_rows {
+    pub com_f: *const u8,
+    pub com_g: *const u8,
+    pub com_q: *const u8,
+    pub evals: *const u8,
+    pub proofs: *const u8,
+    pub randomizers: *const u8,
+    pub pok_c: *const u8,
+    pub pok_s: *const u8,
+}
+
 pub enum cg_ctx {}
 pub enum cg_partial {}
 pub enum cg_msm_ctx {}
@@ -507,5 +529,39 @@ extern "C" {
         y_last: *const u8,
         n: u64,
         c_out: *mut u8,
+    ) -> c_int;
+    pub fn cg_verify_showings_batch(
+        k: *mut cg_pvk,
+        rk: *mut cg_range_vk,
+        io_types: *const u8,
+        n_io: u64,
+        context: *const u8,
+        context_len: u64,
+        context_stride: u64,
+        revealed: *const u8,
+        rand_proofs: *const u8,
+        com_hidden: *const u8,
+        committed: *const u8,
+        pok_c: *const u8,
+        pok_s: *const u8,
+        n_ranges: u32,
+        links: *const cg_show_range_link,
+        shifts: *const u8,
+        ranges: *const cg_range_rows,
+        n: u64,
+        verdicts: *mut u8,
+        part_verdicts: *mut u8,
+    ) -> c_int;
+    pub fn cg_pvk_set_showings_overlap(k: *mut cg_pvk, on: i32) -> c_int;
+    pub fn cg_show_shift_batch(
+        k: *mut cg_pvk,
+        input_index: u32,
+        openings: *const u8,
+        commitments: *const u8,
+        shifts: *const u8,
+        n: u64,
+        openings_out: *mut u8,
+        ped_com_out: *mut u8,
+        status: *mut u8,
     ) -> c_int;
 }
