@@ -169,6 +169,10 @@ class _CgRangeRows(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in ("com_f", "com_g", "com_q", "evals", "proofs", "randomizers", "pok_c", "pok_s")]
 
 
+class _CgRangeMade(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("com_f", "com_g", "com_q", "evals", "proofs", "pok_c", "pok_s", "challenges")]
+
+
 class _CgR1csHeader(C.Structure):
     _fields_ = [("field_size", C.c_uint32), ("n_wires", C.c_uint32), ("n_pub_out", C.c_uint32),
                 ("n_pub_in", C.c_uint32), ("n_prv_in", C.c_uint32), ("n_constraints", C.c_uint32),
@@ -284,6 +288,9 @@ _SIGNATURES = {
     "cg_verify_showings_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6
                                  + [C.c_uint32, C.POINTER(_CgShowRangeLink), C.c_void_p, C.POINTER(_CgRangeRows), C.c_uint64, C.c_void_p, C.c_void_p]),
     "cg_pvk_set_showings_overlap": (C.c_int, [C.c_void_p, C.c_int32]),
+    "cg_create_showings_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 3
+                                 + [C.c_uint32, C.POINTER(_CgShowRangeLink), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
+                                 + [C.POINTER(_CgRangeMade), C.c_void_p, C.c_void_p]),
     "cg_show_shift_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
@@ -1677,6 +1684,97 @@ class Groth16:
         return [bool(v == CG_VERIFY_ACCEPT) for v in verdicts]
 
     @staticmethod
+    def create_showings_batch_packed(pvk: "PreparedVerifyingKey", range_key, io_types, proofs, inputs, rand, links, shifts, range_rand,
+                                     context=None, context_len: Optional[int] = None, context_stride: int = 0):
+        """cg_create_showings_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = proofs / 256):
+        `create_show_proof`'s curve arithmetic and transcripts (creds/src/lib.rs:364-373, :468-471, :505-509) in one call.
+        proofs, inputs, rand: as show_commit_batch_packed takes them; links: one (committed_index, slot of range_key) per
+        range proof of a showing; shifts: n x n_ranges x 32 B; range_rand: n x n_ranges x 18 x 32 B; context: as
+        dlog_challenge_batch takes it.  range_key may be None without links.  Returns (rand_proofs n x 256, com_hidden n x
+        64, committed n x n_committed x 64, pok_c n x 32, pok_s n x n_resp x 32, ranges: per link the tuple (com_f, com_g,
+        com_q, evals, proofs, pok_c, pok_s, challenges) as range_prove_batch_packed returns them, status n, part_status n x
+        (1 + n_ranges)) as uint8 arrays; a part that was not made has zero bytes in its rows."""
+        io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+        n_com = int((io == CG_IO_COMMITTED).sum())
+        pb = _u8(proofs)
+        if pb.size % 256:
+            raise ValueError("proofs must be n x 256 bytes")
+        n = pb.size // 256
+        links = list(links)
+        n_ranges = len(links)
+        n_rand = show_rand_count(io)
+        n_resp = n_rand - 3 - n_com
+        ib, rb = _u8(inputs, 32 * io.size * n), _u8(rand, 32 * n_rand * n)
+        sb, rrb = _u8(shifts, 32 * n_ranges * n), _u8(range_rand, 32 * CG_RANGE_N_RAND * n_ranges * n)
+        cb = _u8(context if context is not None else b"")
+        if context_len is None:
+            context_len = context_stride if context_stride else cb.size
+        if cb.size < (context_stride * (n - 1) + context_len if context_stride and n else context_len):
+            raise ValueError("context is shorter than its length and stride say")
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        rp, comh, comm = np.zeros((m, 256), np.uint8), np.zeros((m, 64), np.uint8), np.zeros((m, max(n_com, 1), 64), np.uint8)
+        pok_c, pok_s = np.zeros((m, 32), np.uint8), np.zeros((m, n_resp, 32), np.uint8)
+        status, parts = np.zeros(m, np.uint8), np.zeros((m, 1 + n_ranges), np.uint8)
+        shapes = ((64,), (64,), (64,), (3, 32), (3, 96), (32,), (CG_RANGE_N_RESP, 32), (3, 32))
+        made = [[np.zeros((m,) + sh, np.uint8) for sh in shapes] for _ in links]
+        c_links = (_CgShowRangeLink * max(n_ranges, 1))(*[_CgShowRangeLink(int(ci), int(slot)) for ci, slot in links])
+        c_made = (_CgRangeMade * max(n_ranges, 1))(*[_CgRangeMade(*[_ptr(a) for a in rows]) for rows in made])
+        _check(lib().cg_create_showings_batch(pvk._h, None if range_key is None else range_key._h, ptr(io), io.size, ptr(cb), context_len,
+                                              context_stride, ptr(pb), ptr(ib), ptr(rb), n_ranges, c_links if n_ranges else None, ptr(sb),
+                                              ptr(rrb), n, _ptr(rp), _ptr(comh), _ptr(comm), _ptr(pok_c), _ptr(pok_s),
+                                              c_made if n_ranges else None, _ptr(status), _ptr(parts)))
+        return (rp[:n], comh[:n], comm[:n, :n_com], pok_c[:n], pok_s[:n], [tuple(a[:n] for a in rows) for rows in made], status[:n],
+                parts[:n])
+
+    @staticmethod
+    def create_showings_batch(pvk: "PreparedVerifyingKey", range_key, io_types, states, links, shifts, rand=None, range_rand=None,
+                              context=None):
+        """`create_show_proof` / `create_show_proof_mdl`'s `show_groth16` and `show_range` steps (creds/src/lib.rs:364-373,
+        :468-471, :505-509) for n client states of one layout in one call (cg_create_showings_batch), the transcripts the
+        library's Merlin on the GPU.  states: a sequence of (proof bytes or Proof, inputs); links: (committed_index, slot of
+        range_key) per range proof of a showing; shifts[i][j]: the public value t of state i's link j (ints); rand: per
+        state its show_rand_count scalars in the header's order and range_rand[i][j]: the 18 scalars of link j (ints) -
+        None draws either with `secrets.randbelow` (r1, r2 non-zero), but a host that keeps the openings (the r_i and z) draws
+        them itself and passes them in; context: bytes, or None as the reference's `None`.  Returns per state
+        (ShowGroth16, [RangeProof per link]), or None for a state any part of which was not made."""
+        io = [int(t) for t in io_types]
+        n, links = len(states), list(links)
+        if n == 0:
+            return []
+        if len(shifts) != n or any(len(row) != len(links) for row in shifts):
+            raise ValueError("one shift per state and link")
+        import secrets
+        if rand is None:
+            n_rand = show_rand_count(io)
+            rand = [[1 + secrets.randbelow(FR_MODULUS - 1) for _ in range(2)] + [secrets.randbelow(FR_MODULUS) for _ in range(n_rand - 2)]
+                    for _ in range(n)]
+        if range_rand is None:
+            range_rand = [[[secrets.randbelow(FR_MODULUS) for _ in range(CG_RANGE_N_RAND)] for _ in links] for _ in range(n)]
+        n_com, n_hid = io.count(CG_IO_COMMITTED), io.count(CG_IO_HIDDEN)
+        fr = lambda v: int(v).to_bytes(32, "little")
+        rp, comh, comm, pok_c, s, ranges, status, _ = Groth16.create_showings_batch_packed(
+            pvk, range_key, io, b"".join(p.data if isinstance(p, Proof) else bytes(p) for p, _ in states),
+            np.concatenate([_inputs_array(x) for _, x in states]), _u8(b"".join(fr(v) for row in rand for v in row)), links,
+            _u8(b"".join(fr(t) for row in shifts for t in row)), _u8(b"".join(fr(v) for row in range_rand for link in row for v in link)), context)
+        val = lambda a: int.from_bytes(a.tobytes(), "little")
+        out = []
+        for i in range(n):
+            if status[i] != CG_SHOW_MADE:
+                out.append(None)
+                continue
+            flat = [val(s[i, j]) for j in range(s.shape[1])]
+            pok_s = [flat[2 * j:2 * j + 2] for j in range(n_com)] + [flat[2 * n_com:]]
+            assert len(pok_s[-1]) == n_hid + 1
+            show = ShowGroth16(rp[i].tobytes(), comh[i].tobytes(), val(pok_c[i]), pok_s, [comm[i, j].tobytes() for j in range(n_com)])
+            proofs = [RangeProof(com_f[i].tobytes(), com_g[i].tobytes(), val(evals[i, 0]), pr[i, 0].tobytes(), val(evals[i, 1]), pr[i, 1].tobytes(),
+                                 com_q[i].tobytes(), val(evals[i, 2]), pr[i, 2].tobytes(), val(rc[i]),
+                                 [[val(rs[i, j]) for j in range(2)], [val(rs[i, j]) for j in range(2, 6)]])
+                      for com_f, com_g, com_q, evals, pr, rc, rs, _ in ranges]
+            out.append((show, proofs))
+        return out
+
+    @staticmethod
     def show_shift_batch(pvk: "PreparedVerifyingKey", input_index: int, openings, commitments, shifts):
         """cg_show_shift_batch: the creating side's link `com.m -= t; com.c -= bases[0] * t` (creds/src/lib.rs:370-372,
         :468-470, :505-507) for n openings of the committed input `input_index` (an index into io_types).  openings: n x 64
@@ -1768,8 +1866,8 @@ class PreparedVerifyingKey(_LatencyMode, _Handle):
             self.set_latency(True)
 
     def set_showings_overlap(self, on: bool) -> None:
-        """cg_pvk_set_showings_overlap: whether verify_showings_batch starts the range half beside the Groth16 half (the
-        default) or behind it; the bytes are the same"""
+        """cg_pvk_set_showings_overlap: whether verify_showings_batch and create_showings_batch start the range half beside
+        the Groth16 half (the default) or behind it; the bytes are the same"""
         _check(lib().cg_pvk_set_showings_overlap(self._h, 1 if on else 0))
 
     def last_kernel_ms(self) -> Tuple[float, float]:

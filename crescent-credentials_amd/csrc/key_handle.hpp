@@ -7,6 +7,7 @@
 #include "ark_codec.hpp"
 #include "fixed_base.hpp"
 #include "merlin.hpp"
+#include "show_make.hpp"
 
 namespace cg {
 namespace {
@@ -156,7 +157,7 @@ struct RowBuf {
     uint8_t* bytes() { return d.p; }                               // a status, flag or verdict byte per item
 };
 
-// DLogPoK::prove's responses (dlog.rs:101-109), s = nonce - c·secret, for n showings of n_resp responses each:
+// DLogPoK::prove's responses (dlog.rs:101-109), s = nonce - c·secret (show_make.hpp's row), for n showings of n_resp responses each:
 // secret(p, t) and nonce(p, t) point at the 32 bytes of showing p's t-th pair, `what` names the secrets' source in the
 // message.  Every value is checked first, so an error writes nothing; a showing whose status is not CG_SHOW_MADE gets zeros.
 template <class Secret, class Nonce>
@@ -174,9 +175,15 @@ int dlog_respond(uint64_t n, uint32_t n_resp, const uint8_t* status, const uint8
             memset(s, 0, 32 * (size_t)n_resp);
             continue;
         }
-        const Fr cm = to_mont(fp_from_bytes<Fr>(c + 32 * p));               // c·R times a canonical x is c·x, canonical
-        for (uint32_t t = 0; t < n_resp; ++t)
-            fp_to_bytes(sub(fp_from_bytes<Fr>(nonce(p, t)), mul(cm, fp_from_bytes<Fr>(secret(p, t)))), s + 32 * t);
+        uint32_t w[3][8];                                                   // c, then per row the secret and the nonce; the row is s
+        memcpy(w[0], c + 32 * p, 32);
+        const Fr cm = mk_challenge_mont(w[0]);
+        for (uint32_t t = 0; t < n_resp; ++t) {                             // show_make.hpp: the row k_mk_respond computes
+            memcpy(w[1], secret(p, t), 32);
+            memcpy(w[2], nonce(p, t), 32);
+            mk_response_row(cm, w[1], w[2], w[0]);
+            memcpy(s + 32 * t, w[0], 32);
+        }
     }
     return CG_OK;
 }

@@ -21,7 +21,8 @@
 //   open      W of proof_g, proof_gw, proof_w^   4n + 15 terms (KZG10::open, kzg10/mod.rs:247-331)
 // cg_range_respond_batch, the DLEQ's responses once the host's transcript has produced its challenge, is host arithmetic.
 // cg_range_prove_batch is the three phases in one call with the transcripts on the device (merlin.hpp): the same kernels,
-// k_range_challenge_c and k_range_challenge_rho between them and k_range_finish (the responses) behind them.
+// k_range_challenge_c and k_range_challenge_rho between them and k_range_finish (the responses) behind them.  Its chunk
+// body is also rangeproof.hpp's internal entry, which cg_create_showings_batch (verify.hip) puts behind its own kernels.
 // The handle's device, stream and lock, the timing of the two stages, the slots and the per-call arrays are key_handle.hpp's
 // (KeyHandle, StageTimer, PedersenSlots, RowBuf), shared with cg_pvk and cg_range_vk; so are the responses (dlog_respond).
 #include <memory>
@@ -30,6 +31,7 @@
 #include "fixed_base.hpp"
 #include "key_handle.hpp"
 #include "rangepoly.hpp"
+#include "rangeproof.hpp"
 
 using namespace cg;
 
@@ -418,74 +420,93 @@ extern "C" int cg_range_respond_batch(const uint8_t* openings, const uint8_t* ra
 // challenge rho, open, the responses - and the proof comes down once; the host waits once, for that copy.  The phases'
 // kernels are the three calls' own, so the two paths give the same bytes.  The two stages are not timed apart here:
 // cg_range_pk_last_kernel_ms reads zeros after this call.
+//
+// One body for the public call and for rangeproof.hpp's internal entry: rp_reserve, then per piece of at most RCHUNK
+// showings rp_piece, which reads the openings and ped_com from device memory - the public call's own uploads, or what
+// k_mk_shift of cg_create_showings_batch wrote - and waits for nothing.
+namespace {
+void rp_reserve(cg_range_pk* k, uint64_t chunk) {
+    for (RowBuf* b : {&k->b_open, &k->b_rand, &k->b_c, &k->b_rho, &k->b_status, &k->o_ped, &k->o_pedc, &k->o_comf, &k->o_comg, &k->o_ts,
+                      &k->o_comq, &k->o_tsq, &k->o_evals, &k->o_proofs, &k->o_pokc, &k->o_poks, &k->o_chal})
+        b->reserve(chunk);
+    const uint32_t max_terms = k->shape[PH_OPEN].n_terms;                  // the most of the three phases
+    k->b_terms.reserve(chunk, 32 * max_terms);
+    grow(k->b_part, chunk * max_terms);
+    k->timer.reset();
+}
+
+void rp_piece(cg_range_pk* k, uint32_t slot, const uint32_t* d_open, const uint32_t* d_ped, const uint8_t* rand, uint64_t rand_pitch,
+              const RangePkOut& out, uint64_t off, uint64_t m, uint8_t* d_status_out) {
+    const G1Affine* tab_slot = k->slots.table(slot, "cg_range_pk_add_bases");
+    const uint8_t* slot_cmp = k->slots.compressed(slot);
+    if (rand_pitch == k->b_rand.row) k->b_rand.up(k->st, rand, 0, m);
+    else CG_HIP(hipMemcpy2DAsync(k->b_rand.bytes(), k->b_rand.row, rand, rand_pitch, k->b_rand.row, m, hipMemcpyHostToDevice, k->st));
+    const uint32_t* d_rand = k->b_rand.words();
+    uint32_t *d_c = k->b_c.words_mut(), *d_rho = k->b_rho.words_mut(), *d_terms = k->b_terms.words_mut();
+    uint32_t *d_ev = k->o_evals.words_mut(), *d_pr = k->o_proofs.words_mut();
+    uint8_t* d_status = k->b_status.bytes();
+    const uint32_t lanes = ceil_div(m, RWAVE);
+    auto points = [&](int ph, uint32_t* unc0, uint32_t* unc1, uint32_t* cmp) {
+        const RpShape& sh = k->shape[ph];
+        k_range_terms<<<ceil_div(m * sh.n_terms, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + ph, k->d_tab_of[ph].p, d_terms, k->tab.p, tab_slot,
+                                                                             d_status, m, k->b_part.p);
+        CG_KERNEL_CHECK();
+        k_range_sum<<<ceil_div(m * sh.n_pts, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + ph, d_status, m, k->b_part.p, unc0, unc1, cmp);
+        CG_KERNEL_CHECK();
+    };
+    k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_COMMIT].n_terms, d_terms, d_ev,
+                                                              d_pr, d_status, 0);
+    CG_KERNEL_CHECK();
+    points(PH_COMMIT, k->o_comf.words_mut(), k->o_comg.words_mut(), k->o_ts.words_mut());
+    k_range_challenge_c<<<lanes, RWAVE, 0, k->st>>>(k->o_ts.words(), d_ped, slot_cmp, k->key_cmp.p, d_status, m, k->o_pedc.words_mut(), d_c,
+                                                   k->o_pokc.words_mut());
+    CG_KERNEL_CHECK();
+    k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_QUOTIENT].n_terms, d_terms,
+                                                                d_ev, d_pr, d_status, 1);
+    CG_KERNEL_CHECK();
+    points(PH_QUOTIENT, k->o_comq.words_mut(), nullptr, k->o_tsq.words_mut());
+    k_range_challenge_rho<<<lanes, RWAVE, 0, k->st>>>(k->o_ts.words(), k->o_tsq.words(), d_status, m, d_rho);
+    CG_KERNEL_CHECK();
+    k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_OPEN].n_terms, d_terms, d_ev, d_pr,
+                                                            d_status, 1);
+    CG_KERNEL_CHECK();
+    points(PH_OPEN, d_pr, nullptr, nullptr);
+    const RpProof o{k->o_comf.words_mut(), k->o_comg.words_mut(), k->o_comq.words_mut(), d_ev, d_pr, k->o_pokc.words_mut(),
+                    k->o_poks.words_mut(), k->o_chal.words_mut()};
+    k_range_finish<<<lanes, RWAVE, 0, k->st>>>(d_open, d_rand, d_ped, d_c, d_rho, m, o, d_status);
+    CG_KERNEL_CHECK();
+    k->o_comf.down(k->st, out.com_f, off, m);
+    k->o_comg.down(k->st, out.com_g, off, m);
+    k->o_comq.down(k->st, out.com_q, off, m);
+    k->o_evals.down(k->st, out.evals, off, m);
+    k->o_proofs.down(k->st, out.proofs, off, m);
+    k->o_pokc.down(k->st, out.pok_c, off, m);
+    k->o_poks.down(k->st, out.pok_s, off, m);
+    k->o_chal.down(k->st, out.challenges, off, m);
+    k->b_status.down(k->st, out.status, off, m);
+    if (d_status_out) CG_HIP(hipMemcpyAsync(d_status_out, d_status, m, hipMemcpyDeviceToDevice, k->st));
+}
+}  // namespace
+
 extern "C" int cg_range_prove_batch(cg_range_pk* k, uint32_t slot, const uint8_t* openings, const uint8_t* ped_com, const uint8_t* rand,
                                     uint64_t n, uint8_t* com_f, uint8_t* com_g, uint8_t* com_q, uint8_t* evals, uint8_t* proofs,
                                     uint8_t* pok_c, uint8_t* pok_s, uint8_t* challenges_out, uint8_t* status) {
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     try {
         std::lock_guard<std::mutex> lk(k->mu);
-        const G1Affine* tab_slot = k->slots.table(slot, "cg_range_pk_add_bases");
+        (void)k->slots.table(slot, "cg_range_pk_add_bases");
         if (n == 0) return CG_OK;
         if (!openings || !ped_com || !rand || !com_f || !com_g || !com_q || !evals || !proofs || !pok_c || !pok_s || !status)
             return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < RCHUNK ? n : RCHUNK;
-        for (RowBuf* b : {&k->b_open, &k->b_rand, &k->b_c, &k->b_rho, &k->b_status, &k->o_ped, &k->o_pedc, &k->o_comf, &k->o_comg, &k->o_ts,
-                          &k->o_comq, &k->o_tsq, &k->o_evals, &k->o_proofs, &k->o_pokc, &k->o_poks, &k->o_chal})
-            b->reserve(chunk);
-        const uint32_t max_terms = k->shape[PH_OPEN].n_terms;                  // the most of the three phases
-        k->b_terms.reserve(chunk, 32 * max_terms);
-        grow(k->b_part, chunk * max_terms);
-        k->timer.reset();
-        const uint8_t* slot_cmp = k->slots.compressed(slot);
+        rp_reserve(k, chunk);
+        const RangePkOut out{com_f, com_g, com_q, evals, proofs, pok_c, pok_s, challenges_out, status};
         for (uint64_t off = 0; off < n; off += chunk) {
             const uint64_t m = n - off < chunk ? n - off : chunk;
             k->b_open.up(k->st, openings, off, m);
-            k->b_rand.up(k->st, rand, off, m);
             k->o_ped.up(k->st, ped_com, off, m);
-            const uint32_t *d_open = k->b_open.words(), *d_rand = k->b_rand.words(), *d_ped = k->o_ped.words();
-            uint32_t *d_c = k->b_c.words_mut(), *d_rho = k->b_rho.words_mut(), *d_terms = k->b_terms.words_mut();
-            uint32_t *d_ev = k->o_evals.words_mut(), *d_pr = k->o_proofs.words_mut();
-            uint8_t* d_status = k->b_status.bytes();
-            const uint32_t lanes = ceil_div(m, RWAVE);
-            auto points = [&](int ph, uint32_t* unc0, uint32_t* unc1, uint32_t* cmp) {
-                const RpShape& sh = k->shape[ph];
-                k_range_terms<<<ceil_div(m * sh.n_terms, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + ph, k->d_tab_of[ph].p, d_terms, k->tab.p, tab_slot,
-                                                                                     d_status, m, k->b_part.p);
-                CG_KERNEL_CHECK();
-                k_range_sum<<<ceil_div(m * sh.n_pts, RWAVE), RWAVE, 0, k->st>>>(k->d_shape.p + ph, d_status, m, k->b_part.p, unc0, unc1, cmp);
-                CG_KERNEL_CHECK();
-            };
-            k_range_poly<PH_COMMIT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_COMMIT].n_terms, d_terms, d_ev,
-                                                                      d_pr, d_status, 0);
-            CG_KERNEL_CHECK();
-            points(PH_COMMIT, k->o_comf.words_mut(), k->o_comg.words_mut(), k->o_ts.words_mut());
-            k_range_challenge_c<<<lanes, RWAVE, 0, k->st>>>(k->o_ts.words(), d_ped, slot_cmp, k->key_cmp.p, d_status, m, k->o_pedc.words_mut(), d_c,
-                                                           k->o_pokc.words_mut());
-            CG_KERNEL_CHECK();
-            k_range_poly<PH_QUOTIENT><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_QUOTIENT].n_terms, d_terms,
-                                                                        d_ev, d_pr, d_status, 1);
-            CG_KERNEL_CHECK();
-            points(PH_QUOTIENT, k->o_comq.words_mut(), nullptr, k->o_tsq.words_mut());
-            k_range_challenge_rho<<<lanes, RWAVE, 0, k->st>>>(k->o_ts.words(), k->o_tsq.words(), d_status, m, d_rho);
-            CG_KERNEL_CHECK();
-            k_range_poly<PH_OPEN><<<(uint32_t)m, RWAVE, 0, k->st>>>(k->kc, d_open, d_rand, d_c, d_rho, m, k->shape[PH_OPEN].n_terms, d_terms, d_ev, d_pr,
-                                                                    d_status, 1);
-            CG_KERNEL_CHECK();
-            points(PH_OPEN, d_pr, nullptr, nullptr);
-            const RpProof o{k->o_comf.words_mut(), k->o_comg.words_mut(), k->o_comq.words_mut(), d_ev, d_pr, k->o_pokc.words_mut(),
-                            k->o_poks.words_mut(), k->o_chal.words_mut()};
-            k_range_finish<<<lanes, RWAVE, 0, k->st>>>(d_open, d_rand, d_ped, d_c, d_rho, m, o, d_status);
-            CG_KERNEL_CHECK();
-            k->o_comf.down(k->st, com_f, off, m);
-            k->o_comg.down(k->st, com_g, off, m);
-            k->o_comq.down(k->st, com_q, off, m);
-            k->o_evals.down(k->st, evals, off, m);
-            k->o_proofs.down(k->st, proofs, off, m);
-            k->o_pokc.down(k->st, pok_c, off, m);
-            k->o_poks.down(k->st, pok_s, off, m);
-            k->o_chal.down(k->st, challenges_out, off, m);
-            k->b_status.down(k->st, status, off, m);
+            rp_piece(k, slot, k->b_open.words(), k->o_ped.words(), rand + off * k->b_rand.row, k->b_rand.row, out, off, m, nullptr);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -493,3 +514,18 @@ extern "C" int cg_range_prove_batch(cg_range_pk* k, uint32_t slot, const uint8_t
         return translate_current_exception();
     }
 }
+
+namespace cg {
+static_assert(RANGE_PK_PIECE == RCHUNK, "rangeproof.hpp states the piece of rangeproof.hip");
+std::mutex& range_pk_lock(cg_range_pk* k) { return k->mu; }
+int range_pk_device(const cg_range_pk* k) { return k->device; }
+hipStream_t range_pk_stream(cg_range_pk* k) { return k->st; }
+const uint8_t* range_pk_slot_bytes(const cg_range_pk* k, uint32_t slot) {
+    return slot < k->slots.registered.size() ? k->slots.registered[slot].data() : nullptr;
+}
+void range_pk_reserve(cg_range_pk* k, uint64_t piece) { rp_reserve(k, piece < RCHUNK ? piece : RCHUNK); }
+void range_pk_enqueue(cg_range_pk* k, uint32_t slot, const uint32_t* d_openings, const uint32_t* d_ped_com, const uint8_t* rand,
+                      uint64_t rand_pitch, const RangePkOut& out, uint64_t off, uint64_t m, uint8_t* d_status) {
+    rp_piece(k, slot, d_openings, d_ped_com, rand, rand_pitch, out, off, m, d_status);
+}
+}  // namespace cg

@@ -51,6 +51,21 @@
 //   k_show_verdict    one lane per showing: the parts side by side and their conjunction
 // cg_show_shift_batch is the creating side's link (lib.rs:370-372): k_show_shift, the same row routine with the opening.
 //
+// cg_create_showings_batch creates a showing whole: `create_show_proof` (creds/src/lib.rs:364-373, :468-471, :505-509) for a
+// batch of client states of one layout, each with its range proofs.  It owns a cg_range_pk beside the cg_pvk and a chunk of
+// client states runs, with nothing coming down in between,
+//   k_mk_check, k_mk_fixed   as above
+//   k_mk_out          the points that need the fixed-base partials alone: com_hidden, the committed points, the k_i
+//   k_mk_shift        one lane per (range, showing): the link's opening (m - t, r) out of the showing's own inputs and rand
+//                     (show_make.hpp) and ped_com = committed - t·gamma_abc[pos], where the range key's kernels read them
+//   the kernels of cg_range_prove_batch per range and piece, on the range key's stream behind an event (rangeproof.hpp's
+//                     internal entry), beside
+//   k_mk_var, k_mk_out       the re-randomised proof
+//   k_mk_challenge    one lane per showing: DLogPoK::prove's Merlin transcript (dlog.rs:56-99) over the compressed bases,
+//                     the k_i and the y_i as k_mk_out wrote them -> c
+//   k_mk_respond      one lane per (showing, response): s = nonce - c·secret (show_make.hpp, the row dlog_respond takes)
+//   k_mk_parts        one lane per showing: the parts' status bytes side by side and their conjunction
+//
 // Shared by the three entries: the double-and-add chains are fixed_base.hpp's scalar_mul_254_mixed; ark_codec.hpp reads and
 // writes every point on the device; io_layout parses a call's io_types once, for the verifier's and the creator's shapes
 // alike; and the handle has one set of per-call arrays, named by what they hold.  Shared with the range keys, in
@@ -62,8 +77,10 @@
 #include "key_handle.hpp"
 #include "pairing.hpp"
 #include "pairing_team.hpp"
+#include "rangeproof.hpp"
 #include "rangeverify.hpp"
 #include "show_link.hpp"
+#include "show_make.hpp"
 
 using namespace cg;
 
@@ -322,6 +339,18 @@ __global__ __launch_bounds__(VBLOCK) void k_show_k(uint64_t n, ShowShape sh, con
 // (y_cmp: n_com + 1 points of 8 words per showing); k_i is k_show_k's output, on the device already.  A showing whose status
 // is not ST_OK has k_i of zero bytes and a verdict that says so: it is skipped.  c' goes out, with a byte c' == pok_c, and
 // a showing stays CG_VERIFY_ACCEPT only where that byte is set.  Arithmetic on bytes only: no private segment.
+// the transcript of showing p on either side of a showing: y_i compressed into y, then the challenge into c
+__device__ __forceinline__ void show_transcript_lane(uint8_t* __restrict__ sponge_lane, const uint32_t* __restrict__ com_hidden,
+                                                     const uint32_t* __restrict__ committed, uint64_t p, uint32_t n_com, uint32_t n_resp,
+                                                     const uint8_t* __restrict__ bases_cmp, const uint32_t* __restrict__ k_pts,
+                                                     const uint8_t* __restrict__ context, uint64_t context_len, uint32_t* __restrict__ y,
+                                                     uint32_t* __restrict__ c) {
+    const uint32_t n_stmt = n_com + 1, n_last = n_resp - 2 * n_com;
+    for (uint32_t i = 0; i < n_com; ++i) ml_compress_g1(committed + 16 * (p * n_com + i), y + 8 * i);
+    ml_compress_g1(com_hidden + 16 * p, y + 8 * n_com);
+    ml_dlog_shape_challenge(sponge_lane, context, context_len, n_stmt, [=](uint32_t i) { return i < n_com ? 2u : n_last; }, bases_cmp,
+                            (const uint8_t*)(k_pts + 8 * p * n_stmt), (const uint8_t*)y, (uint8_t*)c);
+}
 __global__ __launch_bounds__(VBLOCK) void k_show_challenge(const uint32_t* __restrict__ com_hidden, const uint32_t* __restrict__ committed,
                                                           const uint32_t* __restrict__ pok_c, uint64_t n, ShowShape sh,
                                                           const uint8_t* __restrict__ bases_cmp, const uint32_t* __restrict__ k_pts,
@@ -337,14 +366,8 @@ __global__ __launch_bounds__(VBLOCK) void k_show_challenge(const uint32_t* __res
         same[p] = 0;
         return;
     }
-    const uint32_t n_stmt = sh.n_com + 1, n_last = sh.n_resp - 2 * sh.n_com;
-    uint32_t* y = y_cmp + 8 * p * n_stmt;
-    for (uint32_t i = 0; i < sh.n_com; ++i) ml_compress_g1(committed + 16 * (p * sh.n_com + i), y + 8 * i);
-    ml_compress_g1(com_hidden + 16 * p, y + 8 * sh.n_com);
-    const uint32_t n_com = sh.n_com;
-    ml_dlog_shape_challenge(sponge + ML_STATE * threadIdx.x, context + p * context_stride, context_len, n_stmt,
-                            [=](uint32_t i) { return i < n_com ? 2u : n_last; }, bases_cmp, (const uint8_t*)(k_pts + 8 * p * n_stmt),
-                            (const uint8_t*)y, (uint8_t*)c);
+    show_transcript_lane(sponge + ML_STATE * threadIdx.x, com_hidden, committed, p, sh.n_com, sh.n_resp, bases_cmp, k_pts,
+                         context + p * context_stride, context_len, y_cmp + 8 * p * (sh.n_com + 1), c);
     uint32_t differ = 0;
     for (int l = 0; l < 8; ++l) differ |= c[l] ^ pok_c[8 * p + l];
     same[p] = differ == 0;
@@ -493,16 +516,18 @@ __global__ __launch_bounds__(VBLOCK) void k_mk_check(const uint32_t* __restrict_
 }
 
 // one lane per (showing, output point): the partials summed with the general `add` (two of them coincide or cancel for
-// chosen randomness), affine, written as ark-serialize writes them; zeros for a malformed showing
-__global__ __launch_bounds__(VBLOCK) void k_mk_out(const uint32_t* __restrict__ proofs, uint64_t n, MkShape sh,
+// chosen randomness), affine, written as ark-serialize writes them; zeros for a malformed showing.  A launch writes the
+// points [o_lo, o_lo + o_n) of every showing: all n_out of them, or - cg_create_showings_batch - the points from 3 on, which
+// need k_mk_fixed's partials alone, before k_mk_var and A', B', C'' behind it
+__global__ __launch_bounds__(VBLOCK) void k_mk_out(const uint32_t* __restrict__ proofs, uint64_t n, MkShape sh, uint32_t o_lo, uint32_t o_n,
                                                   const G1XYZZ* __restrict__ part, const G2XYZZ* __restrict__ part_g2,
                                                   const uint8_t* __restrict__ status, uint32_t* __restrict__ rand_proofs,
                                                   uint32_t* __restrict__ com_hidden, uint32_t* __restrict__ committed,
                                                   uint32_t* __restrict__ k_out) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n * sh.n_out) return;
-    const uint64_t p = g / sh.n_out;
-    const uint32_t o = (uint32_t)(g % sh.n_out);
+    if (g >= n * o_n) return;
+    const uint64_t p = g / o_n;
+    const uint32_t o = o_lo + (uint32_t)(g % o_n);
     const bool made = status[p] == CG_SHOW_MADE;
     const G1XYZZ* pt = part + p * sh.n_terms;
     if (o == 1) {                                                 // B' = r1·(B + r2·delta_g2)
@@ -549,6 +574,102 @@ __global__ __launch_bounds__(VBLOCK) void k_mk_out(const uint32_t* __restrict__ 
     dev_put_g1(to_affine(acc), out, compressed);
 }
 
+// ---- creating whole showings (create_show_proof, creds/src/lib.rs:364-373, :468-471, :505-509) ----------------------------
+// DLogPoK::prove's transcript (dlog.rs:56-99), one lane per showing, the sponge in LDS at ML_STATE bytes per lane as in
+// k_show_challenge, whose text it shares (show_transcript_lane): the bases compressed once per call in resp_tab order, y_i
+// compressed here from committed / com_hidden and k_i read as k_mk_out wrote them.  A showing that is not CG_SHOW_MADE has
+// zero rows there and gets c = 0.  Arithmetic on bytes only: no private segment.
+__global__ __launch_bounds__(VBLOCK) void k_mk_challenge(const uint32_t* __restrict__ com_hidden, const uint32_t* __restrict__ committed, uint64_t n,
+                                                        MkShape sh, const uint8_t* __restrict__ bases_cmp, const uint32_t* __restrict__ k_pts,
+                                                        const uint8_t* __restrict__ context, uint64_t context_len, uint64_t context_stride,
+                                                        const uint8_t* __restrict__ status, uint32_t* __restrict__ y_cmp, uint32_t* __restrict__ c_out) {
+    __shared__ __attribute__((aligned(8))) uint8_t sponge[VBLOCK * ML_STATE];
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    uint32_t* c = c_out + 8 * p;
+    if (status[p] != CG_SHOW_MADE) {
+        for (int l = 0; l < 8; ++l) c[l] = 0;
+        return;
+    }
+    show_transcript_lane(sponge + ML_STATE * threadIdx.x, com_hidden, committed, p, sh.n_com, sh.n_resp, bases_cmp, k_pts,
+                         context + p * context_stride, context_len, y_cmp + 8 * p * (sh.n_com + 1), c);
+}
+
+// DLogPoK::prove's responses (dlog.rs:101-109), one lane per (showing, response): the secret and the nonce where `desc`
+// says k_mk_fixed read them, c to Montgomery form once per lane (k_range_finish does it once per showing, for six rows),
+// then show_make.hpp's row.  k_mk_check found every scalar below r; zeros for a showing it refused.
+__global__ __launch_bounds__(VBLOCK) void k_mk_respond(const uint32_t* __restrict__ inputs, const uint32_t* __restrict__ rand,
+                                                      const uint32_t* __restrict__ c, uint64_t n, MkShape sh, const uint32_t* __restrict__ desc,
+                                                      const uint8_t* __restrict__ status, uint32_t* __restrict__ pok_s) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * sh.n_resp) return;
+    const uint64_t p = g / sh.n_resp;
+    const uint32_t t = (uint32_t)(g % sh.n_resp);
+    uint32_t* s = pok_s + 8 * g;
+    if (status[p] != CG_SHOW_MADE) {
+        for (int l = 0; l < 8; ++l) s[l] = 0;
+        return;
+    }
+    const uint32_t src = desc[sh.n_fix + t], nonce = desc[sh.n_fix + sh.n_resp + t] & ~MK_RAND;
+    const uint32_t* rd = rand + 8 * p * sh.n_rand;
+    mk_response_row(mk_challenge_mont(c + 8 * p), src & MK_RAND ? rd + 8 * (src & ~MK_RAND) : inputs + 8 * (p * sh.n_io + src), rd + 8 * nonce, s);
+}
+
+// The creating side's link inside the call: one lane per (range, showing), range-major so that a wave walks one table, as
+// k_show_link.  link: per range the committed index, then per range the input (its table).  The opening is the showing's
+// own (show_make.hpp): m = inputs[pos], r = r_ci of rand; the row is k_show_shift's - m, r, t below r, the committed point as
+// k_mk_out wrote it through the checked read - and it goes out as (m - t, r), 64 B, and ped_com, 64 B, range j's m rows at
+// j·m, where the range key's kernels read them, with a made byte per row.
+// How the range half learns of a refused row (the showing is not CG_SHOW_MADE, or a scalar is >= r): its opening is written
+// as zeros and its ped_com with both flag bits set.  k_range_finish's checked read of ped_com refuses that as it refuses
+// any such row, zeroes every output row of the proof and sets its status to CG_SHOW_MALFORMED; k_mk_parts also reads the
+// made byte.
+__global__ __launch_bounds__(VBLOCK) void k_mk_shift(const uint32_t* __restrict__ inputs, const uint32_t* __restrict__ rand,
+                                                    const uint32_t* __restrict__ committed, const uint32_t* __restrict__ shifts,
+                                                    const uint8_t* __restrict__ status, uint64_t n, MkShape sh, uint32_t n_ranges,
+                                                    const uint32_t* __restrict__ link, const G1Affine* __restrict__ tab,
+                                                    uint32_t* __restrict__ openings, uint32_t* __restrict__ ped_com, uint8_t* __restrict__ made) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n * n_ranges) return;
+    const uint32_t j = (uint32_t)(g / n);
+    const uint64_t p = g % n;
+    const uint32_t ci = link[j], pos = link[n_ranges + j];
+    const MkOpeningAt at = mk_link_opening(p, sh.n_io, sh.n_rand, pos, ci);
+    const uint32_t *m = inputs + 8 * at.m, *r = rand + 8 * at.r, *t = shifts + 8 * (p * n_ranges + j);
+    uint32_t *op = openings + 16 * g, *pc_out = ped_com + 16 * g;
+    G1Affine pc;
+    const bool ok = status[p] == CG_SHOW_MADE && link_below_r(m) && link_below_r(r) &&
+                    link_row(committed + 16 * (p * sh.n_com + ci), t, tab + (uint64_t)pos * FB_NWIN * FB_WIN, pc);
+    made[g] = ok ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+    if (!ok) {
+        for (int l = 0; l < 16; ++l) {
+            op[l] = 0;
+            pc_out[l] = 0xFFFFFFFFu;
+        }
+        return;
+    }
+    shift_opening(m, t, op);
+    for (int l = 0; l < 8; ++l) op[8 + l] = r[l];
+    dev_put_g1(pc, pc_out, false);
+}
+
+// The conjunction, one lane per showing: the Groth16 part, then the range parts (range j's m bytes at j·m: made only where
+// k_mk_shift made the row and the range key's kernels the proof) -> parts, row per showing, and the showing's status
+__global__ __launch_bounds__(VBLOCK) void k_mk_parts(const uint8_t* __restrict__ groth, const uint8_t* __restrict__ shift_made,
+                                                    const uint8_t* __restrict__ range, uint64_t n, uint32_t n_ranges,
+                                                    uint8_t* __restrict__ parts, uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    bool all = groth[p] == CG_SHOW_MADE;
+    parts[p * (n_ranges + 1)] = groth[p];
+    for (uint32_t j = 0; j < n_ranges; ++j) {
+        const bool made = shift_made[j * n + p] == CG_SHOW_MADE && range[j * n + p] == CG_SHOW_MADE;
+        parts[p * (n_ranges + 1) + 1 + j] = made ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+        all = all && made;
+    }
+    status[p] = all ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+}
+
 }  // namespace
 
 struct cg_pvk : KeyHandle {
@@ -591,6 +712,9 @@ struct cg_pvk : KeyHandle {
     DevBuf<uint8_t> b_bases_cmp;
     RowBuf b_ctx, b_ycmp, b_cprime{32}, b_same{1}, b_shift, b_link, b_rverd, b_parts, b_final{1};
     hipEvent_t ev_link = nullptr, ev_ranges = nullptr;      // the range key's stream behind the link, ours behind its last kernel
+    // creating whole showings (cg_create_showings_batch) also: the responses, and per (showing, range) the link's opening and
+    // made byte; ped_com is in b_link and the range parts' status bytes come back into b_rverd
+    RowBuf b_resp, b_lopen, b_lmade;
     void open_second() {
         CG_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_link, &ev_ranges}) CG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -899,6 +1023,49 @@ extern "C" int cg_pvk_set_showings_overlap(cg_pvk* k, int32_t on) {
     return CG_OK;
 }
 
+// ---- what the two whole-showing entries check and build alike, on the host --------------------------------------------------
+namespace {
+// the DLogPoK's context as cg_dlog_challenge_batch takes it: CG_OK, or the failure already recorded
+int check_context(const uint8_t* context, uint64_t context_len, uint64_t context_stride) {
+    if (context_len && !context) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (context_stride && context_stride < context_len)
+        return fail(CG_ERR_INVALID_ARGUMENT, "a context stride of %llu is shorter than the context's %llu bytes", (unsigned long long)context_stride,
+                    (unsigned long long)context_len);
+    if (context_len > 0xffffffffull - 8) return fail(CG_ERR_INVALID_ARGUMENT, "a context of %llu bytes is longer than a Merlin message", (unsigned long long)context_len);
+    return CG_OK;
+}
+// every link's slot holds gamma_abc_g1[pos] ‖ delta_g1 of this key; slot_bytes(slot) is the range key's registered 128 bytes or
+// null, `add_bases` the call that registers them.  Under both locks
+template <class SlotBytes>
+int check_link_slots(const cg_pvk* k, const IoLayout& L, uint64_t n_io, uint32_t n_ranges, const cg_show_range_link* links, SlotBytes slot_bytes,
+                     const char* add_bases) {
+    const uint8_t* delta = k->base_bytes.data() + 64 * n_io;
+    for (uint32_t j = 0; j < n_ranges; ++j) {
+        const uint8_t* reg = slot_bytes(links[j].slot);
+        if (!reg) return fail(CG_ERR_INVALID_ARGUMENT, "link %u: slot %u was not registered on the range key (%s)", j, links[j].slot, add_bases);
+        const uint32_t input = L.com[links[j].committed_index];
+        if (memcmp(reg, k->base_bytes.data() + 64 * (uint64_t)input, 64) || memcmp(reg + 64, delta, 64))
+            return fail(CG_ERR_INVALID_ARGUMENT, "link %u: slot %u does not hold gamma_abc_g1[%u] and delta_g1 of this key", j, links[j].slot, input + 1);
+    }
+    return CG_OK;
+}
+// the bases as the DLogPoK's transcript absorbs them, in the order the responses meet them
+std::vector<uint32_t> compressed_bases(const cg_pvk* k, const IoLayout& L) {
+    std::vector<uint32_t> bases_cmp(8 * L.resp_tab.size());
+    for (size_t t = 0; t < L.resp_tab.size(); ++t) {
+        uint32_t w[16];
+        memcpy(w, k->base_bytes.data() + 64 * (uint64_t)L.resp_tab[t], 64);
+        ml_compress_g1(w, bases_cmp.data() + 8 * t);
+    }
+    return bases_cmp;
+}
+// a chunk's contexts, one per showing: the caller's last context ends with its bytes, not with its stride
+void contexts_up(cg_pvk* k, const uint8_t* context, uint64_t context_len, uint64_t context_stride, uint64_t off, uint64_t m) {
+    if (context_stride && context_len)
+        CG_HIP(hipMemcpyAsync(k->b_ctx.bytes(), context + off * context_stride, (m - 1) * context_stride + context_len, hipMemcpyHostToDevice, k->st));
+}
+}  // namespace
+
 // `verify_show`'s cryptographic checks (creds/src/lib.rs:630-658, :832-890) for a batch of showings of one layout: the
 // kernels of cg_verify_show_batch, k_show_challenge behind k_show_k, k_show_link into memory the range key's kernels read
 // (rangeverify.hpp's internal entry, on the range key's stream behind an event), k_show_verdict.  Per chunk nothing comes
@@ -916,12 +1083,9 @@ extern "C" int cg_verify_showings_batch(cg_pvk* k, cg_range_vk* rk, const uint8_
     const ShowShape sh = show_shape(L, true, desc);
     const uint32_t n_tab_of = (uint32_t)desc.size(), n_stmt = sh.n_com + 1;
     if (!rand_proofs || !com_hidden || !verdicts || !pok_c || !pok_s || (sh.n_rev && !revealed) || (sh.n_com && !committed) ||
-        (context_len && !context) || (n_ranges && (!rk || !links || !shifts || !ranges)))
+        (n_ranges && (!rk || !links || !shifts || !ranges)))
         return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
-    if (context_stride && context_stride < context_len)
-        return fail(CG_ERR_INVALID_ARGUMENT, "a context stride of %llu is shorter than the context's %llu bytes", (unsigned long long)context_stride,
-                    (unsigned long long)context_len);
-    if (context_len > 0xffffffffull - 8) return fail(CG_ERR_INVALID_ARGUMENT, "a context of %llu bytes is longer than a Merlin message", (unsigned long long)context_len);
+    if (int rc = check_context(context, context_len, context_stride)) return rc;
     for (uint32_t j = 0; j < n_ranges; ++j) {
         const cg_range_rows& r = ranges[j];
         if (!r.com_f || !r.com_g || !r.com_q || !r.evals || !r.proofs || !r.randomizers || !r.pok_c || !r.pok_s)
@@ -939,21 +1103,9 @@ extern "C" int cg_verify_showings_batch(cg_pvk* k, cg_range_vk* rk, const uint8_
             if (range_vk_device(rk) != k->device)
                 return fail(CG_ERR_INVALID_ARGUMENT, "the Groth16 key is on device %d and the range key on device %d", k->device, range_vk_device(rk));
         }
-        const uint8_t* delta = k->base_bytes.data() + 64 * n_io;
-        for (uint32_t j = 0; j < n_ranges; ++j) {
-            const uint8_t* reg = range_vk_slot_bytes(rk, links[j].slot);
-            if (!reg) return fail(CG_ERR_INVALID_ARGUMENT, "link %u: slot %u was not registered on the range key (cg_range_vk_add_bases)", j, links[j].slot);
-            const uint32_t input = L.com[links[j].committed_index];
-            if (memcmp(reg, k->base_bytes.data() + 64 * (uint64_t)input, 64) || memcmp(reg + 64, delta, 64))
-                return fail(CG_ERR_INVALID_ARGUMENT, "link %u: slot %u does not hold gamma_abc_g1[%u] and delta_g1 of this key", j, links[j].slot, input + 1);
-        }
-        // the bases as the transcript absorbs them, in the order the responses meet them
-        std::vector<uint32_t> bases_cmp(8 * (size_t)sh.n_resp);
-        for (uint32_t t = 0; t < sh.n_resp; ++t) {
-            uint32_t w[16];
-            memcpy(w, k->base_bytes.data() + 64 * (uint64_t)L.resp_tab[t], 64);
-            ml_compress_g1(w, bases_cmp.data() + 8 * t);
-        }
+        if (int rc = check_link_slots(k, L, n_io, n_ranges, links, [&](uint32_t slot) { return range_vk_slot_bytes(rk, slot); }, "cg_range_vk_add_bases"))
+            return rc;
+        const std::vector<uint32_t> bases_cmp = compressed_bases(k, L);
         CG_HIP(hipSetDevice(k->device));
         const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
         for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_verdict, &k->b_in_g2, &k->b_comh, &k->b_chal, &k->b_cprime, &k->b_same, &k->b_final})
@@ -988,9 +1140,7 @@ extern "C" int cg_verify_showings_batch(cg_pvk* k, cg_range_vk* rk, const uint8_
             k->b_chal.up(k->st, pok_c, off, m);
             k->b_rows.up(k->st, pok_s, off, m);
             k->b_shift.up(k->st, shifts, off, m);
-            if (context_stride && context_len)    // the caller's last context ends with its bytes, not with its stride
-                CG_HIP(hipMemcpyAsync(k->b_ctx.bytes(), context + off * context_stride, (m - 1) * context_stride + context_len,
-                                      hipMemcpyHostToDevice, k->st));
+            contexts_up(k, context, context_len, context_stride, off, m);
             const uint32_t *d_rev = k->b_inputs.words(), *d_s = k->b_rows.words(), *d_c = k->b_chal.words(), *d_comh = k->b_comh.words(),
                            *d_comm = k->b_comm.words();
             const uint32_t grid = ceil_div(m, VBLOCK);
@@ -1033,6 +1183,150 @@ extern "C" int cg_verify_showings_batch(cg_pvk* k, cg_range_vk* rk, const uint8_
             CG_KERNEL_CHECK();
             k->b_final.down(k->st, verdicts, off, m);
             k->b_parts.down(k->st, part_verdicts, off, m);
+            CG_HIP(hipStreamSynchronize(k->st));
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
+// `create_show_proof`'s curve arithmetic and transcripts (creds/src/lib.rs:364-373, :468-471, :505-509) for a batch of client
+// states of one layout.  Per chunk of VCHUNK states the kernels run in the order of this file's head; the range half walks
+// the chunk in pieces of RANGE_PK_PIECE on the range key's stream (rangeproof.hpp), reading the openings and ped_com where
+// k_mk_shift wrote them and bringing its proof rows down itself.  With the overlap on it waits for an event recorded right
+// behind k_mk_shift and so runs beside k_mk_var, which it does not need; with it off, for one recorded behind k_mk_respond.
+// Either way the range half is put on its stream after every Groth16 kernel is on ours: its copies to the caller's memory
+// may hold the host.  Our stream waits for the range stream's last copy before k_mk_parts.  The locks are taken in the
+// order cg_pvk, cg_range_pk.
+extern "C" int cg_create_showings_batch(cg_pvk* k, cg_range_pk* rk, const uint8_t* io_types, uint64_t n_io, const uint8_t* context,
+                                        uint64_t context_len, uint64_t context_stride, const uint8_t* proofs, const uint8_t* inputs,
+                                        const uint8_t* rand, uint32_t n_ranges, const cg_show_range_link* links, const uint8_t* shifts,
+                                        const uint8_t* range_rand, uint64_t n, uint8_t* rand_proofs, uint8_t* com_hidden, uint8_t* committed,
+                                        uint8_t* pok_c, uint8_t* pok_s, const cg_range_made* ranges, uint8_t* status, uint8_t* part_status) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    IoLayout L;
+    if (int rc = io_layout(k, io_types, n_io, L)) return rc;
+    if (!k->gamma_is_one)
+        return fail(CG_ERR_MALFORMED_KEY, "gamma_g2 is not the G2 generator: C - (acc_r + z) G re-randomises gamma = 1 keys only");
+    if (n == 0) return CG_OK;
+    const MkShape sh = mk_shape(L, n_io);
+    if (!proofs || !rand || !rand_proofs || !com_hidden || !pok_c || !pok_s || !status || (sh.n_resp > 1 && !inputs) || (sh.n_com && !committed) ||
+        (n_ranges && (!rk || !links || !shifts || !range_rand || !ranges)))
+        return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (int rc = check_context(context, context_len, context_stride)) return rc;
+    for (uint32_t j = 0; j < n_ranges; ++j) {
+        const cg_range_made& r = ranges[j];
+        if (!r.com_f || !r.com_g || !r.com_q || !r.evals || !r.proofs || !r.pok_c || !r.pok_s) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+        if (links[j].committed_index >= sh.n_com)
+            return fail(CG_ERR_INVALID_ARGUMENT, "link %u: committed_index %u of %u committed inputs", j, links[j].committed_index, sh.n_com);
+    }
+    std::vector<uint32_t> desc = mk_desc(L, sh);                  // then k_mk_shift's: the committed index and the input per range
+    const uint32_t n_mk_desc = (uint32_t)desc.size(), n_stmt = sh.n_com + 1;
+    for (uint32_t j = 0; j < n_ranges; ++j) desc.push_back(links[j].committed_index);
+    for (uint32_t j = 0; j < n_ranges; ++j) desc.push_back(L.com[links[j].committed_index]);
+    try {
+        std::lock_guard<std::mutex> lk(k->mu);
+        std::unique_lock<std::mutex> lr;
+        if (n_ranges) {
+            lr = std::unique_lock<std::mutex>(range_pk_lock(rk));
+            if (range_pk_device(rk) != k->device)
+                return fail(CG_ERR_INVALID_ARGUMENT, "the Groth16 key is on device %d and the range key on device %d", k->device, range_pk_device(rk));
+        }
+        if (int rc = check_link_slots(k, L, n_io, n_ranges, links, [&](uint32_t slot) { return range_pk_slot_bytes(rk, slot); }, "cg_range_pk_add_bases"))
+            return rc;
+        const std::vector<uint32_t> bases_cmp = compressed_bases(k, L);
+        CG_HIP(hipSetDevice(k->device));
+        const uint64_t chunk = n < VCHUNK ? n : VCHUNK;
+        for (RowBuf* b : {&k->b_proofs, &k->b_status, &k->b_rproofs, &k->b_comh, &k->b_cprime, &k->b_final}) b->reserve(chunk);
+        k->b_inputs.reserve(chunk, sh.n_io * 32);
+        k->b_rows.reserve(chunk, sh.n_rand * 32);
+        k->b_comm.reserve(chunk, sh.n_com * 64);
+        k->b_k.reserve(chunk, n_stmt * 32);
+        k->b_ycmp.reserve(chunk, n_stmt * 32);
+        k->b_resp.reserve(chunk, sh.n_resp * 32);
+        k->b_shift.reserve(chunk, n_ranges * 32);
+        k->b_lopen.reserve(chunk, n_ranges * 64);
+        k->b_link.reserve(chunk, n_ranges * 64);
+        k->b_lmade.reserve(chunk, n_ranges);
+        k->b_rverd.reserve(chunk, n_ranges);
+        k->b_parts.reserve(chunk, n_ranges + 1);
+        if (context_stride) k->b_ctx.reserve(chunk, context_stride);
+        else k->b_ctx.reserve(1, context_len);
+        grow(k->b_part, chunk * sh.n_terms + 1);
+        grow(k->b_part_g2, chunk);
+        grow(k->b_desc, desc.size());
+        grow(k->b_bases_cmp, bases_cmp.size() * sizeof(uint32_t));
+        h2d_sync(k->b_desc.p, desc.data(), desc.size() * sizeof(uint32_t), k->st);
+        h2d_sync(k->b_bases_cmp.p, bases_cmp.data(), bases_cmp.size() * sizeof(uint32_t), k->st);
+        if (!context_stride) k->b_ctx.up(k->st, context, 0, 1);
+        if (n_ranges) range_pk_reserve(rk, chunk);
+        k->timer.reset();                     // the two handles' stages interleave: nothing is timed
+        const uint64_t rand_pitch = (uint64_t)n_ranges * CG_RANGE_N_RAND * 32;
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            k->b_proofs.up(k->st, proofs, off, m);
+            k->b_inputs.up(k->st, inputs, off, m);
+            k->b_rows.up(k->st, rand, off, m);
+            k->b_shift.up(k->st, shifts, off, m);
+            contexts_up(k, context, context_len, context_stride, off, m);
+            const uint32_t *d_pr = k->b_proofs.words(), *d_in = k->b_inputs.words(), *d_rd = k->b_rows.words();
+            uint8_t* d_status = k->b_status.bytes();
+            const uint32_t grid = ceil_div(m, VBLOCK);
+            auto out = [&](uint32_t o_lo, uint32_t o_n) {
+                k_mk_out<<<ceil_div(m * o_n, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, o_lo, o_n, k->b_part.p, k->b_part_g2.p, d_status,
+                                                                         k->b_rproofs.words_mut(), k->b_comh.words_mut(), k->b_comm.words_mut(),
+                                                                         k->b_k.words_mut());
+                CG_KERNEL_CHECK();
+            };
+            k_mk_check<<<grid, VBLOCK, 0, k->st>>>(d_pr, d_in, d_rd, m, sh, k->b_desc.p, d_status);
+            CG_KERNEL_CHECK();
+            k_mk_fixed<<<ceil_div(m * sh.n_fix, VBLOCK), VBLOCK, 0, k->st>>>(d_in, d_rd, m, sh, k->b_desc.p, k->tab.p, k->b_part.p);
+            CG_KERNEL_CHECK();
+            out(3u, sh.n_out - 3);                                // com_hidden, committed, k: the fixed-base partials alone
+            if (n_ranges) {
+                k_mk_shift<<<ceil_div(m * n_ranges, VBLOCK), VBLOCK, 0, k->st>>>(d_in, d_rd, k->b_comm.words(), k->b_shift.words(), d_status, m, sh, n_ranges,
+                                                                                k->b_desc.p + n_mk_desc, k->tab.p, k->b_lopen.words_mut(),
+                                                                                k->b_link.words_mut(), k->b_lmade.bytes());
+                CG_KERNEL_CHECK();
+                if (k->overlap) CG_HIP(hipEventRecord(k->ev_link, k->st));
+            }
+            k_mk_var<<<ceil_div(2 * m, VBLOCK) + grid, VBLOCK, 0, k->st>>>(d_pr, d_rd, m, sh, k->tab_g2.p, k->b_part.p, k->b_part_g2.p);
+            CG_KERNEL_CHECK();
+            out(0u, 3u);                                          // A', B', C''
+            k_mk_challenge<<<grid, VBLOCK, 0, k->st>>>(k->b_comh.words(), k->b_comm.words(), m, sh, k->b_bases_cmp.p, k->b_k.words(), k->b_ctx.bytes(),
+                                                      context_len, context_stride, d_status, k->b_ycmp.words_mut(), k->b_cprime.words_mut());
+            CG_KERNEL_CHECK();
+            k_mk_respond<<<ceil_div(m * sh.n_resp, VBLOCK), VBLOCK, 0, k->st>>>(d_in, d_rd, k->b_cprime.words(), m, sh, k->b_desc.p, d_status,
+                                                                               k->b_resp.words_mut());
+            CG_KERNEL_CHECK();
+            if (n_ranges) {
+                if (!k->overlap) CG_HIP(hipEventRecord(k->ev_link, k->st));
+                hipStream_t rst = range_pk_stream(rk);
+                CG_HIP(hipStreamWaitEvent(rst, k->ev_link, 0));
+                for (uint32_t j = 0; j < n_ranges; ++j) {
+                    const cg_range_made& r = ranges[j];
+                    const RangePkOut ro{r.com_f, r.com_g, r.com_q, r.evals, r.proofs, r.pok_c, r.pok_s, r.challenges, nullptr};
+                    for (uint64_t po = 0; po < m; po += RANGE_PK_PIECE) {
+                        const uint64_t mm = m - po < RANGE_PK_PIECE ? m - po : RANGE_PK_PIECE;
+                        const uint64_t row = (uint64_t)j * m + po;
+                        range_pk_enqueue(rk, links[j].slot, k->b_lopen.words() + 16 * row, k->b_link.words() + 16 * row,
+                                         range_rand + (off + po) * rand_pitch + (uint64_t)j * CG_RANGE_N_RAND * 32, rand_pitch, ro, off + po, mm,
+                                         k->b_rverd.bytes() + row);
+                    }
+                }
+                CG_HIP(hipEventRecord(k->ev_ranges, rst));
+                CG_HIP(hipStreamWaitEvent(k->st, k->ev_ranges, 0));
+            }
+            k_mk_parts<<<grid, VBLOCK, 0, k->st>>>(d_status, k->b_lmade.bytes(), k->b_rverd.bytes(), m, n_ranges, k->b_parts.bytes(), k->b_final.bytes());
+            CG_KERNEL_CHECK();
+            k->b_rproofs.down(k->st, rand_proofs, off, m);
+            k->b_comh.down(k->st, com_hidden, off, m);
+            k->b_comm.down(k->st, committed, off, m);
+            k->b_cprime.down(k->st, pok_c, off, m);
+            k->b_resp.down(k->st, pok_s, off, m);
+            k->b_final.down(k->st, status, off, m);
+            k->b_parts.down(k->st, part_status, off, m);
             CG_HIP(hipStreamSynchronize(k->st));
         }
         return CG_OK;
@@ -1125,7 +1419,7 @@ extern "C" int cg_show_commit_batch(cg_pvk* k, const uint8_t* io_types, uint64_t
             k_mk_var<<<ceil_div(2 * m, VBLOCK) + ceil_div(m, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, d_rd, m, sh, k->tab_g2.p, k->b_part.p,
                                                                                          k->b_part_g2.p);
             CG_KERNEL_CHECK();
-            k_mk_out<<<ceil_div(m * sh.n_out, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, k->b_part.p, k->b_part_g2.p, k->b_status.bytes(),
+            k_mk_out<<<ceil_div(m * sh.n_out, VBLOCK), VBLOCK, 0, k->st>>>(d_pr, m, sh, 0u, sh.n_out, k->b_part.p, k->b_part_g2.p, k->b_status.bytes(),
                                                                           k->b_rproofs.words_mut(), k->b_comh.words_mut(),
                                                                           k->b_comm.words_mut(), k->b_k.words_mut());
             CG_KERNEL_CHECK();

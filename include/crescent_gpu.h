@@ -919,7 +919,7 @@ int cg_dlog_challenge_batch(const uint8_t* context, uint64_t context_len, uint64
  * (gamma_abc_g1[pos], delta_g1) of that input - the vk's entry of the input, i.e. gamma_abc_g1[input index + 1]. */
 typedef struct cg_show_range_link {
     uint32_t committed_index;  /* which committed input, counted in committed order (0 = first) */
-    uint32_t slot;             /* cg_range_vk_add_bases' slot for that input's bases */
+    uint32_t slot;             /* cg_range_vk_add_bases' slot for that input's bases (cg_range_pk_add_bases' when creating) */
 } cg_show_range_link;
 /* One range proof per showing, n rows each, in the layouts of cg_range_verify_proofs_batch. */
 typedef struct cg_range_rows {
@@ -963,11 +963,55 @@ int cg_verify_showings_batch(cg_pvk* k, cg_range_vk* rk, const uint8_t* io_types
                              const uint8_t* com_hidden, const uint8_t* committed, const uint8_t* pok_c, const uint8_t* pok_s,
                              uint32_t n_ranges, const cg_show_range_link* links, const uint8_t* shifts, const cg_range_rows* ranges,
                              uint64_t n, uint8_t* verdicts, uint8_t* part_verdicts);
-/* Diagnostic: how cg_verify_showings_batch orders the two halves of a chunk.  1 = the range half starts on the range key's
- * stream as soon as the link is written, beside the Groth16 half; 0 = it starts when the Groth16 half has finished.  The
- * bytes are the same either way (profiles/showing_verify.md has both timings).  A value other than 0 or 1, or a null handle,
+/* Diagnostic: how cg_verify_showings_batch and cg_create_showings_batch order the two halves of a chunk.  1 = the range
+ * half starts on the range key's stream as soon as the link is written, beside the Groth16 half; 0 = it starts when the
+ * Groth16 half has finished.  The bytes are the same either way (profiles/showing_verify.md and profiles/showing_create.md
+ * have both timings).  A value other than 0 or 1, or a null handle,
  * is CG_ERR_INVALID_ARGUMENT.  (No counterpart in the reference.) */
 int cg_pvk_set_showings_overlap(cg_pvk* k, int32_t on);
+/* One range proof per showing, n rows each, in the layouts cg_range_prove_batch writes; challenges may be NULL. */
+typedef struct cg_range_made { uint8_t *com_f, *com_g, *com_q, *evals, *proofs, *pok_c, *pok_s, *challenges; } cg_range_made;
+/* Replaces: the curve arithmetic and the transcripts of `create_show_proof` / `create_show_proof_mdl` (creds/src/lib.rs:364-373,
+ *           :468-471, :505-509) for n client states of one layout in ONE call: `ClientState::show_groth16` whole
+ *           (groth16rand.rs:100-187, with `DLogPoK::prove`'s Merlin transcript, dlog.rs:56-99, and its responses), per range
+ *           proof the link `com.m -= t; com.c -= bases[0] * t` (lib.rs:370-372) and `show_range` whole about it.  It is
+ *           cg_show_commit_batch, cg_dlog_challenge_batch over the key's bases, cg_show_respond_batch and, per link,
+ *           cg_show_shift_batch and cg_range_prove_batch, with every output row byte for byte what that sequence writes for
+ *           the same operands - and nothing coming down or going up again in between.
+ * NOT done here: drawing randomness (the library draws none), `revealed_preimages`, the device proof.
+ * io_types, proofs, inputs, rand: as for cg_show_commit_batch (rand: cg_show_rand_count scalars per showing, same order).
+ * context: as for cg_verify_showings_batch, with the same limits and errors.
+ * links:   n_ranges of them, shared by the batch; `slot` is a slot of the PROVING range key rk (cg_range_pk_add_bases).  Two
+ *          links may name the same committed input (mDL proves two ranges about one date, with different shifts).
+ * shifts:  n x n_ranges x 32 B canonical Fr.  range_rand: n x n_ranges x CG_RANGE_N_RAND x 32 B, the 18 scalars of
+ *          cg_range_prove_batch per (showing, link).
+ * The opening of link j is no input: it is the showing's own, m = inputs[pos] of the linked committed input and r = that
+ * input's r_i in rand (index 2 + committed_index) - `committed_input_openings[ci]` of groth16rand.rs:135-139.
+ * rand_proofs, com_hidden, committed: the layouts of cg_show_commit_batch;  pok_c: n x 32 B;  pok_s: n x n_resp x 32 B, the
+ * layout of cg_show_respond_batch.  ranges: n_ranges cg_range_made of n rows each.
+ * part_status: n x (1 + n_ranges) of CG_SHOW_MADE / CG_SHOW_MALFORMED, may be NULL: the Groth16 part, then the range parts.
+ * status:  n x CG_SHOW_*: MADE only if every part of the showing is.
+ * A malformed part has zero bytes in each of its rows.  A range part whose Groth16 part is malformed is malformed too: there
+ * is no commitment to link from.  A range part alone fails on a shift >= r, a range_rand scalar >= r, or m - t outside
+ * [0, 2^n_bits); the Groth16 rows of that showing stay as made.  A bad showing leaves its neighbours untouched.
+ * Errors, all reported before any HIP call and with no output touched: a null array (rk, links, shifts, range_rand and
+ * ranges may be NULL only with n_ranges = 0, which is `show_groth16` whole); n_io != cg_pvk_num_inputs (CG_ERR_MALFORMED_KEY);
+ * an io byte above 2; a key that is not gamma = 1 (CG_ERR_MALFORMED_KEY); the two handles on different devices; a
+ * committed_index >= n_committed; an unknown slot; a slot whose registered 128 bytes are not byte for byte gamma_abc_g1[pos] ‖
+ * delta_g1 of this key for the linked input; a context_stride shorter than context_len.  n = 0 is CG_OK.
+ * Locks: both handles' locks are held for the call, always taken in the order cg_pvk, then cg_range_pk.  The range proofs
+ * need the committed points alone, so they run on the range key's stream beside the re-randomisation's long chains when
+ * cg_pvk_set_showings_overlap says so; the bytes are the same either way.  Measured on an MI355X at 26 inputs with one 32-bit
+ * range proof (profiles/showing_create.md): 17.5 ms for 1024 whole showings and 64 ms for 16384, against 27 and 92 ms for the
+ * five separate calls; a lone showing 18 ms against 28 ms.
+ * cg_pvk_last_kernel_ms and cg_range_pk_last_kernel_ms read zeros after this call. */
+int cg_create_showings_batch(cg_pvk* k, cg_range_pk* rk, const uint8_t* io_types, uint64_t n_io,
+                             const uint8_t* context, uint64_t context_len, uint64_t context_stride,
+                             const uint8_t* proofs, const uint8_t* inputs, const uint8_t* rand,
+                             uint32_t n_ranges, const cg_show_range_link* links, const uint8_t* shifts, const uint8_t* range_rand,
+                             uint64_t n,
+                             uint8_t* rand_proofs, uint8_t* com_hidden, uint8_t* committed, uint8_t* pok_c, uint8_t* pok_s,
+                             const cg_range_made* ranges, uint8_t* status, uint8_t* part_status);
 /* Replaces: the creating side's link, `com.m -= t; com.c -= bases[0] * t` before `show_range` (lib.rs:370-372, :468-470,
  *           :505-507), for n openings of the committed input `input_index` (an index into io_types; its base is
  *           gamma_abc_g1[input_index + 1]).

@@ -901,8 +901,100 @@ impl GpuVerifyingKey {
         Ok((out, ped, status))
     }
 
-    /// Diagnostic (`cg_pvk_set_showings_overlap`): whether `verify_showings_batch` starts the range half beside the Groth16
-    /// half (the default) or behind it
+    /// `create_show_proof`'s `show_groth16` and `show_range` steps (creds/src/lib.rs:364-373, :468-471, :505-509) for `n`
+    /// client states of one proof spec in one call (`cg_create_showings_batch`): the re-randomised proof, the commitments,
+    /// `DLogPoK::prove` whole with its Merlin transcript over `context`, and per link the shift by `shifts` and
+    /// `prove_n_bits` whole.  `inputs`: n x io_types.len(); `rand`: n x `cg_show_rand_count` scalars drawn by the caller in
+    /// the header's order (r1, r2, the r_i, z, the nonces) - keep the r_i and z as `committed_input_openings` /
+    /// `input_com_randomness`; `links[j]`: the committed input and the slot of `range_key` (`GpuRangeKey::add_bases`);
+    /// `shifts`: n x links.len(); `range_rand`: n x links.len() x CG_RANGE_N_RAND.  The opening of a link is the showing's
+    /// own: (inputs[pos], r_ci).  INTEGRATION.md, "Creating whole showings".
+    #[allow(clippy::too_many_arguments)]
+    pub fn create_showings_batch(&self, range_key: Option<&GpuRangeKey>, io_types: &[u8], context: Option<&[u8]>, proofs: &[Proof<Bn254>],
+                                 inputs: &[Fr], rand: &[Fr], links: &[(u32, u32)], shifts: &[Fr], range_rand: &[Fr])
+                                 -> Result<ShowingsMade, SynthesisError> {
+        let n = proofs.len();
+        let n_com = io_types.iter().filter(|t| **t == sys::CG_IO_COMMITTED).count();
+        let mut n_rand = 0u64;
+        let rc = unsafe { sys::cg_show_rand_count(io_types.as_ptr(), io_types.len() as u64, &mut n_rand) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        if !links.is_empty() && range_key.is_none() {
+            return Err(SynthesisError::AssignmentMissing);
+        }
+        if inputs.len() != n * io_types.len() || rand.len() != n * n_rand as usize || shifts.len() != n * links.len()
+            || range_rand.len() != n * links.len() * sys::CG_RANGE_N_RAND
+        {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let n_resp = n_rand as usize - 3 - n_com;
+        let mut pb = Vec::with_capacity(n * 256);
+        for p in proofs {
+            p.serialize_uncompressed(&mut pb).map_err(|_| SynthesisError::AssignmentMissing)?;
+        }
+        let (ib, rb, sb, rrb) = (canonical_bytes(inputs), canonical_bytes(rand), canonical_bytes(shifts), canonical_bytes(range_rand));
+        let c_links: Vec<sys::cg_show_range_link> = links.iter().map(|&(committed_index, slot)| sys::cg_show_range_link { committed_index, slot }).collect();
+        let mut out = ShowingsMade {
+            rand_proofs: vec![0u8; n * 256],
+            com_hidden: vec![0u8; n * 64],
+            committed: vec![0u8; n * n_com * 64 + 64],
+            pok_c: vec![0u8; n * 32],
+            pok_s: vec![0u8; n * n_resp * 32],
+            ranges: links
+                .iter()
+                .map(|_| RangeProofsMade {
+                    com_f: vec![0u8; n * 64],
+                    com_g: vec![0u8; n * 64],
+                    com_q: vec![0u8; n * 64],
+                    evals: vec![0u8; n * 96],
+                    proofs: vec![0u8; n * 288],
+                    pok_c: vec![0u8; n * 32],
+                    pok_s: vec![0u8; n * sys::CG_RANGE_N_RESP * 32],
+                    challenges: vec![0u8; n * 96],
+                    status: vec![0u8; n],
+                })
+                .collect(),
+            status: vec![0u8; n],
+        };
+        let c_made: Vec<sys::cg_range_made> = out
+            .ranges
+            .iter_mut()
+            .map(|r| sys::cg_range_made {
+                com_f: r.com_f.as_mut_ptr(),
+                com_g: r.com_g.as_mut_ptr(),
+                com_q: r.com_q.as_mut_ptr(),
+                evals: r.evals.as_mut_ptr(),
+                proofs: r.proofs.as_mut_ptr(),
+                pok_c: r.pok_c.as_mut_ptr(),
+                pok_s: r.pok_s.as_mut_ptr(),
+                challenges: r.challenges.as_mut_ptr(),
+            })
+            .collect();
+        let ctx = context.unwrap_or(&[]);
+        let width = 1 + links.len();
+        let mut parts = vec![0u8; n * width];
+        let rc = unsafe {
+            sys::cg_create_showings_batch(self.h, range_key.map_or(std::ptr::null_mut(), |k| k.h), io_types.as_ptr(), io_types.len() as u64,
+                                          if ctx.is_empty() { std::ptr::null() } else { ctx.as_ptr() }, ctx.len() as u64, 0, pb.as_ptr(), ib.as_ptr(),
+                                          rb.as_ptr(), links.len() as u32, c_links.as_ptr(), sb.as_ptr(), rrb.as_ptr(), n as u64,
+                                          out.rand_proofs.as_mut_ptr(), out.com_hidden.as_mut_ptr(), out.committed.as_mut_ptr(),
+                                          out.pok_c.as_mut_ptr(), out.pok_s.as_mut_ptr(), c_made.as_ptr(), out.status.as_mut_ptr(), parts.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        out.committed.truncate(n * n_com * 64);
+        for (j, r) in out.ranges.iter_mut().enumerate() {
+            for i in 0..n {
+                r.status[i] = parts[i * width + 1 + j];
+            }
+        }
+        Ok(out)
+    }
+
+    /// Diagnostic (`cg_pvk_set_showings_overlap`): whether `verify_showings_batch` and `create_showings_batch` start the range
+    /// half beside the Groth16 half (the default) or behind it
     pub fn set_showings_overlap(&self, on: bool) -> Result<(), SynthesisError> {
         let rc = unsafe { sys::cg_pvk_set_showings_overlap(self.h, on as i32) };
         if rc != 0 {
@@ -910,6 +1002,19 @@ impl GpuVerifyingKey {
         }
         Ok(())
     }
+}
+
+/// What `GpuVerifyingKey::create_showings_batch` returns: the Groth16 part in the layouts of `show_commit_batch` and
+/// `show_respond_batch`, per link the rows of `GpuRangeKey::prove_batch` (their `status` is the link's part status), and one
+/// CG_SHOW_* byte per client state: CG_SHOW_MADE only if every part was made.  A part that was not made has zero bytes.
+pub struct ShowingsMade {
+    pub rand_proofs: Vec<u8>,
+    pub com_hidden: Vec<u8>,
+    pub committed: Vec<u8>,
+    pub pok_c: Vec<u8>,
+    pub pok_s: Vec<u8>,
+    pub ranges: Vec<RangeProofsMade>,
+    pub status: Vec<u8>,
 }
 
 /// What `GpuVerifyingKey::show_commit_batch` returns: the flat arrays of `cg_show_commit_batch`, one row per client state.

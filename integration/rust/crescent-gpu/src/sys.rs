@@ -156,7 +156,8 @@ pub struct cg_witness_report {
     pub reserved: [i32; 7],
 }
 
-/// one range proof of a showing for `cg_verify_showings_batch`: which committed input, and the range key's slot for its bases
+/// one range proof of a showing for `cg_verify_showings_batch` and `cg_create_showings_batch`: which committed input, and the
+/// (verifying or proving) range key's slot for its bases
 #[repr(C)]
 #[derive(Default, Clone, Copy, Debug)]
 pub struct cg_show_range_link {
@@ -176,6 +177,20 @@ pub struct cg_range_rows {
     pub randomizers: *const u8,
     pub pok_c: *const u8,
     pub pok_s: *const u8,
+}
+
+/// one range proof per showing, n rows each, in the layouts `cg_range_prove_batch` writes; `challenges` may be null
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct cg_range_made {
+    pub com_f: *mut u8,
+    pub com_g: *mut u8,
+    pub com_q: *mut u8,
+    pub evals: *mut u8,
+    pub proofs: *mut u8,
+    pub pok_c: *mut u8,
+    pub pok_s: *mut u8,
+    pub challenges: *mut u8,
 }
 
 pub enum cg_ctx {}
@@ -553,6 +568,31 @@ extern "C" {
         part_verdicts: *mut u8,
     ) -> c_int;
     pub fn cg_pvk_set_showings_overlap(k: *mut cg_pvk, on: i32) -> c_int;
+    pub fn cg_create_showings_batch(
+        k: *mut cg_pvk,
+        rk: *mut cg_range_pk,
+        io_types: *const u8,
+        n_io: u64,
+        context: *const u8,
+        context_len: u64,
+        context_stride: u64,
+        proofs: *const u8,
+        inputs: *const u8,
+        rand: *const u8,
+        n_ranges: u32,
+        links: *const cg_show_range_link,
+        shifts: *const u8,
+        range_rand: *const u8,
+        n: u64,
+        rand_proofs: *mut u8,
+        com_hidden: *mut u8,
+        committed: *mut u8,
+        pok_c: *mut u8,
+        pok_s: *mut u8,
+        ranges: *const cg_range_made,
+        status: *mut u8,
+        part_status: *mut u8,
+    ) -> c_int;
     pub fn cg_show_shift_batch(
         k: *mut cg_pvk,
         input_index: u32,
