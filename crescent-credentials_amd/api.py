@@ -169,6 +169,10 @@ class _CgRangeRows(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in ("com_f", "com_g", "com_q", "evals", "proofs", "randomizers", "pok_c", "pok_s")]
 
 
+class _CgDeviceLinkRows(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("com1", "comz", "h_q", "m", "pi0_c", "pi0_s", "pi1_c", "pi1_s")]
+
+
 class _CgRangeMade(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in ("com_f", "com_g", "com_q", "evals", "proofs", "pok_c", "pok_s", "challenges")]
 
@@ -292,6 +296,10 @@ _SIGNATURES = {
                                  + [C.c_uint32, C.POINTER(_CgShowRangeLink), C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
                                  + [C.POINTER(_CgRangeMade), C.c_void_p, C.c_void_p]),
     "cg_show_shift_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_device_link_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(_CgDeviceLinkRows),
+                                              C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_device_link_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cg_revealed_digest_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 
@@ -1841,9 +1849,79 @@ class Groth16:
         return Groth16.dlog_challenge_batch([2] * len(com) + [len(hid) + 1], np.concatenate(bases), k, committed if com else None,
                                             com_hidden, context)
 
+    @staticmethod
+    def device_link_verify_batch_packed(pvk: "PreparedVerifyingKey", io_types, pos0: int, pos1: int, committed, com1, comz, h_q, m, pi0_c,
+                                        pi0_s, pi1_c, pi1_s, h_len: Optional[int] = None):
+        """cg_device_link_verify_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = com1 / 64): the
+        BN254 half of `DeviceProof::verify` (creds/src/device.rs:168-213) for n device-bound showings of one layout.
+        committed is the showing's own n x n_committed x 64 array, as verify_showings_batch_packed takes it; pos0 and pos1 are
+        the input indices of the two device key values.  h_len defaults to len(h_q) / n.  Returns (verdicts n, part_verdicts
+        n x 2 for (pi0, pi1), e_out n x 32: the digest e1_bytes ‖ e2_bytes, zeros on a malformed row)."""
+        io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+        n_com = int((io == CG_IO_COMMITTED).sum())
+        c1 = _u8(com1)
+        if c1.size % 64:
+            raise ValueError("com1 must be n x 64 bytes")
+        n = c1.size // 64
+        hq = _u8(h_q if h_q is not None else b"")
+        if h_len is None:
+            h_len = hq.size // n if n else 0
+        comm, cz, hq = _u8(committed, 64 * n_com * n), _u8(comz, 64 * n), _u8(hq, h_len * n)
+        arrays = [c1, cz, hq, _u8(m, 32 * n), _u8(pi0_c, 32 * n), _u8(pi0_s, 128 * n), _u8(pi1_c, 32 * n), _u8(pi1_s, 96 * n)]
+        ptr = lambda a: _ptr(a) if a.size else None
+        rows = _CgDeviceLinkRows(*[ptr(a) for a in arrays])
+        verdicts, parts, e_out = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 2), np.uint8), np.zeros((max(n, 1), 32), np.uint8)
+        _check(lib().cg_device_link_verify_batch(pvk._h, ptr(io), io.size, int(pos0), int(pos1), ptr(comm), C.byref(rows), int(h_len), n,
+                                                 _ptr(verdicts), _ptr(parts), _ptr(e_out)))
+        return verdicts[:n], parts[:n], e_out[:n]
+
+    @staticmethod
+    def device_link_verify_batch(pvk: "PreparedVerifyingKey", io_types, pos0: int, pos1: int, committed, proofs) -> List[bool]:
+        """The BN254 half of `DeviceProof::verify` for a sequence of DeviceLinkProof, one per showing; committed: per showing
+        the sequence of its 64-byte committed points.  True where pi0 (with its equal-scalar pair) and pi1 verify: the
+        reference's `true` short of pi2.  Every h_Q must have the same length."""
+        proofs = list(proofs)
+        fr = lambda v: int(v).to_bytes(32, "little")
+        join = lambda f: b"".join(f(p) for p in proofs)
+        verdicts, _, _ = Groth16.device_link_verify_batch_packed(
+            pvk, io_types, pos0, pos1, b"".join(bytes(c) for row in committed for c in row), join(lambda p: bytes(p.com1)),
+            join(lambda p: bytes(p.comz)), join(lambda p: bytes(p.h_q)), join(lambda p: fr(p.m)), join(lambda p: fr(p.pi0_c)),
+            join(lambda p: b"".join(fr(x) for si in p.pi0_s for x in si)), join(lambda p: fr(p.pi1_c)),
+            join(lambda p: b"".join(fr(x) for si in p.pi1_s for x in si)), h_len=len(proofs[0].h_q) if proofs else 0)
+        return [bool(v == CG_VERIFY_ACCEPT) for v in verdicts]
+
+    @staticmethod
+    def revealed_digest_batch(items) -> np.ndarray:
+        """cg_revealed_digest_batch (host only, no GPU needed): per item SHA-256 and the digest's first 31 bytes through
+        `bits_to_num` (creds/src/lib.rs:590-603, utils.rs:78-94), the canonical Fr a host places into `revealed`.  items: a
+        sequence of bytes.  Returns n x 32 bytes."""
+        items = [bytes(b) for b in items]
+        offsets = np.zeros(len(items) + 1, np.uint64)
+        offsets[1:] = np.cumsum([len(b) for b in items], dtype=np.uint64)
+        data = _u8(b"".join(items))
+        out = np.zeros((max(len(items), 1), 32), np.uint8)
+        _check(lib().cg_revealed_digest_batch(_ptr(data) if data.size else None, offsets.ctypes.data_as(C.POINTER(C.c_uint64)), len(items),
+                                              _ptr(out)))
+        return out[:len(items)]
+
     @classmethod
     def clear_cache(cls):
         cls._cache.clear()
+
+
+@dataclass
+class DeviceLinkProof:
+    """The BN254 half of a `DeviceProof` (creds/src/device.rs:80-93) as its serialized pieces: com1 and comz 64 B
+    ark-serialize uncompressed G1, h_Q bytes, m an int, and the two DLogPoK as c and the responses s[statement][j] ints
+    (pi0: [[s00, s01], [s10, s11]], pi1: [[t0], [u0, u1]])."""
+    com1: bytes
+    comz: bytes
+    h_q: bytes
+    m: int
+    pi0_c: int
+    pi0_s: List[List[int]]
+    pi1_c: int
+    pi1_s: List[List[int]]
 
 
 class PreparedVerifyingKey(_LatencyMode, _Handle):
@@ -1875,6 +1953,13 @@ class PreparedVerifyingKey(_LatencyMode, _Handle):
         a, b = C.c_float(), C.c_float()
         _check(lib().cg_pvk_last_kernel_ms(self._h, C.byref(a), C.byref(b)))
         return float(a.value), float(b.value)
+
+    def device_link_last_kernel_ms(self) -> Tuple[float, float, float, float]:
+        """HIP-event milliseconds of the four kernels of the last device_link_verify_batch on this key: the digest and
+        scalar stage, the terms, the sums, the two transcripts"""
+        ms = (C.c_float * 4)()
+        _check(lib().cg_device_link_last_kernel_ms(self._h, ms))
+        return tuple(float(x) for x in ms)
 
     @property
     def num_inputs(self) -> int:

@@ -70,9 +70,11 @@
 // writes every point on the device; io_layout parses a call's io_types once, for the verifier's and the creator's shapes
 // alike; and the handle has one set of per-call arrays, named by what they hold.  Shared with the range keys, in
 // key_handle.hpp: the handle's device, stream and lock, an array with its row width (RowBuf), the responses (dlog_respond).
+#include <algorithm>
 #include <memory>
 
 #include "common.hpp"
+#include "device_link.hpp"
 #include "fixed_base.hpp"
 #include "key_handle.hpp"
 #include "pairing.hpp"
@@ -715,6 +717,9 @@ struct cg_pvk : KeyHandle {
     // creating whole showings (cg_create_showings_batch) also: the responses, and per (showing, range) the link's opening and
     // made byte; ped_com is in b_link and the range parts' status bytes come back into b_rverd
     RowBuf b_resp, b_lopen, b_lmade;
+    // the device link (cg_device_link_verify_batch, devicelink.hip): its per-call arrays, which that file creates and names
+    void* dl_state = nullptr;
+    void (*dl_free)(void*) = nullptr;
     void open_second() {
         CG_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_link, &ev_ranges}) CG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -722,6 +727,7 @@ struct cg_pvk : KeyHandle {
     ~cg_pvk() {                            // both streams are waited for before the buffers above are freed (key_handle.hpp)
         if (st2) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); }
         drain();
+        if (dl_state) dl_free(dl_state);
         for (hipEvent_t e : {ev_fork, ev_join, ev_link, ev_ranges}) if (e) (void)hipEventDestroy(e);
     }
 
@@ -898,6 +904,30 @@ int io_layout(const cg_pvk* k, const uint8_t* io_types, uint64_t n_io, IoLayout&
     return io_layout(io_types, n_io, L);
 }
 
+}  // namespace
+
+// ---- the internal entry (device_link.hpp): what cg_device_link_verify_batch needs of a key it cannot see into ----------------
+namespace cg {
+int pvk_link_view(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1, PvkLinkView& v) {
+    IoLayout L;
+    if (int rc = io_layout(k, io_types, n_io, L)) return rc;
+    if (pos0 >= n_io || pos1 >= n_io) return fail(CG_ERR_INVALID_ARGUMENT, "pos0 = %u or pos1 = %u is no input of a key with %llu", pos0, pos1, (unsigned long long)n_io);
+    if (io_types[pos0] != CG_IO_COMMITTED || io_types[pos1] != CG_IO_COMMITTED)
+        return fail(CG_ERR_INVALID_ARGUMENT, "the device key's inputs %u and %u must both be committed inputs of the showing", pos0, pos1);
+    if (pos0 == pos1) return fail(CG_ERR_INVALID_ARGUMENT, "pos0 and pos1 name the same input %u", pos0);
+    auto ci = [&](uint32_t pos) { return (uint32_t)(std::find(L.com.begin(), L.com.end(), pos) - L.com.begin()); };
+    pvk_link_handle(k, v);
+    v.n_com = (uint32_t)L.com.size();
+    v.ci0 = ci(pos0);
+    v.ci1 = ci(pos1);
+    return CG_OK;
+}
+void pvk_link_handle(cg_pvk* k, PvkLinkView& v) {
+    v = PvkLinkView{&k->mu, k->device, k->st, k->tab.p, k->base_bytes.data(), k->n_inputs, 0, 0, 0, &k->dl_state, &k->dl_free};
+}
+}  // namespace cg
+
+namespace {
 // the verifier's shape and tab_of: the revealed inputs, then (with a DLogPoK) the responses
 ShowShape show_shape(const IoLayout& L, bool pok, std::vector<uint32_t>& tab_of) {
     ShowShape sh;

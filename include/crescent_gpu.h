@@ -933,8 +933,9 @@ typedef struct cg_range_rows {
  *           Merlin transcript over the compressed bases, the recomputed k_i and y_i as their bytes stand, compared with
  *           pok_c; ped_com per (showing, range) from the key's tables, written to device memory that the kernels of
  *           cg_range_verify_proofs_batch then read on the range key's stream, ordered behind the link by an event.
- * NOT done here (they are no curve arithmetic): the SHA-256 of revealed preimages (lib.rs:560-605), the freshness test on
- * cur_time (:637-643) and the device proof (ECDSA / Spartan over T-256).
+ * NOT done here: the SHA-256 of revealed preimages (lib.rs:560-605), which cg_revealed_digest_batch computes on the host; the
+ * freshness test on cur_time (:637-643); and the device proof, whose BN254 half cg_device_link_verify_batch verifies on the
+ * same `committed` array and whose Spartan proof over T-256 stays with the host.
  * io_types .. pok_s: as for cg_verify_show_batch; pok_c and pok_s are required.
  * context: the DLogPoK's context string as cg_dlog_challenge_batch takes it: context_len bytes, context_stride = 0 for one
  *          context shared by the batch, otherwise showing i's starts at context + i * context_stride; NULL with length 0 is
@@ -978,7 +979,8 @@ typedef struct cg_range_made { uint8_t *com_f, *com_g, *com_q, *evals, *proofs, 
  *           cg_show_commit_batch, cg_dlog_challenge_batch over the key's bases, cg_show_respond_batch and, per link,
  *           cg_show_shift_batch and cg_range_prove_batch, with every output row byte for byte what that sequence writes for
  *           the same operands - and nothing coming down or going up again in between.
- * NOT done here: drawing randomness (the library draws none), `revealed_preimages`, the device proof.
+ * NOT done here: drawing randomness (the library draws none), `revealed_preimages`, the device proof: `DeviceProof::prove`
+ * runs on a wallet, one proof at a time, and stays on the host (the verifying side has cg_device_link_verify_batch).
  * io_types, proofs, inputs, rand: as for cg_show_commit_batch (rand: cg_show_rand_count scalars per showing, same order).
  * context: as for cg_verify_showings_batch, with the same limits and errors.
  * links:   n_ranges of them, shared by the batch; `slot` is a slot of the PROVING range key rk (cg_range_pk_add_bases).  Two
@@ -1024,6 +1026,64 @@ int cg_create_showings_batch(cg_pvk* k, cg_range_pk* rk, const uint8_t* io_types
  * input_index >= cg_pvk_num_inputs or a null array is CG_ERR_INVALID_ARGUMENT, reported before any HIP call; n = 0 is CG_OK. */
 int cg_show_shift_batch(cg_pvk* k, uint32_t input_index, const uint8_t* openings, const uint8_t* commitments, const uint8_t* shifts,
                         uint64_t n, uint8_t* openings_out, uint8_t* ped_com_out, uint8_t* status);
+
+/* Device-bound showings.  Two of the reference's credential configurations (`mdl1`, `rs256-db`) are "device_bound": after
+ * `ShowGroth16::verify`, `verify_show` and `verify_show_mdl` call `DeviceProof::verify` on every showing.
+ *
+ * One device proof per showing, n rows each. */
+typedef struct cg_device_link_rows {
+    const uint8_t *com1;    /* n x 64 B ark-serialize uncompressed: DeviceProof.com1, the re-committed com1 */
+    const uint8_t *comz;    /* n x 64 B */
+    const uint8_t *h_q;     /* n x h_len bytes; may be NULL with h_len = 0 */
+    const uint8_t *m;       /* n x 32 B canonical Fr */
+    const uint8_t *pi0_c, *pi0_s;   /* n x 32 B;  n x 4 x 32 B: s[0][0], s[0][1], s[1][0], s[1][1] */
+    const uint8_t *pi1_c, *pi1_s;   /* n x 32 B;  n x 3 x 32 B: s[0][0], s[1][0], s[1][1] */
+} cg_device_link_rows;
+/* Replaces: the BN254 half of `DeviceProof::verify` (creds/src/device.rs:168-213), as `verify_show` and `verify_show_mdl` call
+ *           it per showing (creds/src/lib.rs:660-680, :893-913), for n showings of one layout in ONE call: pi0 - a DLogPoK
+ *           with the equal-scalar pair (0, 0) about com1_orig and the re-committed com1 -, the SHA-256 challenge (e1, e2)
+ *           over the text forms of pi0.c, com0, com1 and comz and over h_Q, the recombination
+ *           lhs1 = com0 + e1 com1 + e2 comz - m g, and pi1 about lhs1 and comz, both with their Merlin transcripts.  Per
+ *           chunk of showings everything runs on the device and nothing comes down between the steps.
+ * NOT done here: pi2, the Spartan proof over T-256 (`ECDSAProof::verify`, device.rs:215-216).  The host passes m and e_out on
+ * to it; a showing is the reference's `true` where this call answers CG_VERIFY_ACCEPT and pi2 verifies (INTEGRATION.md,
+ * "Device-bound showings").
+ * UNVERIFIED text forms: the digest is taken over `to_string()` of arkworks 0.4 values - a field element as its decimal digits
+ * with no leading zero, ZERO AS THE EMPTY STRING; a point as "infinity" or "(x, y)".  arkworks is not available to this
+ * project and the reference pins no such string, so these rules are restated from the 0.4 sources and hold until an
+ * arkworks-made DeviceProof meets this code; each is one function of csrc/device_link.hpp.
+ * io_types: as for cg_verify_show_batch.  pos0, pos1: the input indices of `device_key_0_value` and `device_key_1_value`, as
+ *           cg_show_shift_batch's input_index; g = gamma_abc_g1[pos0 + 1], g' = gamma_abc_g1[pos1 + 1], h = delta_g1.
+ * committed: the showing's own n x n_committed x 64 B array, exactly as cg_verify_showings_batch takes it: com0 and com1_orig
+ *           are read from it at the committed indices of pos0 and pos1, so they cannot fall out of step with the showing.
+ * h_len:    bytes of h_Q per row, at most 64 (`compute_hQ` returns the 32 bytes of a P-256 field element).
+ * verdicts: n x CG_VERIFY_*.  ACCEPT: pi0's recomputed challenge equals pi0_c, pi0_s[0] == pi0_s[2], and pi1's recomputed
+ *           challenge equals pi1_c.  MALFORMED (that row only, its e_out bytes zero, its parts MALFORMED): com0, com1_orig,
+ *           com1 or comz fails ark's checked G1 deserialisation, or m, a challenge or a response is >= r.  A point at
+ *           infinity is legal.  Else REJECT.  A bad row leaves its neighbours untouched.
+ * part_verdicts: n x 2 for (pi0, pi1), may be NULL.
+ * e_out:    n x 32 B: the digest, e1_bytes ‖ e2_bytes, written for every row that is not MALFORMED, accepted or not.
+ * Errors, all reported before any HIP call and with no output touched: a null array; n_io != cg_pvk_num_inputs
+ * (CG_ERR_MALFORMED_KEY); an io byte above 2; pos0 or pos1 out of range, not CG_IO_COMMITTED, or equal; h_len above 64.
+ * n = 0 is CG_OK.  There is no pairing here, so the latency mode of the handle has no bearing.  The call runs on the key's
+ * stream under its lock, beside nothing: it may follow cg_verify_showings_batch on the same handle at once.
+ * Measured on an MI355X in the mDL-like layout with h_Q of 32 bytes (profiles/device_link.md): 7.6 ms for one proof, 7.1 ms for
+ * 1024 and 10.8 ms for 16384 (1.5 M proofs/s), an eighth of what cg_verify_showings_batch takes at that size; the chains are
+ * 85 % of it. */
+int cg_device_link_verify_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1,
+                                const uint8_t* committed, const cg_device_link_rows* rows, uint32_t h_len, uint64_t n,
+                                uint8_t* verdicts, uint8_t* part_verdicts, uint8_t* e_out);
+/* Diagnostic: what the four kernels of the handle's last cg_device_link_verify_batch took, by HIP events, summed over its
+ * chunks: the digest and scalar stage, the terms, the sums, the two transcripts.  Zeros before the first such call.
+ * (No counterpart in the reference.) */
+int cg_device_link_last_kernel_ms(cg_pvk* k, float ms[4]);
+/* Replaces: the digests of `revealed_preimages` that `verify_show` places among the public inputs (creds/src/lib.rs:590-603):
+ *           per hashed attribute SHA-256 of the preimage string and its first 31 bytes through `bits_to_num`
+ *           (creds/src/utils.rs:78-94), as the canonical Fr a host places into `revealed`.  Host only, on the library's worker
+ *           threads: no handle, no HIP call, usable in a process without a GPU.
+ * Item i is data[offsets[i] .. offsets[i+1]); offsets has n_items + 1 entries, ascending; an item has fewer than 2^32 bytes.
+ * out: n_items x 32 B, little-endian: byte j < 31 is digest byte j with its bits mirrored, byte 31 is zero. */
+int cg_revealed_digest_batch(const uint8_t* data, const uint64_t* offsets, uint64_t n_items, uint8_t* out);
 
 /* Replaces: `prepare_verifying_key` (forks/groth16/src/verifier.rs:13-20), on the host (one pairing).
  * vk_bytes: one VerifyingKey as ark-serialize writes it (the fork's layout, delta_g1 included); pvk_out receives the

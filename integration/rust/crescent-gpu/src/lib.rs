@@ -901,6 +901,45 @@ impl GpuVerifyingKey {
         Ok((out, ped, status))
     }
 
+    /// The BN254 half of `DeviceProof::verify` (creds/src/device.rs:168-213; called from creds/src/lib.rs:660-680, :893-913) for
+    /// n device-bound showings of one layout in one call (`cg_device_link_verify_batch`): pi0 with its equal-scalar pair, the
+    /// SHA-256 challenge over the commitments' text forms, the recombination and pi1.  `committed` is the showing's own
+    /// n x n_committed x 64 B array, as `verify_showings_batch` takes it; `pos0` and `pos1` are the input indices of
+    /// `device_key_0_value` and `device_key_1_value`; every array of `rows` holds n rows in the header's layout and every h_Q
+    /// has `h_len` bytes.  Returns (verdicts n x CG_VERIFY_*, part verdicts n x 2, e n x 32 B: e1_bytes ‖ e2_bytes, which the
+    /// host passes on to `ECDSAProof::verify` with m).  pi2 stays with the host.
+    pub fn device_link_verify_batch(&self, io_types: &[u8], pos0: u32, pos1: u32, committed: &[u8], rows: &DeviceLinkRows, h_len: u32) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = rows.com1.len() / 64;
+        let n_com = io_types.iter().filter(|&&t| t == 2).count();
+        if rows.com1.len() != n * 64 || rows.comz.len() != n * 64 || rows.h_q.len() != n * h_len as usize || rows.m.len() != n * 32 || rows.pi0_c.len() != n * 32
+            || rows.pi0_s.len() != n * 128 || rows.pi1_c.len() != n * 32 || rows.pi1_s.len() != n * 96 || committed.len() != n * n_com * 64
+        {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let c_rows = sys::cg_device_link_rows { com1: rows.com1.as_ptr(), comz: rows.comz.as_ptr(), h_q: rows.h_q.as_ptr(), m: rows.m.as_ptr(),
+                                                pi0_c: rows.pi0_c.as_ptr(), pi0_s: rows.pi0_s.as_ptr(), pi1_c: rows.pi1_c.as_ptr(), pi1_s: rows.pi1_s.as_ptr() };
+        let (mut verdicts, mut parts, mut e) = (vec![0u8; n], vec![0u8; n * 2], vec![0u8; n * 32]);
+        let rc = unsafe {
+            sys::cg_device_link_verify_batch(self.h, io_types.as_ptr(), io_types.len() as u64, pos0, pos1, committed.as_ptr(), &c_rows, h_len, n as u64,
+                                             verdicts.as_mut_ptr(), parts.as_mut_ptr(), e.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((verdicts, parts, e))
+    }
+
+    /// HIP-event milliseconds of the four kernels of the last `device_link_verify_batch` on this key
+    /// (`cg_device_link_last_kernel_ms`): the digest and scalar stage, the terms, the sums, the two transcripts.
+    pub fn device_link_last_kernel_ms(&self) -> Result<[f32; 4], SynthesisError> {
+        let mut ms = [0f32; 4];
+        let rc = unsafe { sys::cg_device_link_last_kernel_ms(self.h, ms.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(ms)
+    }
+
     /// `create_show_proof`'s `show_groth16` and `show_range` steps (creds/src/lib.rs:364-373, :468-471, :505-509) for `n`
     /// client states of one proof spec in one call (`cg_create_showings_batch`): the re-randomised proof, the commitments,
     /// `DLogPoK::prove` whole with its Merlin transcript over `context`, and per link the shift by `shifts` and
@@ -1291,6 +1330,36 @@ pub fn dlog_challenge_batch(context: Option<&[u8]>, n_bases: &[u32], bases: &[u8
         return Err(map_err(rc));
     }
     Ok(c)
+}
+
+/// The rows of `device_link_verify_batch`, n each, in the layouts of `cg_device_link_rows`
+pub struct DeviceLinkRows {
+    pub com1: Vec<u8>,
+    pub comz: Vec<u8>,
+    pub h_q: Vec<u8>,
+    pub m: Vec<u8>,
+    pub pi0_c: Vec<u8>,
+    pub pi0_s: Vec<u8>,
+    pub pi1_c: Vec<u8>,
+    pub pi1_s: Vec<u8>,
+}
+
+/// The digests of `revealed_preimages` as `verify_show` places them among the public inputs (creds/src/lib.rs:590-603): per item
+/// SHA-256 and the digest's first 31 bytes through `bits_to_num` (`cg_revealed_digest_batch`, host only).  Returns n x 32 B
+/// canonical scalars.
+pub fn revealed_digest_batch(items: &[&[u8]]) -> Result<Vec<u8>, SynthesisError> {
+    let mut offsets = vec![0u64; items.len() + 1];
+    let mut data = Vec::new();
+    for (i, b) in items.iter().enumerate() {
+        data.extend_from_slice(b);
+        offsets[i + 1] = data.len() as u64;
+    }
+    let mut out = vec![0u8; items.len() * 32];
+    let rc = unsafe { sys::cg_revealed_digest_batch(if data.is_empty() { std::ptr::null() } else { data.as_ptr() }, offsets.as_ptr(), items.len() as u64, out.as_mut_ptr()) };
+    if rc != 0 {
+        return Err(map_err(rc));
+    }
+    Ok(out)
 }
 
 impl Drop for GpuRangeKey {

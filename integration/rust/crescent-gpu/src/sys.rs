@@ -179,6 +179,20 @@ pub struct cg_range_rows {
     pub pok_s: *const u8,
 }
 
+/// one device proof per showing, n rows each (`cg_device_link_verify_batch`); `h_q` may be null with `h_len` 0
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct cg_device_link_rows {
+    pub com1: *const u8,
+    pub comz: *const u8,
+    pub h_q: *const u8,
+    pub m: *const u8,
+    pub pi0_c: *const u8,
+    pub pi0_s: *const u8,
+    pub pi1_c: *const u8,
+    pub pi1_s: *const u8,
+}
+
 /// one range proof per showing, n rows each, in the layouts `cg_range_prove_batch` writes; `challenges` may be null
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -604,4 +618,20 @@ extern "C" {
         ped_com_out: *mut u8,
         status: *mut u8,
     ) -> c_int;
+    pub fn cg_device_link_verify_batch(
+        k: *mut cg_pvk,
+        io_types: *const u8,
+        n_io: u64,
+        pos0: u32,
+        pos1: u32,
+        committed: *const u8,
+        rows: *const cg_device_link_rows,
+        h_len: u32,
+        n: u64,
+        verdicts: *mut u8,
+        part_verdicts: *mut u8,
+        e_out: *mut u8,
+    ) -> c_int;
+    pub fn cg_device_link_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32) -> c_int;
+    pub fn cg_revealed_digest_batch(data: *const u8, offsets: *const u64, n_items: u64, out: *mut u8) -> c_int;
 }
