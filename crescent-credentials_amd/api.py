@@ -35,6 +35,7 @@ CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
 CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED = 0, 1, 2      # PublicIOType, creds/src/structs.rs:33-37
 CG_SHOW_MADE, CG_SHOW_MALFORMED = 1, 2
 CG_RANGE_N_RAND, CG_RANGE_N_RESP = 18, 6
+CG_DEVICE_LINK_N_RAND = 9
 
 
 class CrescentGpuError(RuntimeError):
@@ -173,6 +174,10 @@ class _CgDeviceLinkRows(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in ("com1", "comz", "h_q", "m", "pi0_c", "pi0_s", "pi1_c", "pi1_s")]
 
 
+class _CgDeviceLinkMade(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("com1", "comz", "m", "pi0_c", "pi0_s", "pi1_c", "pi1_s")]
+
+
 class _CgRangeMade(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in ("com_f", "com_g", "com_q", "evals", "proofs", "pok_c", "pok_s", "challenges")]
 
@@ -299,6 +304,9 @@ _SIGNATURES = {
     "cg_device_link_verify_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(_CgDeviceLinkRows),
                                               C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_device_link_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cg_device_link_prove_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(_CgDeviceLinkMade), C.c_void_p, C.c_void_p]),
+    "cg_device_link_prove_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "cg_revealed_digest_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
@@ -1891,6 +1899,82 @@ class Groth16:
         return [bool(v == CG_VERIFY_ACCEPT) for v in verdicts]
 
     @staticmethod
+    def device_link_prove_batch_packed(pvk: "PreparedVerifyingKey", io_types, pos0: int, pos1: int, committed, openings, rand, h_q,
+                                       h_len: Optional[int] = None):
+        """cg_device_link_prove_batch on flat byte arrays laid out as include/crescent_gpu.h states (n = openings / 128): the
+        BN254 half of `DeviceProof::prove` (creds/src/device.rs:104-160) for n device-bound showings of one layout.
+        committed is the showing's own n x n_committed x 64 array, as create_showings_batch_packed returns it; openings: n x
+        (q0, r0, q1, r1_orig); rand: n x 9 scalars (z, t_z, r1, a, b, d, n0, n1, n2); h_len defaults to len(h_q) / n.
+        Returns (com1 n x 64, comz n x 64, m n x 32, pi0_c n x 32, pi0_s n x 4 x 32, pi1_c n x 32, pi1_s n x 3 x 32, e_out n x
+        32: the digest e1_bytes ‖ e2_bytes, status n) as uint8 arrays; a CG_SHOW_MALFORMED row is zero bytes throughout."""
+        io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+        n_com = int((io == CG_IO_COMMITTED).sum())
+        ob = _u8(openings)
+        if ob.size % 128:
+            raise ValueError("openings must be n x 128 bytes (q0, r0, q1, r1_orig)")
+        n = ob.size // 128
+        hq = _u8(h_q if h_q is not None else b"")
+        if h_len is None:
+            h_len = hq.size // n if n else 0
+        comm, rb, hq = _u8(committed, 64 * n_com * n), _u8(rand, 32 * CG_DEVICE_LINK_N_RAND * n), _u8(hq, h_len * n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        rows = [np.zeros((m,) + sh, np.uint8) for sh in ((64,), (64,), (32,), (32,), (4, 32), (32,), (3, 32))]
+        e_out, status = np.zeros((m, 32), np.uint8), np.zeros(m, np.uint8)
+        made = _CgDeviceLinkMade(*[_ptr(a) for a in rows])
+        _check(lib().cg_device_link_prove_batch(pvk._h, ptr(io), io.size, int(pos0), int(pos1), ptr(comm), ptr(ob), ptr(rb), ptr(hq),
+                                                int(h_len), n, C.byref(made), _ptr(e_out), _ptr(status)))
+        return tuple(a[:n] for a in rows) + (e_out[:n], status[:n])
+
+    @staticmethod
+    def device_link_prove_batch(pvk: "PreparedVerifyingKey", io_types, pos0: int, pos1: int, committed, openings, h_qs, rand=None):
+        """The BN254 half of `DeviceProof::prove` for n showings: committed: per showing the sequence of its 64-byte committed
+        points; openings: per showing (q0, r0, q1, r1_orig) ints; h_qs: per showing the bytes `compute_hQ` returned, all of
+        one length; rand: per showing the nine scalars in the header's order - None draws them with `secrets.randbelow`, but
+        a host that goes on to `ECDSAProof::prove` needs its z and draws them itself.  Returns (proofs, digests): per showing
+        a DeviceLinkProof, which device_link_verify_batch takes as it is, or None for a showing that was not made; and the n x
+        32 digests e1_bytes ‖ e2_bytes (zeros for such a showing)."""
+        openings, h_qs = list(openings), [bytes(h) for h in h_qs]
+        n = len(openings)
+        if n == 0:
+            return [], np.zeros((0, 32), np.uint8)
+        if rand is None:
+            import secrets
+            rand = [[secrets.randbelow(FR_MODULUS) for _ in range(CG_DEVICE_LINK_N_RAND)] for _ in range(n)]
+        fr = lambda v: int(v).to_bytes(32, "little")
+        com1, comz, m, c0, s0, c1, s1, e, status = Groth16.device_link_prove_batch_packed(
+            pvk, io_types, pos0, pos1, b"".join(bytes(c) for row in committed for c in row), b"".join(fr(v) for row in openings for v in row),
+            b"".join(fr(v) for row in rand for v in row), b"".join(h_qs), h_len=len(h_qs[0]))
+        val = lambda a: int.from_bytes(a.tobytes(), "little")
+        out = []
+        for i in range(n):
+            if status[i] != CG_SHOW_MADE:
+                out.append(None)
+                continue
+            out.append(DeviceLinkProof(com1[i].tobytes(), comz[i].tobytes(), h_qs[i], val(m[i]), val(c0[i]),
+                                       [[val(s0[i, 0]), val(s0[i, 1])], [val(s0[i, 2]), val(s0[i, 3])]], val(c1[i]),
+                                       [[val(s1[i, 0])], [val(s1[i, 1]), val(s1[i, 2])]]))
+        return out, e
+
+    @staticmethod
+    def device_link_openings(io_types, pos0: int, pos1: int, inputs, rand) -> np.ndarray:
+        """The openings (q0, r0, q1, r1_orig) of the two device key values, cut out of the arrays create_showings_batch_packed
+        took: per showing m = inputs[pos] and r = rand[2 + committed_index] (`committed_input_openings` of
+        groth16rand.rs:135-139).  inputs: n x n_io x 32 B; rand: n x show_rand_count x 32 B.  Returns n x 4 x 32 bytes, the
+        layout device_link_prove_batch_packed takes."""
+        io = [int(t) for t in io_types]
+        com = [i for i, t in enumerate(io) if t == CG_IO_COMMITTED]
+        if pos0 not in com or pos1 not in com:
+            raise ValueError("pos0 and pos1 must be committed inputs")
+        n_rand = show_rand_count(io)
+        ib = _u8(inputs)
+        if not io or ib.size % (32 * len(io)):
+            raise ValueError("inputs must be n x n_io x 32 bytes")
+        n = ib.size // (32 * len(io))
+        ib, rb = ib.reshape(n, len(io), 32), _u8(rand, 32 * n_rand * n).reshape(n, n_rand, 32)
+        return np.stack([ib[:, pos0], rb[:, 2 + com.index(pos0)], ib[:, pos1], rb[:, 2 + com.index(pos1)]], axis=1).copy()
+
+    @staticmethod
     def revealed_digest_batch(items) -> np.ndarray:
         """cg_revealed_digest_batch (host only, no GPU needed): per item SHA-256 and the digest's first 31 bytes through
         `bits_to_num` (creds/src/lib.rs:590-603, utils.rs:78-94), the canonical Fr a host places into `revealed`.  items: a
@@ -1959,6 +2043,13 @@ class PreparedVerifyingKey(_LatencyMode, _Handle):
         scalar stage, the terms, the sums, the two transcripts"""
         ms = (C.c_float * 4)()
         _check(lib().cg_device_link_last_kernel_ms(self._h, ms))
+        return tuple(float(x) for x in ms)
+
+    def device_link_prove_last_kernel_ms(self) -> Tuple[float, ...]:
+        """HIP-event milliseconds of the six kernels of the last device_link_prove_batch on this key: the checks, the walks,
+        the sums, pi0 with the digest, lhs1, pi1"""
+        ms = (C.c_float * 6)()
+        _check(lib().cg_device_link_prove_last_kernel_ms(self._h, ms))
         return tuple(float(x) for x in ms)
 
     @property

@@ -14,6 +14,8 @@
 //     of c1·lhs1 = c1·com0 + (c1 e1)·proof.com1 + (c1 e2)·comz - (c1 m)·g, so that every chain of a proof starts at once
 //     (csrc/devicelink.hip has the terms).  Merging scalars does not change the group elements.
 #pragma once
+#include <string.h>
+
 #include "sha256.hpp"
 #include "show_link.hpp"
 
@@ -172,6 +174,24 @@ CG_HD uint32_t dl_scalars(const DlIn& in, uint32_t* out, uint64_t stride) {
     return eq ? DL_EQ_POS : 0u;
 }
 
+// ---- what the two transcripts absorb besides a proof's own points -------------------------------------------------------------
+// The two contexts (2 x DL_CTX_LEN bytes), then the bases g', h, g, h compressed (4 x 32): pi0 absorbs all four, pi1 the last
+// three.  base_bytes: gamma_abc_g1[1..] and then delta_g1 as the key's bytes hold them, 64 B each (n_io + 1 points).  Host only;
+// the verifying and the creating call write the same bytes.
+constexpr uint32_t DL_CTX_LEN = 42;
+constexpr uint32_t DL_CONSTS_LEN = 2 * DL_CTX_LEN + 4 * 32;
+inline void dl_link_consts(const uint8_t* base_bytes, uint64_t n_io, uint32_t pos0, uint32_t pos1, uint8_t consts[DL_CONSTS_LEN]) {
+    memcpy(consts, "creating sigma proof pi0 for linking proof", DL_CTX_LEN);
+    memcpy(consts + DL_CTX_LEN, "creating sigma proof pi1 for linking proof", DL_CTX_LEN);
+    const uint64_t base_of[4] = {pos1, n_io, pos0, n_io};
+    for (int i = 0; i < 4; ++i) {
+        uint32_t w[16], c[8];
+        memcpy(w, base_bytes + 64 * base_of[i], 64);
+        ml_compress_g1(w, c);
+        memcpy(consts + 2 * DL_CTX_LEN + 32 * i, c, 32);
+    }
+}
+
 }  // namespace cg
 
 #ifdef __HIPCC__
@@ -191,9 +211,12 @@ struct PvkLinkView {
     uint64_t n_io;
     uint32_t n_com, ci0, ci1;      // committed inputs of the layout; the committed indices of pos0 and pos1
     // the per-call arrays of the device link: created by the first call, under the lock, and freed with the handle after its
-    // streams have been waited for
+    // streams have been waited for.  The verifying call (devicelink.hip) and the creating call (devicelinkmake.hip) have a
+    // slot each, so that calls of both kinds on one handle do not evict each other.
     void** state;
     void (**state_free)(void*);
+    void** make_state;
+    void (**make_state_free)(void*);
 };
 // what needs no layout: everything but n_com, ci0 and ci1
 void pvk_link_handle(cg_pvk* k, PvkLinkView& v);

@@ -39,7 +39,6 @@ namespace {
 constexpr uint64_t DLCHUNK = 1u << 15;     // proofs per launch set; 3 KB of device memory per proof
 constexpr int DLBLOCK = 64;
 constexpr int DL_LANE_LDS = SHA_BLOCK + DL_DIGITS_ROOM;      // 148 bytes = 37 words per lane: an odd stride, no bank shared
-constexpr uint32_t DL_CTX_LEN = 42;
 
 // one chunk's arrays on the device, as the caller laid them out
 struct DlArgs {
@@ -242,16 +241,8 @@ extern "C" int cg_device_link_verify_batch(cg_pvk* k, const uint8_t* io_types, u
         grow(s.b_scal, chunk * 8 * DL_N_SCALARS);
         grow(s.b_part, chunk * (uint64_t)(DL_N_FIXED + DL_N_VAR));
         // the contexts and the compressed bases of this call's pos0 and pos1
-        uint8_t consts[2 * DL_CTX_LEN + 4 * 32];
-        memcpy(consts, "creating sigma proof pi0 for linking proof", DL_CTX_LEN);
-        memcpy(consts + DL_CTX_LEN, "creating sigma proof pi1 for linking proof", DL_CTX_LEN);
-        const uint64_t base_of[4] = {pos1, v.n_io, pos0, v.n_io};
-        for (int i = 0; i < 4; ++i) {
-            uint32_t w[16], c[8];
-            memcpy(w, v.base_bytes + 64 * base_of[i], 64);
-            ml_compress_g1(w, c);
-            memcpy(consts + 2 * DL_CTX_LEN + 32 * i, c, 32);
-        }
+        uint8_t consts[DL_CONSTS_LEN];
+        dl_link_consts(v.base_bytes, v.n_io, pos0, pos1, consts);
         grow(s.consts, sizeof(consts));
         h2d_sync(s.consts.p, consts, sizeof(consts), v.st);
         const uint64_t tab_stride = (uint64_t)FB_NWIN * FB_WIN;

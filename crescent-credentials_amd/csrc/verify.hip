@@ -720,6 +720,9 @@ struct cg_pvk : KeyHandle {
     // the device link (cg_device_link_verify_batch, devicelink.hip): its per-call arrays, which that file creates and names
     void* dl_state = nullptr;
     void (*dl_free)(void*) = nullptr;
+    // and those of cg_device_link_prove_batch (devicelinkmake.hip)
+    void* dlm_state = nullptr;
+    void (*dlm_free)(void*) = nullptr;
     void open_second() {
         CG_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_link, &ev_ranges}) CG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -728,6 +731,7 @@ struct cg_pvk : KeyHandle {
         if (st2) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); }
         drain();
         if (dl_state) dl_free(dl_state);
+        if (dlm_state) dlm_free(dlm_state);
         for (hipEvent_t e : {ev_fork, ev_join, ev_link, ev_ranges}) if (e) (void)hipEventDestroy(e);
     }
 
@@ -923,7 +927,8 @@ int pvk_link_view(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t po
     return CG_OK;
 }
 void pvk_link_handle(cg_pvk* k, PvkLinkView& v) {
-    v = PvkLinkView{&k->mu, k->device, k->st, k->tab.p, k->base_bytes.data(), k->n_inputs, 0, 0, 0, &k->dl_state, &k->dl_free};
+    v = PvkLinkView{&k->mu, k->device, k->st, k->tab.p, k->base_bytes.data(), k->n_inputs, 0, 0, 0, &k->dl_state, &k->dl_free,
+                    &k->dlm_state, &k->dlm_free};
 }
 }  // namespace cg
 

@@ -979,8 +979,8 @@ typedef struct cg_range_made { uint8_t *com_f, *com_g, *com_q, *evals, *proofs, 
  *           cg_show_commit_batch, cg_dlog_challenge_batch over the key's bases, cg_show_respond_batch and, per link,
  *           cg_show_shift_batch and cg_range_prove_batch, with every output row byte for byte what that sequence writes for
  *           the same operands - and nothing coming down or going up again in between.
- * NOT done here: drawing randomness (the library draws none), `revealed_preimages`, the device proof: `DeviceProof::prove`
- * runs on a wallet, one proof at a time, and stays on the host (the verifying side has cg_device_link_verify_batch).
+ * NOT done here: drawing randomness (the library draws none), `revealed_preimages`, and the device proof, whose BN254 half
+ * cg_device_link_prove_batch makes from this call's `committed` in a call of its own (cg_device_link_verify_batch verifies it).
  * io_types, proofs, inputs, rand: as for cg_show_commit_batch (rand: cg_show_rand_count scalars per showing, same order).
  * context: as for cg_verify_showings_batch, with the same limits and errors.
  * links:   n_ranges of them, shared by the batch; `slot` is a slot of the PROVING range key rk (cg_range_pk_add_bases).  Two
@@ -1077,6 +1077,51 @@ int cg_device_link_verify_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_i
  * chunks: the digest and scalar stage, the terms, the sums, the two transcripts.  Zeros before the first such call.
  * (No counterpart in the reference.) */
 int cg_device_link_last_kernel_ms(cg_pvk* k, float ms[4]);
+/* The scalars a device proof draws, in the reference's drawing order (device.rs:104-160): z, t_z (comz = z g + t_z h); r1 (the
+ * re-committed com1 = q1 g + r1 h); a, b, d (pi0's nonces: r[0] = [a, b], r[1] = [a, d], the equal-scalar pair (0, 0) applied);
+ * n0, n1, n2 (pi1's: r[0] = [n0], r[1] = [n1, n2]). */
+#define CG_DEVICE_LINK_N_RAND 9
+/* One device proof per showing, n rows each, in exactly the layouts cg_device_link_rows takes: com1, comz n x 64 B
+ * ark-serialize uncompressed; m n x 32 B; pi0_c n x 32 B; pi0_s n x 4 x 32 B; pi1_c n x 32 B; pi1_s n x 3 x 32 B. */
+typedef struct cg_device_link_made { uint8_t *com1, *comz, *m, *pi0_c, *pi0_s, *pi1_c, *pi1_s; } cg_device_link_made;
+/* Replaces: the BN254 half of `DeviceProof::prove` (creds/src/device.rs:104-160) for n showings of one layout in ONE call: comz
+ *           and the re-committed com1, pi0 with its Merlin transcript and responses, the SHA-256 challenge (e1, e2), the
+ *           recombination m = q0 + q1 e1 + z e2 and r = r0 + r1 e1 + t_z e2, lhs1 and pi1.  The prover knows every discrete
+ *           logarithm, so each group element is a sum of walks through the key's fixed-base tables of g, g' and h - lhs1 is the
+ *           one walk r h - and a proof has no variable-base chain.  Per chunk of showings everything runs on the device and
+ *           nothing comes down between the steps.
+ * NOT done here: `compute_hQ`, which is Poseidon over P-256's base field, and pi2 (`ECDSAProof::prove`); the library draws no
+ * randomness.  The host computes h_Q first, and afterwards hands m, e_out and its own z to `ECDSAProof::prove` (INTEGRATION.md,
+ * "Creating device proofs").
+ * UNVERIFIED text forms: as for cg_device_link_verify_batch; both calls take the digest from the same function of
+ * csrc/device_link.hpp.
+ * io_types, n_io, pos0, pos1, committed, h_q, h_len: exactly as for cg_device_link_verify_batch.  com0 and com1_orig are read
+ *           from the showing's own `committed` array at the committed indices of pos0 and pos1.
+ * openings: n x 4 x 32 B canonical Fr: q0, r0, q1, r1_orig - `committed_input_openings[1]` and `[2]` of lib.rs:378-379.  For a
+ *           showing made by cg_create_showings_batch, m = inputs[pos] and r = rand[2 + committed_index] of that call.
+ * rand:     n x CG_DEVICE_LINK_N_RAND x 32 B canonical Fr, in the order above.
+ * out:      the proof's rows.  The caller passes h_q itself on to the verifier.
+ * e_out:    n x 32 B: the digest, e1_bytes ‖ e2_bytes.
+ * status:   n x CG_SHOW_MADE / CG_SHOW_MALFORMED.  MALFORMED means that row only: every output row of it, e_out included, is
+ *           zero bytes, and its neighbours are untouched.  A row is malformed when an opening or rand scalar is >= r, when com0
+ *           or com1_orig fails ark's checked G1 deserialisation, or when an opening does not open its committed point
+ *           (q0 g + r0 h != com0, or q1 g' + r1_orig h != com1_orig; O against the infinity flag counts as equal).  The last
+ *           is the library's fail-closed reading of the reference's `assert!(lhs1 == h * r)` (device.rs:153-154), which
+ *           panics on a wrong opening of com0; it is extended to com1_orig, where the reference would silently emit a proof
+ *           that does not verify.  Zero scalars and points at infinity are legal everywhere: z = t_z = 0 gives comz = O.
+ * Errors, all reported before any HIP call and with no output touched: a null array or a null member of `out` (h_q may be NULL
+ * only with h_len = 0); n_io != cg_pvk_num_inputs (CG_ERR_MALFORMED_KEY); an io byte above 2; pos0 or pos1 out of range, not
+ * CG_IO_COMMITTED, or equal; h_len above 64.  n = 0 is CG_OK.  The call runs on the key's stream under its lock; it has
+ * per-call arrays of its own, so it and cg_device_link_verify_batch do not evict each other on one handle.
+ * Measured on an MI355X: profiles/device_link_create.md. */
+int cg_device_link_prove_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1,
+                               const uint8_t* committed, const uint8_t* openings, const uint8_t* rand,
+                               const uint8_t* h_q, uint32_t h_len, uint64_t n,
+                               const cg_device_link_made* out, uint8_t* e_out, uint8_t* status);
+/* Diagnostic: what the six kernels of the handle's last cg_device_link_prove_batch took, by HIP events, summed over its
+ * chunks: the checks, the fifteen walks, the sums, pi0 with the digest, lhs1, pi1.  Zeros before the first such call.
+ * (No counterpart in the reference.) */
+int cg_device_link_prove_last_kernel_ms(cg_pvk* k, float ms[6]);
 /* Replaces: the digests of `revealed_preimages` that `verify_show` places among the public inputs (creds/src/lib.rs:590-603):
  *           per hashed attribute SHA-256 of the preimage string and its first 31 bytes through `bits_to_num`
  *           (creds/src/utils.rs:78-94), as the canonical Fr a host places into `revealed`.  Host only, on the library's worker

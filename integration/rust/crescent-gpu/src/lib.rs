@@ -940,6 +940,45 @@ impl GpuVerifyingKey {
         Ok(ms)
     }
 
+    /// The BN254 half of `DeviceProof::prove` (creds/src/device.rs:104-160) for n device-bound showings of one layout in one
+    /// call (`cg_device_link_prove_batch`), short of `compute_hQ` and of pi2: comz, the re-committed com1, pi0, the SHA-256
+    /// challenge, m, lhs1 and pi1.  `committed` is the showing's own n x n_committed x 64 B array, as `create_showings_batch`
+    /// returned it; `openings` holds n x (q0, r0, q1, r1_orig) and `rand` n x `CG_DEVICE_LINK_N_RAND` canonical scalars in the
+    /// header's order; `h_q` n x `h_len` bytes.  Returns (the rows, with the caller's h_q, as `device_link_verify_batch` takes
+    /// them; e n x 32 B: e1_bytes ‖ e2_bytes, which the host hands to `ECDSAProof::prove` with m and its own z; status n x
+    /// CG_SHOW_MADE / CG_SHOW_MALFORMED, a malformed row being zero bytes throughout).
+    pub fn device_link_prove_batch(&self, io_types: &[u8], pos0: u32, pos1: u32, committed: &[u8], openings: &[u8], rand: &[u8], h_q: &[u8], h_len: u32) -> Result<(DeviceLinkRows, Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = openings.len() / 128;
+        let n_com = io_types.iter().filter(|&&t| t == 2).count();
+        if openings.len() != n * 128 || rand.len() != n * 32 * sys::CG_DEVICE_LINK_N_RAND || h_q.len() != n * h_len as usize || committed.len() != n * n_com * 64 {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let mut rows = DeviceLinkRows { com1: vec![0u8; n * 64], comz: vec![0u8; n * 64], h_q: h_q.to_vec(), m: vec![0u8; n * 32], pi0_c: vec![0u8; n * 32],
+                                        pi0_s: vec![0u8; n * 128], pi1_c: vec![0u8; n * 32], pi1_s: vec![0u8; n * 96] };
+        let made = sys::cg_device_link_made { com1: rows.com1.as_mut_ptr(), comz: rows.comz.as_mut_ptr(), m: rows.m.as_mut_ptr(), pi0_c: rows.pi0_c.as_mut_ptr(),
+                                              pi0_s: rows.pi0_s.as_mut_ptr(), pi1_c: rows.pi1_c.as_mut_ptr(), pi1_s: rows.pi1_s.as_mut_ptr() };
+        let (mut e, mut status) = (vec![0u8; n * 32], vec![0u8; n]);
+        let rc = unsafe {
+            sys::cg_device_link_prove_batch(self.h, io_types.as_ptr(), io_types.len() as u64, pos0, pos1, committed.as_ptr(), openings.as_ptr(), rand.as_ptr(),
+                                            h_q.as_ptr(), h_len, n as u64, &made, e.as_mut_ptr(), status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((rows, e, status))
+    }
+
+    /// HIP-event milliseconds of the six kernels of the last `device_link_prove_batch` on this key
+    /// (`cg_device_link_prove_last_kernel_ms`): the checks, the walks, the sums, pi0 with the digest, lhs1, pi1.
+    pub fn device_link_prove_last_kernel_ms(&self) -> Result<[f32; 6], SynthesisError> {
+        let mut ms = [0f32; 6];
+        let rc = unsafe { sys::cg_device_link_prove_last_kernel_ms(self.h, ms.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(ms)
+    }
+
     /// `create_show_proof`'s `show_groth16` and `show_range` steps (creds/src/lib.rs:364-373, :468-471, :505-509) for `n`
     /// client states of one proof spec in one call (`cg_create_showings_batch`): the re-randomised proof, the commitments,
     /// `DLogPoK::prove` whole with its Merlin transcript over `context`, and per link the shift by `shifts` and

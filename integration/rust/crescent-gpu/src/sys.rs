@@ -193,6 +193,22 @@ pub struct cg_device_link_rows {
     pub pi1_s: *const u8,
 }
 
+/// the scalars one device proof draws: z, t_z, r1, a, b, d, n0, n1, n2 (`cg_device_link_prove_batch`)
+pub const CG_DEVICE_LINK_N_RAND: usize = 9;
+
+/// one device proof per showing, n rows each, written by `cg_device_link_prove_batch` in the layouts `cg_device_link_rows` takes
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct cg_device_link_made {
+    pub com1: *mut u8,
+    pub comz: *mut u8,
+    pub m: *mut u8,
+    pub pi0_c: *mut u8,
+    pub pi0_s: *mut u8,
+    pub pi1_c: *mut u8,
+    pub pi1_s: *mut u8,
+}
+
 /// one range proof per showing, n rows each, in the layouts `cg_range_prove_batch` writes; `challenges` may be null
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -633,5 +649,22 @@ extern "C" {
         e_out: *mut u8,
     ) -> c_int;
     pub fn cg_device_link_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32) -> c_int;
+    pub fn cg_device_link_prove_batch(
+        k: *mut cg_pvk,
+        io_types: *const u8,
+        n_io: u64,
+        pos0: u32,
+        pos1: u32,
+        committed: *const u8,
+        openings: *const u8,
+        rand: *const u8,
+        h_q: *const u8,
+        h_len: u32,
+        n: u64,
+        out: *const cg_device_link_made,
+        e_out: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_device_link_prove_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32) -> c_int;
     pub fn cg_revealed_digest_batch(data: *const u8, offsets: *const u64, n_items: u64, out: *mut u8) -> c_int;
 }
