@@ -307,6 +307,11 @@ _SIGNATURES = {
     "cg_device_link_prove_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(_CgDeviceLinkMade), C.c_void_p, C.c_void_p]),
     "cg_device_link_prove_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "cg_poseidon_p256_permute_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cg_hq_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cg_device_link_prove_hq_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_uint64, C.POINTER(_CgDeviceLinkMade), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_hq_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "cg_revealed_digest_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
@@ -1957,6 +1962,77 @@ class Groth16:
         return out, e
 
     @staticmethod
+    def poseidon_p256_permute_batch_packed(pvk: "PreparedVerifyingKey", states):
+        """cg_poseidon_p256_permute_batch: Poseidon of width 3 over P-256's base field on n states of 3 x 32 bytes, canonical
+        little-endian.  Returns (out n x 3 x 32, status n); a row with an element >= p is CG_SHOW_MALFORMED and zero."""
+        sb = _u8(states)
+        if sb.size % 96:
+            raise ValueError("states must be n x 3 x 32 bytes")
+        n = sb.size // 96
+        out, status = np.zeros((max(n, 1), 3, 32), np.uint8), np.zeros(max(n, 1), np.uint8)
+        _check(lib().cg_poseidon_p256_permute_batch(pvk._h, _ptr(sb) if n else None, n, _ptr(out), _ptr(status)))
+        return out[:n], status[:n]
+
+    @staticmethod
+    def hq_batch_packed(pvk: "PreparedVerifyingKey", q):
+        """cg_hq_batch: `compute_hQ` (ecdsa-pop/src/lib.rs:308-320) for n rows of (q0, q1, z), 3 x 32 bytes canonical Fr.
+        Returns (h_q n x 32, big-endian as device_link_prove_batch_packed takes them, status n); a row with a scalar >= r is
+        CG_SHOW_MALFORMED and zero."""
+        qb = _u8(q)
+        if qb.size % 96:
+            raise ValueError("q must be n x 3 x 32 bytes (q0, q1, z)")
+        n = qb.size // 96
+        out, status = np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8)
+        _check(lib().cg_hq_batch(pvk._h, _ptr(qb) if n else None, n, _ptr(out), _ptr(status)))
+        return out[:n], status[:n]
+
+    @staticmethod
+    def device_link_prove_hq_batch_packed(pvk: "PreparedVerifyingKey", io_types, pos0: int, pos1: int, committed, openings, rand):
+        """cg_device_link_prove_hq_batch: device_link_prove_batch_packed with h_Q computed on the GPU in the same call, from q0
+        and q1 (openings) and z (rand[0]).  Returns that call's nine arrays and h_q n x 32 as a tenth."""
+        io = _u8(np.asarray(list(io_types), dtype=np.uint8))
+        n_com = int((io == CG_IO_COMMITTED).sum())
+        ob = _u8(openings)
+        if ob.size % 128:
+            raise ValueError("openings must be n x 128 bytes (q0, r0, q1, r1_orig)")
+        n = ob.size // 128
+        comm, rb = _u8(committed, 64 * n_com * n), _u8(rand, 32 * CG_DEVICE_LINK_N_RAND * n)
+        ptr = lambda a: _ptr(a) if a.size else None
+        m = max(n, 1)
+        rows = [np.zeros((m,) + sh, np.uint8) for sh in ((64,), (64,), (32,), (32,), (4, 32), (32,), (3, 32))]
+        e_out, status, h_q = np.zeros((m, 32), np.uint8), np.zeros(m, np.uint8), np.zeros((m, 32), np.uint8)
+        made = _CgDeviceLinkMade(*[_ptr(a) for a in rows])
+        _check(lib().cg_device_link_prove_hq_batch(pvk._h, ptr(io), io.size, int(pos0), int(pos1), ptr(comm), ptr(ob), ptr(rb), n, C.byref(made),
+                                                   _ptr(e_out), _ptr(status), _ptr(h_q)))
+        return tuple(a[:n] for a in rows) + (e_out[:n], status[:n], h_q[:n])
+
+    @staticmethod
+    def device_link_prove_hq_batch(pvk: "PreparedVerifyingKey", io_types, pos0: int, pos1: int, committed, openings, rand=None):
+        """device_link_prove_batch without h_qs: each DeviceLinkProof carries the h_Q the GPU computed for it.  A host that
+        goes on to `ECDSAProof::prove` needs z = rand[i][0] and draws rand itself."""
+        openings = list(openings)
+        n = len(openings)
+        if n == 0:
+            return [], np.zeros((0, 32), np.uint8)
+        if rand is None:
+            import secrets
+            rand = [[secrets.randbelow(FR_MODULUS) for _ in range(CG_DEVICE_LINK_N_RAND)] for _ in range(n)]
+        fr = lambda v: int(v).to_bytes(32, "little")
+        com1, comz, m, c0, s0, c1, s1, e, status, h_q = Groth16.device_link_prove_hq_batch_packed(
+            pvk, io_types, pos0, pos1, b"".join(bytes(c) for row in committed for c in row), b"".join(fr(v) for row in openings for v in row),
+            b"".join(fr(v) for row in rand for v in row))
+        val = lambda a: int.from_bytes(a.tobytes(), "little")
+        out = []
+        for i in range(n):
+            if status[i] != CG_SHOW_MADE:
+                out.append(None)
+                continue
+            out.append(DeviceLinkProof(com1[i].tobytes(), comz[i].tobytes(), h_q[i].tobytes(), val(m[i]), val(c0[i]),
+                                       [[val(s0[i, 0]), val(s0[i, 1])], [val(s0[i, 2]), val(s0[i, 3])]], val(c1[i]),
+                                       [[val(s1[i, 0])], [val(s1[i, 1]), val(s1[i, 2])]]))
+        return out, e
+
+    @staticmethod
     def device_link_openings(io_types, pos0: int, pos1: int, inputs, rand) -> np.ndarray:
         """The openings (q0, r0, q1, r1_orig) of the two device key values, cut out of the arrays create_showings_batch_packed
         took: per showing m = inputs[pos] and r = rand[2 + committed_index] (`committed_input_openings` of
@@ -2051,6 +2127,13 @@ class PreparedVerifyingKey(_LatencyMode, _Handle):
         ms = (C.c_float * 6)()
         _check(lib().cg_device_link_prove_last_kernel_ms(self._h, ms))
         return tuple(float(x) for x in ms)
+
+    def hq_last_kernel_ms(self) -> Tuple[float, float, int]:
+        """cg_hq_last_kernel_ms: HIP-event milliseconds of the kernel of the last hq_batch or permute call on this key and of
+        the h_Q kernel of its last device_link_prove_hq_batch, and how often the Poseidon constants were uploaded (0 or 1)"""
+        ms, up = (C.c_float * 2)(), C.c_uint32()
+        _check(lib().cg_hq_last_kernel_ms(self._h, ms, C.byref(up)))
+        return float(ms[0]), float(ms[1]), int(up.value)
 
     @property
     def num_inputs(self) -> int:

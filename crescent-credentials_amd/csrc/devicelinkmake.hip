@@ -19,12 +19,20 @@
 //   k_dlm_pi1     one lane per proof: pi1's transcript over y = (lhs1, comz) -> c1; pi1's responses
 // A malformed proof costs nothing after the stage that found it.  k_dlm_pi0 and k_dlm_pi1 do arithmetic on bytes and words
 // only and declare no private segment.
+//
+// h_Q (`compute_hQ`, ecdsa-pop/src/lib.rs:308-320) is csrc/poseidon_p256.hpp's, one lane per hash, on the same stream under the
+// same lock: k_hq_permute behind cg_poseidon_p256_permute_batch, k_hq_hash behind cg_hq_batch, and k_hq_link, which
+// cg_device_link_prove_hq_batch runs in front of the six kernels above to fill the chunk's h_Q rows from the openings
+// (q0, q1) and rand[0] (z), so that k_dlm_pi0's digest finds them on the device.  The Poseidon constants are derived on the
+// host once per process and uploaded once per handle.  The three kernels keep their state in registers, read the constants
+// at a wave-uniform address and declare no private segment.
 #include <memory>
 
 #include "common.hpp"
 #include "device_link_make.hpp"
 #include "fixed_base.hpp"
 #include "key_handle.hpp"
+#include "poseidon_p256.hpp"
 
 using namespace cg;
 
@@ -154,18 +162,115 @@ struct DlmState {
 };
 void dlm_state_free(void* s) { delete (DlmState*)s; }
 
+// ---- h_Q --------------------------------------------------------------------------------------------------------------------
+// states: three canonical elements of P-256's field per row; a row with an element >= p is malformed and comes back zero
+__global__ __launch_bounds__(DLMBLOCK) void k_hq_permute(const F256* __restrict__ consts, const uint32_t* __restrict__ states, uint64_t n,
+                                                        uint32_t* __restrict__ out, uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const bool ok = pos_permute_row(consts, states + 24 * p, out + 24 * p);
+    if (!ok)
+        for (int l = 0; l < 24; ++l) out[24 * p + l] = 0;
+    status[p] = ok ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+}
+
+// q: q0, q1 and z per row, canonical Fr; h_q: 32 bytes per row
+__global__ __launch_bounds__(DLMBLOCK) void k_hq_hash(const F256* __restrict__ consts, const uint32_t* __restrict__ q, uint64_t n,
+                                                     uint32_t* __restrict__ h_q, uint8_t* __restrict__ status) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t* row = q + 24 * p;
+    status[p] = pos_hq_row(consts, row, row + 8, row + 16, h_q + 8 * p) ? CG_SHOW_MADE : CG_SHOW_MALFORMED;
+}
+
+// the same from a chunk of the maker's inputs; a row with a scalar >= r gets zero bytes and is found malformed by k_dlm_check
+__global__ __launch_bounds__(DLMBLOCK) void k_hq_link(const F256* __restrict__ consts, DlmArgs a, uint32_t* __restrict__ h_q) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.n) return;
+    (void)pos_hq_row(consts, a.open(p) + 8 * DLM_Q0, a.open(p) + 8 * DLM_Q1, a.rnd(p) + 8 * DLM_Z, h_q + 8 * p);
+}
+
+// A key's Poseidon constants on the device, uploaded by the first call that needs them, and the arrays of the two h_Q
+// entries.  Its own slot of the handle: the maker's and the verifier's arrays stay where they are.
+struct HqState {
+    DevBuf<F256> consts;
+    uint32_t uploads = 0;
+    RowBuf b_in{96}, b_out, b_status{1};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float ms = 0, ms_link = 0;             // the kernel of the last cg_hq_batch or permute call; k_hq_link of the last proving call
+    ~HqState() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+};
+void hq_state_free(void* s) { delete (HqState*)s; }
+
+// under the handle's lock, after hipSetDevice
+HqState& hq_state(PvkLinkView& v) {
+    if (!*v.hq_state) {
+        std::unique_ptr<HqState> fresh(new HqState());
+        for (hipEvent_t& x : fresh->ev) CG_HIP(hipEventCreate(&x));
+        *v.hq_state_free = hq_state_free;
+        *v.hq_state = fresh.release();
+    }
+    HqState& h = *(HqState*)*v.hq_state;
+    if (!h.uploads) {
+        grow(h.consts, (uint64_t)POS_N_CONSTS);
+        h2d_sync(h.consts.p, pos_consts().c, sizeof(F256) * POS_N_CONSTS, v.st);
+        h.uploads = 1;
+    }
+    return h;
+}
+
+// cg_poseidon_p256_permute_batch (out_row 96) and cg_hq_batch (out_row 32): rows of 96 bytes in, in chunks
+int hq_rows(cg_pvk* k, const uint8_t* in, uint64_t n, uint8_t* out, uint8_t* status, uint64_t out_row) {
+    if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return CG_OK;
+    if (!in || !out || !status) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    PvkLinkView v;
+    pvk_link_handle(k, v);
+    try {
+        std::lock_guard<std::mutex> lk(*v.mu);
+        CG_HIP(hipSetDevice(v.device));
+        HqState& h = hq_state(v);
+        const uint64_t chunk = n < DLMCHUNK ? n : DLMCHUNK;
+        h.b_in.reserve(chunk);
+        h.b_out.reserve(chunk, out_row);
+        h.b_status.reserve(chunk);
+        h.ms = 0;
+        for (uint64_t off = 0; off < n; off += chunk) {
+            const uint64_t m = n - off < chunk ? n - off : chunk;
+            h.b_in.up(v.st, in, off, m);
+            CG_HIP(hipEventRecord(h.ev[0], v.st));
+            if (out_row == 96) k_hq_permute<<<ceil_div(m, DLMBLOCK), DLMBLOCK, 0, v.st>>>(h.consts.p, h.b_in.words(), m, h.b_out.words_mut(), h.b_status.bytes());
+            else k_hq_hash<<<ceil_div(m, DLMBLOCK), DLMBLOCK, 0, v.st>>>(h.consts.p, h.b_in.words(), m, h.b_out.words_mut(), h.b_status.bytes());
+            CG_KERNEL_CHECK();
+            CG_HIP(hipEventRecord(h.ev[1], v.st));
+            h.b_out.down(v.st, out, off, m);
+            h.b_status.down(v.st, status, off, m);
+            CG_HIP(hipStreamSynchronize(v.st));
+            float t = 0;
+            CG_HIP(hipEventElapsedTime(&t, h.ev[0], h.ev[1]));
+            h.ms += t;
+        }
+        return CG_OK;
+    } catch (...) {
+        return translate_current_exception();
+    }
+}
+
 }  // namespace
 
-extern "C" int cg_device_link_prove_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1,
-                                          const uint8_t* committed, const uint8_t* openings, const uint8_t* rand, const uint8_t* h_q,
-                                          uint32_t h_len, uint64_t n, const cg_device_link_made* out, uint8_t* e_out, uint8_t* status) {
+namespace {
+// cg_device_link_prove_batch (h_q_out null: h_Q is the caller's, h_len bytes per row) and cg_device_link_prove_hq_batch
+// (h_q null, h_len 32: k_hq_link fills the chunk's rows on the device, and they come down into h_q_out)
+int dlm_prove(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1, const uint8_t* committed, const uint8_t* openings,
+              const uint8_t* rand, const uint8_t* h_q, uint32_t h_len, uint64_t n, const cg_device_link_made* out, uint8_t* e_out, uint8_t* status,
+              uint8_t* h_q_out, bool on_device) {
     if (!k) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     PvkLinkView v;
     if (int rc = pvk_link_view(k, io_types, n_io, pos0, pos1, v)) return rc;
     if (h_len > DL_H_MAX) return fail(CG_ERR_INVALID_ARGUMENT, "h_len = %u: h_Q has at most %u bytes here", h_len, DL_H_MAX);
     if (n == 0) return CG_OK;
-    if (!committed || !openings || !rand || (h_len && !h_q) || !out || !e_out || !status || !out->com1 || !out->comz || !out->m || !out->pi0_c ||
-        !out->pi0_s || !out->pi1_c || !out->pi1_s)
+    if (!committed || !openings || !rand || (!on_device && h_len && !h_q) || (on_device && !h_q_out) || !out || !e_out || !status || !out->com1 ||
+        !out->comz || !out->m || !out->pi0_c || !out->pi0_s || !out->pi1_c || !out->pi1_s)
         return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
     try {
         std::lock_guard<std::mutex> lk(*v.mu);
@@ -177,6 +282,8 @@ extern "C" int cg_device_link_prove_batch(cg_pvk* k, const uint8_t* io_types, ui
             *v.make_state = fresh.release();
         }
         DlmState& s = *(DlmState*)*v.make_state;
+        HqState* hq = on_device ? &hq_state(v) : nullptr;
+        if (hq) hq->ms_link = 0;
         const uint64_t chunk = n < DLMCHUNK ? n : DLMCHUNK;
         s.b_comm.reserve(chunk, 64ull * v.n_com);
         s.b_hq.reserve(chunk, h_len);
@@ -196,11 +303,16 @@ extern "C" int cg_device_link_prove_batch(cg_pvk* k, const uint8_t* io_types, ui
             s.b_comm.up(v.st, committed, off, m);
             s.b_open.up(v.st, openings, off, m);
             s.b_rand.up(v.st, rand, off, m);
-            s.b_hq.up(v.st, h_q, off, m);
+            if (!hq) s.b_hq.up(v.st, h_q, off, m);
             const DlmArgs a{s.b_comm.words(), v.n_com, v.ci0, v.ci1, s.b_open.words(), s.b_rand.words(), s.b_hq.bytes(), h_len, m};
             const DlmOut o{s.b_com1.words_mut(), s.b_comz.words_mut(), s.b_m.words_mut(), s.b_c0.words_mut(), s.b_s0.words_mut(),
                            s.b_c1.words_mut(), s.b_s1.words_mut(), s.b_e.words_mut(), s.b_status.bytes()};
             const uint32_t grid = ceil_div(m, DLMBLOCK);
+            if (hq) {
+                CG_HIP(hipEventRecord(hq->ev[0], v.st));
+                k_hq_link<<<grid, DLMBLOCK, 0, v.st>>>(hq->consts.p, a, s.b_hq.words_mut());
+                CG_KERNEL_CHECK();
+            }
             CG_HIP(hipEventRecord(s.ev[0], v.st));
             k_dlm_check<<<grid, DLMBLOCK, 0, v.st>>>(a, s.b_flags.bytes());
             CG_KERNEL_CHECK();
@@ -230,17 +342,67 @@ extern "C" int cg_device_link_prove_batch(cg_pvk* k, const uint8_t* io_types, ui
             s.b_s1.down(v.st, out->pi1_s, off, m);
             s.b_e.down(v.st, e_out, off, m);
             s.b_status.down(v.st, status, off, m);
+            if (hq) s.b_hq.down(v.st, h_q_out, off, m);
             CG_HIP(hipStreamSynchronize(v.st));
             for (int i = 0; i < 6; ++i) {
                 float t = 0;
                 CG_HIP(hipEventElapsedTime(&t, s.ev[i], s.ev[i + 1]));
                 s.ms[i] += t;
             }
+            if (hq) {
+                float t = 0;
+                CG_HIP(hipEventElapsedTime(&t, hq->ev[0], s.ev[0]));
+                hq->ms_link += t;
+                // a row that a later stage found malformed (an opening that does not open) has every output zero, h_Q included
+                for (uint64_t p = off; p < off + m; ++p)
+                    if (status[p] != CG_SHOW_MADE) memset(h_q_out + 32 * p, 0, 32);
+            }
         }
         return CG_OK;
     } catch (...) {
         return translate_current_exception();
     }
+}
+}  // namespace
+
+extern "C" int cg_device_link_prove_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1,
+                                          const uint8_t* committed, const uint8_t* openings, const uint8_t* rand, const uint8_t* h_q,
+                                          uint32_t h_len, uint64_t n, const cg_device_link_made* out, uint8_t* e_out, uint8_t* status) {
+    return dlm_prove(k, io_types, n_io, pos0, pos1, committed, openings, rand, h_q, h_len, n, out, e_out, status, nullptr, false);
+}
+
+// the same with h_Q computed on the device from q0, q1 (openings) and z (rand[0]); its 32 bytes per row come back in h_q_out
+extern "C" int cg_device_link_prove_hq_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1,
+                                             const uint8_t* committed, const uint8_t* openings, const uint8_t* rand, uint64_t n,
+                                             const cg_device_link_made* out, uint8_t* e_out, uint8_t* status, uint8_t* h_q_out) {
+    return dlm_prove(k, io_types, n_io, pos0, pos1, committed, openings, rand, nullptr, 32, n, out, e_out, status, h_q_out, true);
+}
+
+// Poseidon over P-256's base field, width 3: n states of three canonical elements (32 bytes little-endian each) -> the
+// permuted states.  A row with an element >= p is CG_SHOW_MALFORMED, that row alone, and its output zero.
+extern "C" int cg_poseidon_p256_permute_batch(cg_pvk* k, const uint8_t* states, uint64_t n, uint8_t* out, uint8_t* status) {
+    return hq_rows(k, states, n, out, status, 96);
+}
+
+// h_Q = compute_hQ(q0, q1, z) for n rows of three canonical Fr -> 32 bytes big-endian per row, as cg_device_link_rows.h_q
+// takes them with h_len = 32.  A row with a scalar >= r is CG_SHOW_MALFORMED, that row alone, and its output zero.
+extern "C" int cg_hq_batch(cg_pvk* k, const uint8_t* q, uint64_t n, uint8_t* h_q_out, uint8_t* status) {
+    return hq_rows(k, q, n, h_q_out, status, 32);
+}
+
+// Diagnostic: ms[0] the kernel of the handle's last cg_hq_batch or cg_poseidon_p256_permute_batch, ms[1] k_hq_link of its
+// last cg_device_link_prove_hq_batch, by HIP events, summed over the chunks; *uploads how often the Poseidon constants went
+// up to this handle (0 before the first call that needs them, 1 ever after)
+extern "C" int cg_hq_last_kernel_ms(cg_pvk* k, float ms[2], uint32_t* uploads) {
+    if (!k || !ms || !uploads) return fail(CG_ERR_INVALID_ARGUMENT, "null argument");
+    PvkLinkView v;
+    pvk_link_handle(k, v);
+    std::lock_guard<std::mutex> lk(*v.mu);
+    const HqState* h = (const HqState*)*v.hq_state;
+    ms[0] = h ? h->ms : 0.f;
+    ms[1] = h ? h->ms_link : 0.f;
+    *uploads = h ? h->uploads : 0u;
+    return CG_OK;
 }
 
 // Diagnostic: what the six kernels of the handle's last cg_device_link_prove_batch took, by HIP events, summed over its

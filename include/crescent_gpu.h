@@ -1090,9 +1090,10 @@ typedef struct cg_device_link_made { uint8_t *com1, *comz, *m, *pi0_c, *pi0_s, *
  *           logarithm, so each group element is a sum of walks through the key's fixed-base tables of g, g' and h - lhs1 is the
  *           one walk r h - and a proof has no variable-base chain.  Per chunk of showings everything runs on the device and
  *           nothing comes down between the steps.
- * NOT done here: `compute_hQ`, which is Poseidon over P-256's base field, and pi2 (`ECDSAProof::prove`); the library draws no
- * randomness.  The host computes h_Q first, and afterwards hands m, e_out and its own z to `ECDSAProof::prove` (INTEGRATION.md,
- * "Creating device proofs").
+ * NOT done here: pi2 (`ECDSAProof::prove`), and in THIS call `compute_hQ`, which is Poseidon over P-256's base field: h_Q is
+ * an input here, from cg_hq_batch or from the host.  cg_device_link_prove_hq_batch below computes it on the device in the same
+ * call.  The library draws no randomness.  Afterwards the host hands m, e_out and its own z to `ECDSAProof::prove`
+ * ("Creating device proofs").
  * UNVERIFIED text forms: as for cg_device_link_verify_batch; both calls take the digest from the same function of
  * csrc/device_link.hpp.
  * io_types, n_io, pos0, pos1, committed, h_q, h_len: exactly as for cg_device_link_verify_batch.  com0 and com1_orig are read
@@ -1122,6 +1123,47 @@ int cg_device_link_prove_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io
  * chunks: the checks, the fifteen walks, the sums, pi0 with the digest, lhs1, pi1.  Zeros before the first such call.
  * (No counterpart in the reference.) */
 int cg_device_link_prove_last_kernel_ms(cg_pvk* k, float ms[6]);
+/* Replaces: the Poseidon permutation over P-256's base field (p = 2^256 - 2^224 + 2^192 + 2^96 - 1) that `compute_hQ` is built
+ *           on: width 3, (R_F, R_P) = (8, 55), neptune's `Strength::Standard` constants derived by the library itself
+ *           (csrc/poseidon_p256.hpp), for n states in one call.  The primitive under cg_hq_batch, and the entry through which
+ *           the field's edges are reached.
+ * states, out: n x 3 x 32 B, canonical little-endian.
+ * status: n x CG_SHOW_MADE / CG_SHOW_MALFORMED.  MALFORMED means that row only: an element of it is >= p, and its output is
+ *         zero bytes.
+ * Errors, reported before any HIP call and with no output touched: a null argument.  n = 0 is CG_OK.  Runs on the key's stream
+ * under its lock; the constants go up to the handle once, with the first call that needs them. */
+int cg_poseidon_p256_permute_batch(cg_pvk* k, const uint8_t* states, uint64_t n, uint8_t* out, uint8_t* status);
+/* Replaces: `compute_hQ` (ecdsa-pop/src/lib.rs:308-320): h_Q = Poseidon(q0, q1, z) over P-256's base field, for n rows in one
+ *           call.
+ * UNVERIFIED readings: the constants, the permutation and the IO-pattern tag reproduce neptune's own known answers over
+ * BLS12-381's Fr (tests/golden/neptune_kats.json).  Three things no recorded value pins, each one function of
+ * csrc/poseidon_p256.hpp, until a Rust-made h_Q meets this code: (1) the Grain LFSR's first byte takes 8 bits where the
+ * field's bit length is a multiple of 8, as P-256's 256 is; (2) the sponge is state = [tag, 0, 0], q0 and q1 added to elements
+ * 1 and 2, a permutation, z added to element 1, a permutation, element 1 out; (3) `to_bytes()` reversed is the element's 32
+ * bytes big-endian.
+ * q:       n x 3 x 32 B canonical Fr: q0, q1, z as a showing holds them (r < p, so each is a field element).
+ * h_q_out: n x 32 B big-endian: exactly the bytes cg_device_link_rows.h_q and cg_device_link_prove_batch take with h_len = 32.
+ * status:  n x CG_SHOW_MADE / CG_SHOW_MALFORMED.  MALFORMED means that row only: a scalar of it is >= r, the rule of the
+ *          openings, and its output is zero bytes.
+ * Errors and scheduling as for cg_poseidon_p256_permute_batch.  Measured on an MI355X: profiles/device_link_hq.md. */
+int cg_hq_batch(cg_pvk* k, const uint8_t* q, uint64_t n, uint8_t* h_q_out, uint8_t* status);
+/* cg_device_link_prove_batch with `compute_hQ` in the same call: one more kernel in front of the chunk's six computes h_Q from
+ * q0 and q1 (openings) and z (rand[0]) where the digest reads it, so the host computes nothing before the call and hands only
+ * m, e_out and z to `ECDSAProof::prove` after it.
+ * NOT done here: pi2 (`ECDSAProof::prove`); the library draws no randomness.
+ * UNVERIFIED: the text forms of cg_device_link_verify_batch and the three readings of cg_hq_batch.
+ * Every argument but the last as for cg_device_link_prove_batch, which has h_q and h_len in addition.
+ * h_q_out: n x 32 B: the row's h_Q, which the caller passes on to the verifier.  Every other output is byte for byte what
+ *          cg_hq_batch followed by cg_device_link_prove_batch with h_len = 32 writes.  A malformed row has h_q_out zero as well.
+ * Errors: as for cg_device_link_prove_batch, and a null h_q_out.  n = 0 is CG_OK. */
+int cg_device_link_prove_hq_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t pos0, uint32_t pos1,
+                                  const uint8_t* committed, const uint8_t* openings, const uint8_t* rand, uint64_t n,
+                                  const cg_device_link_made* out, uint8_t* e_out, uint8_t* status, uint8_t* h_q_out);
+/* Diagnostic: ms[0] what the kernel of the handle's last cg_hq_batch or cg_poseidon_p256_permute_batch took, ms[1] what the
+ * h_Q kernel of its last cg_device_link_prove_hq_batch took (cg_device_link_prove_last_kernel_ms has the six behind it), by
+ * HIP events, summed over the chunks; *uploads: how often the Poseidon constants went up to this handle, 0 before the first
+ * call that needs them and 1 ever after.  (No counterpart in the reference.) */
+int cg_hq_last_kernel_ms(cg_pvk* k, float ms[2], uint32_t* uploads);
 /* Replaces: the digests of `revealed_preimages` that `verify_show` places among the public inputs (creds/src/lib.rs:590-603):
  *           per hashed attribute SHA-256 of the preimage string and its first 31 bytes through `bits_to_num`
  *           (creds/src/utils.rs:78-94), as the canonical Fr a host places into `revealed`.  Host only, on the library's worker

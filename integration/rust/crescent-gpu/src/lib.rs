@@ -941,7 +941,7 @@ impl GpuVerifyingKey {
     }
 
     /// The BN254 half of `DeviceProof::prove` (creds/src/device.rs:104-160) for n device-bound showings of one layout in one
-    /// call (`cg_device_link_prove_batch`), short of `compute_hQ` and of pi2: comz, the re-committed com1, pi0, the SHA-256
+    /// call (`cg_device_link_prove_batch`), short of `compute_hQ` (see `device_link_prove_hq_batch`) and of pi2: comz, the re-committed com1, pi0, the SHA-256
     /// challenge, m, lhs1 and pi1.  `committed` is the showing's own n x n_committed x 64 B array, as `create_showings_batch`
     /// returned it; `openings` holds n x (q0, r0, q1, r1_orig) and `rand` n x `CG_DEVICE_LINK_N_RAND` canonical scalars in the
     /// header's order; `h_q` n x `h_len` bytes.  Returns (the rows, with the caller's h_q, as `device_link_verify_batch` takes
@@ -966,6 +966,73 @@ impl GpuVerifyingKey {
             return Err(map_err(rc));
         }
         Ok((rows, e, status))
+    }
+
+    /// `device_link_prove_batch` with `compute_hQ` in the same call (`cg_device_link_prove_hq_batch`): h_Q is computed on the
+    /// GPU from q0 and q1 (`openings`) and z (`rand[0]`) and comes back in the rows' `h_q`, 32 bytes per row.  The host computes
+    /// nothing before the call and hands m, e and z to `ECDSAProof::prove` after it.
+    pub fn device_link_prove_hq_batch(&self, io_types: &[u8], pos0: u32, pos1: u32, committed: &[u8], openings: &[u8], rand: &[u8]) -> Result<(DeviceLinkRows, Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = openings.len() / 128;
+        let n_com = io_types.iter().filter(|&&t| t == 2).count();
+        if openings.len() != n * 128 || rand.len() != n * 32 * sys::CG_DEVICE_LINK_N_RAND || committed.len() != n * n_com * 64 {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let mut rows = DeviceLinkRows { com1: vec![0u8; n * 64], comz: vec![0u8; n * 64], h_q: vec![0u8; n * 32], m: vec![0u8; n * 32], pi0_c: vec![0u8; n * 32],
+                                        pi0_s: vec![0u8; n * 128], pi1_c: vec![0u8; n * 32], pi1_s: vec![0u8; n * 96] };
+        let made = sys::cg_device_link_made { com1: rows.com1.as_mut_ptr(), comz: rows.comz.as_mut_ptr(), m: rows.m.as_mut_ptr(), pi0_c: rows.pi0_c.as_mut_ptr(),
+                                              pi0_s: rows.pi0_s.as_mut_ptr(), pi1_c: rows.pi1_c.as_mut_ptr(), pi1_s: rows.pi1_s.as_mut_ptr() };
+        let (mut e, mut status) = (vec![0u8; n * 32], vec![0u8; n]);
+        let rc = unsafe {
+            sys::cg_device_link_prove_hq_batch(self.h, io_types.as_ptr(), io_types.len() as u64, pos0, pos1, committed.as_ptr(), openings.as_ptr(), rand.as_ptr(),
+                                               n as u64, &made, e.as_mut_ptr(), status.as_mut_ptr(), rows.h_q.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((rows, e, status))
+    }
+
+    /// `compute_hQ` (ecdsa-pop/src/lib.rs:308-320) for n rows of (q0, q1, z), 3 x 32 B canonical Fr (`cg_hq_batch`).  Returns
+    /// (h_Q n x 32 B big-endian, as `device_link_prove_batch` takes them with h_len = 32; status n x CG_SHOW_MADE /
+    /// CG_SHOW_MALFORMED, a row with a scalar >= r being zero bytes).
+    pub fn hq_batch(&self, q: &[u8]) -> Result<(Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = q.len() / 96;
+        if q.len() != n * 96 {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (mut h_q, mut status) = (vec![0u8; n * 32], vec![0u8; n]);
+        let rc = unsafe { sys::cg_hq_batch(self.h, q.as_ptr(), n as u64, h_q.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((h_q, status))
+    }
+
+    /// Poseidon of width 3 over P-256's base field on n states of 3 x 32 B canonical little-endian elements
+    /// (`cg_poseidon_p256_permute_batch`): (the permuted states, status; a row with an element >= p is malformed and zero).
+    pub fn poseidon_p256_permute_batch(&self, states: &[u8]) -> Result<(Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = states.len() / 96;
+        if states.len() != n * 96 {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (mut out, mut status) = (vec![0u8; n * 96], vec![0u8; n]);
+        let rc = unsafe { sys::cg_poseidon_p256_permute_batch(self.h, states.as_ptr(), n as u64, out.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((out, status))
+    }
+
+    /// (`cg_hq_last_kernel_ms`) HIP-event milliseconds of the kernel of the last `hq_batch` or `poseidon_p256_permute_batch`
+    /// on this key and of the h_Q kernel of its last `device_link_prove_hq_batch`; and how often the Poseidon constants were
+    /// uploaded to it (0 or 1).
+    pub fn hq_last_kernel_ms(&self) -> Result<([f32; 2], u32), SynthesisError> {
+        let (mut ms, mut uploads) = ([0f32; 2], 0u32);
+        let rc = unsafe { sys::cg_hq_last_kernel_ms(self.h, ms.as_mut_ptr(), &mut uploads) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((ms, uploads))
     }
 
     /// HIP-event milliseconds of the six kernels of the last `device_link_prove_batch` on this key

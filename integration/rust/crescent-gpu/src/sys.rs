@@ -666,5 +666,23 @@ extern "C" {
         status: *mut u8,
     ) -> c_int;
     pub fn cg_device_link_prove_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32) -> c_int;
+    pub fn cg_poseidon_p256_permute_batch(k: *mut cg_pvk, states: *const u8, n: u64, out: *mut u8, status: *mut u8) -> c_int;
+    pub fn cg_hq_batch(k: *mut cg_pvk, q: *const u8, n: u64, h_q_out: *mut u8, status: *mut u8) -> c_int;
+    pub fn cg_device_link_prove_hq_batch(
+        k: *mut cg_pvk,
+        io_types: *const u8,
+        n_io: u64,
+        pos0: u32,
+        pos1: u32,
+        committed: *const u8,
+        openings: *const u8,
+        rand: *const u8,
+        n: u64,
+        out: *const cg_device_link_made,
+        e_out: *mut u8,
+        status: *mut u8,
+        h_q_out: *mut u8,
+    ) -> c_int;
+    pub fn cg_hq_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32, uploads: *mut u32) -> c_int;
     pub fn cg_revealed_digest_batch(data: *const u8, offsets: *const u64, n_items: u64, out: *mut u8) -> c_int;
 }
