@@ -34,6 +34,7 @@ CG_ERR_UNSATISFIED = -8
 CG_VERIFY_REJECT, CG_VERIFY_ACCEPT, CG_VERIFY_MALFORMED = 0, 1, 2
 CG_IO_REVEALED, CG_IO_HIDDEN, CG_IO_COMMITTED = 0, 1, 2      # PublicIOType, creds/src/structs.rs:33-37
 CG_SHOW_MADE, CG_SHOW_MALFORMED = 1, 2
+CG_P256_BAD_SIGNATURE = 3          # cg_p256_rtu_batch alone: the row is well formed and its signature does not verify
 CG_RANGE_N_RAND, CG_RANGE_N_RESP = 18, 6
 CG_DEVICE_LINK_N_RAND = 9
 
@@ -312,6 +313,9 @@ _SIGNATURES = {
     "cg_device_link_prove_hq_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_uint64, C.POINTER(_CgDeviceLinkMade), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_hq_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "cg_p256_tu_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_p256_rtu_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cg_p256_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "cg_revealed_digest_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
@@ -375,6 +379,12 @@ def scalars_to_array(vals: Sequence[int]) -> np.ndarray:
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def _p256_point(xy: np.ndarray):
+    """x ‖ y, 64 bytes big-endian -> (x, y), or None for the identity's 64 zero bytes"""
+    b = xy.tobytes()
+    return (int.from_bytes(b[:32], "big"), int.from_bytes(b[32:], "big")) if any(b) else None
 
 
 def scalars_convert(a, in_form: int, out_form: int, out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -2033,6 +2043,59 @@ class Groth16:
         return out, e
 
     @staticmethod
+    def p256_tu_batch(pvk: "PreparedVerifyingKey", r_xy, digest):
+        """cg_p256_tu_batch: `compute_TU` (ecdsa-pop/src/lib.rs:217-240) for n rows: r_xy n x 64 B (R as x ‖ y) and digest
+        n x 32 B, every quantity 32 bytes big-endian.  Returns (t_xy n x 64, u_xy n x 64, status n); a row whose R has a
+        coordinate >= p, is off the curve or has R.x = 0 mod n is CG_SHOW_MALFORMED and zero; the identity is 64 zero bytes."""
+        rb, db = _u8(r_xy), _u8(digest)
+        if rb.size % 64 or db.size * 2 != rb.size:
+            raise ValueError("r_xy must be n x 64 bytes and digest n x 32")
+        n = rb.size // 64
+        t, u, status = np.zeros((max(n, 1), 64), np.uint8), np.zeros((max(n, 1), 64), np.uint8), np.zeros(max(n, 1), np.uint8)
+        _check(lib().cg_p256_tu_batch(pvk._h, _ptr(rb) if n else None, _ptr(db) if n else None, n, _ptr(t), _ptr(u), _ptr(status)))
+        return t[:n], u[:n], status[:n]
+
+    @staticmethod
+    def p256_rtu_batch(pvk: "PreparedVerifyingKey", q_xy, sig, digest):
+        """cg_p256_rtu_batch: `compute_RTU` (ecdsa-pop/src/lib.rs:180-215) for n rows: q_xy n x 64 B (the device's public key),
+        sig n x 64 B (r ‖ s), digest n x 32 B.  Returns (r_xy, t_xy, u_xy, each n x 64, status n): CG_SHOW_MADE,
+        CG_SHOW_MALFORMED (Q not a canonical point of the curve, r or s outside [1, n - 1]) or CG_P256_BAD_SIGNATURE, every
+        output of a row that is not made being zero."""
+        qb, sb, db = _u8(q_xy), _u8(sig), _u8(digest)
+        if qb.size % 64 or sb.size != qb.size or db.size * 2 != qb.size:
+            raise ValueError("q_xy and sig must be n x 64 bytes and digest n x 32")
+        n = qb.size // 64
+        r, t, u = (np.zeros((max(n, 1), 64), np.uint8) for _ in range(3))
+        status = np.zeros(max(n, 1), np.uint8)
+        ptr = lambda a: _ptr(a) if n else None
+        _check(lib().cg_p256_rtu_batch(pvk._h, ptr(qb), ptr(sb), ptr(db), n, _ptr(r), _ptr(t), _ptr(u), _ptr(status)))
+        return r[:n], t[:n], u[:n], status[:n]
+
+    @staticmethod
+    def p256_tu(pvk: "PreparedVerifyingKey", rows):
+        """p256_tu_batch on Python integers: rows of ((R.x, R.y), digest), the digest an integer below 2^256.  Returns per row
+        (T, U), a point being (x, y) and the identity None, or None for a malformed row."""
+        rows = list(rows)
+        if not rows:
+            return []
+        be = lambda v: int(v).to_bytes(32, "big")
+        t, u, status = Groth16.p256_tu_batch(pvk, b"".join(be(R[0]) + be(R[1]) for R, _ in rows), b"".join(be(d) for _, d in rows))
+        return [(_p256_point(t[i]), _p256_point(u[i])) if status[i] == CG_SHOW_MADE else None for i in range(len(rows))]
+
+    @staticmethod
+    def p256_rtu(pvk: "PreparedVerifyingKey", rows):
+        """p256_rtu_batch on Python integers: rows of ((Q.x, Q.y), r, s, digest).  Returns per row (status, (R, T, U)), the
+        points as p256_tu returns them and the triple None unless the status is CG_SHOW_MADE."""
+        rows = list(rows)
+        if not rows:
+            return []
+        be = lambda v: int(v).to_bytes(32, "big")
+        r, t, u, status = Groth16.p256_rtu_batch(pvk, b"".join(be(Q[0]) + be(Q[1]) for Q, _, _, _ in rows),
+                                                 b"".join(be(r_) + be(s_) for _, r_, s_, _ in rows), b"".join(be(d) for _, _, _, d in rows))
+        return [(int(status[i]), (_p256_point(r[i]), _p256_point(t[i]), _p256_point(u[i])) if status[i] == CG_SHOW_MADE else None)
+                for i in range(len(rows))]
+
+    @staticmethod
     def device_link_openings(io_types, pos0: int, pos1: int, inputs, rand) -> np.ndarray:
         """The openings (q0, r0, q1, r1_orig) of the two device key values, cut out of the arrays create_showings_batch_packed
         took: per showing m = inputs[pos] and r = rand[2 + committed_index] (`committed_input_openings` of
@@ -2134,6 +2197,14 @@ class PreparedVerifyingKey(_LatencyMode, _Handle):
         ms, up = (C.c_float * 2)(), C.c_uint32()
         _check(lib().cg_hq_last_kernel_ms(self._h, ms, C.byref(up)))
         return float(ms[0]), float(ms[1]), int(up.value)
+
+    def p256_last_kernel_ms(self) -> Tuple[float, float, float, int]:
+        """cg_p256_last_kernel_ms: HIP-event milliseconds of the three kernels of the last p256_tu_batch or p256_rtu_batch on
+        this key - the scalar stage, the terms, the finishing stage - and how often the table of P-256's generator was
+        uploaded (0 or 1)"""
+        ms, up = (C.c_float * 3)(), C.c_uint32()
+        _check(lib().cg_p256_last_kernel_ms(self._h, ms, C.byref(up)))
+        return float(ms[0]), float(ms[1]), float(ms[2]), int(up.value)
 
     @property
     def num_inputs(self) -> int:

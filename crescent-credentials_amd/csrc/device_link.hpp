@@ -212,13 +212,16 @@ struct PvkLinkView {
     uint32_t n_com, ci0, ci1;      // committed inputs of the layout; the committed indices of pos0 and pos1
     // the per-call arrays of the device link: created by the first call, under the lock, and freed with the handle after its
     // streams have been waited for.  The verifying call (devicelink.hip), the creating call and the h_Q entries (both
-    // devicelinkmake.hip) have a slot each, so that calls of different kinds on one handle do not evict each other.
+    // devicelinkmake.hip) and the P-256 entries (p256tu.hip) have a slot each, so that calls of different kinds on one handle
+    // do not evict each other.
     void** state;
     void (**state_free)(void*);
     void** make_state;
     void (**make_state_free)(void*);
     void** hq_state;
     void (**hq_state_free)(void*);
+    void** p256_state;
+    void (**p256_state_free)(void*);
 };
 // what needs no layout: everything but n_com, ci0 and ci1
 void pvk_link_handle(cg_pvk* k, PvkLinkView& v);

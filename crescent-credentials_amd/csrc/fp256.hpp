@@ -199,4 +199,26 @@ inline F256 f256_inv(const F256& a) {
     return r;
 }
 
+// What the group of csrc/p256.hpp needs beyond the above: -a, and an inversion that a device lane can run.  One product site
+// in a rolled loop of 512 steps (a square, then a product where the exponent's bit is set), the exponent's word selected
+// from the eight literals and never indexed out of an array in memory.  Zero gives zero.
+CG_HD F256 f256_neg(const F256& a) { return f256_sub(f256_zero(), a); }
+CG_HD F256 f256_inv_hd(const F256& a) {
+    F256 one = f256_zero();
+    one.l[0] = 1;
+    F256 r = f256_to_mont(one);
+#pragma unroll 1
+    for (int s = 0; s < 512; ++s) {
+        const int bit = 255 - (s >> 1), w = bit >> 5;
+        uint32_t e = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) e = w == i ? f256_p(i) : e;
+        if (w == 0) e -= 2u;
+        const bool square = (s & 1) == 0;
+        if (!square && !((e >> (bit & 31)) & 1u)) continue;
+        r = f256_mul(r, square ? r : a);
+    }
+    return r;
+}
+
 }  // namespace cg

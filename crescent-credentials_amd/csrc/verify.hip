@@ -726,6 +726,9 @@ struct cg_pvk : KeyHandle {
     // and the Poseidon constants and arrays of the h_Q entries (devicelinkmake.hip)
     void* hq_state = nullptr;
     void (*hq_free)(void*) = nullptr;
+    // and the table of P-256's generator and the arrays of the P-256 entries (p256tu.hip)
+    void* p256_state = nullptr;
+    void (*p256_free)(void*) = nullptr;
     void open_second() {
         CG_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
         for (hipEvent_t* e : {&ev_fork, &ev_join, &ev_link, &ev_ranges}) CG_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -736,6 +739,7 @@ struct cg_pvk : KeyHandle {
         if (dl_state) dl_free(dl_state);
         if (dlm_state) dlm_free(dlm_state);
         if (hq_state) hq_free(hq_state);
+        if (p256_state) p256_free(p256_state);
         for (hipEvent_t e : {ev_fork, ev_join, ev_link, ev_ranges}) if (e) (void)hipEventDestroy(e);
     }
 
@@ -932,7 +936,7 @@ int pvk_link_view(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, uint32_t po
 }
 void pvk_link_handle(cg_pvk* k, PvkLinkView& v) {
     v = PvkLinkView{&k->mu, k->device, k->st, k->tab.p, k->base_bytes.data(), k->n_inputs, 0, 0, 0, &k->dl_state, &k->dl_free,
-                    &k->dlm_state, &k->dlm_free, &k->hq_state, &k->hq_free};
+                    &k->dlm_state, &k->dlm_free, &k->hq_state, &k->hq_free, &k->p256_state, &k->p256_free};
 }
 }  // namespace cg
 

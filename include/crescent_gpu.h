@@ -677,6 +677,8 @@ int cg_verify_show_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n_io, cons
  *   the n_resp nonces, statement-major as dlog.rs:60-67 draws them: per committed input (for gamma_abc[i+1], for
  *   delta_g1), then one per hidden input, then one for delta_g1. */
 enum { CG_SHOW_MADE = 1, CG_SHOW_MALFORMED = 2 };
+/* A third status byte, of cg_p256_rtu_batch alone: the row is well formed and its ECDSA signature does not verify. */
+enum { CG_P256_BAD_SIGNATURE = 3 };
 /* The n_rand of a layout.  Host only. */
 int cg_show_rand_count(const uint8_t* io_types, uint64_t n_io, uint64_t* n_rand);
 /* Replaces: `rerandomize_proof` (forks/groth16/src/prover.rs:227-254), the Pedersen commitments and com_hidden_inputs of
@@ -1164,6 +1166,43 @@ int cg_device_link_prove_hq_batch(cg_pvk* k, const uint8_t* io_types, uint64_t n
  * HIP events, summed over the chunks; *uploads: how often the Poseidon constants went up to this handle, 0 before the first
  * call that needs them and 1 ever after.  (No counterpart in the reference.) */
 int cg_hq_last_kernel_ms(cg_pvk* k, float ms[2], uint32_t* uploads);
+/* Replaces: `ECDSACircuitPublicInputs::compute_TU` (ecdsa-pop/src/lib.rs:217-240), which a relying party runs at the top of
+ *           `ECDSAProof::verify`: from the proof's R = (r_x, r_y) and the digest, T = r^-1 · R and U = (-d · r^-1) · G on P-256,
+ *           with r = R.x mod n and d = digest mod n - the public inputs of pi2's circuit - for n rows in one call.  P-256 group
+ *           arithmetic only (csrc/p256.hpp over csrc/fp256.hpp and csrc/fq256.hpp); nothing of the key is used, the handle
+ *           lends its stream, its lock and a state slot.
+ * NOT done here: pi2 itself (Spartan over T-256).  The host hands T and U to its verifier.
+ * Every P-256 quantity is 32 bytes BIG-endian, the convention of h_Q, of SEC1 and of the 64-byte signature
+ * `ECDSASig::new_from_bytes` splits; a point is x ‖ y, 64 B, and the identity is 64 zero bytes, which is what halo2curves'
+ * `to_affine` makes of it.
+ * r_xy:   n x 64 B: R.    digest: n x 32 B, read as the reference's `from_str_vartime` reads it: an integer below 2^256,
+ *         reduced mod n.
+ * t_xy, u_xy: n x 64 B.  d = 0 mod n is valid: U is then the identity, 64 zero bytes, and the status CG_SHOW_MADE.
+ * status: n x CG_SHOW_MADE / CG_SHOW_MALFORMED.  MALFORMED means that row only, with every output of it zero bytes: a
+ *         coordinate of R is >= p (the reference reduces it silently; this library fails closed on non-canonical input, as it
+ *         does for scalars >= r), R is not on the curve (the reference panics on `from_xy(..).unwrap()`), or r = 0 mod n (the
+ *         reference asserts).
+ * Errors, reported before any HIP call and with no output touched: a null argument.  n = 0 is CG_OK.  Runs on the key's stream
+ * under its lock, in chunks; the table of G (0.5 MB) goes up to the handle once, with the first call that needs it.
+ * A kernel's time is one lane's latency at every batch size, some milliseconds: a host with one row and a P-256 library of
+ * its own should use that.  Measured on an MI355X: profiles/p256_tu.md. */
+int cg_p256_tu_batch(cg_pvk* k, const uint8_t* r_xy, const uint8_t* digest, uint64_t n, uint8_t* t_xy, uint8_t* u_xy, uint8_t* status);
+/* Replaces: `compute_RTU` (ecdsa-pop/src/lib.rs:180-215), which a prover runs at the top of `ECDSAProof::prove` and which is
+ *           the only place where the device's ECDSA signature is checked: R = (d/s) · G + (r/s) · Q, R.x mod n must equal r,
+ *           and then T and U as cg_p256_tu_batch makes them from R, for n rows in one call.  The sum goes through a complete
+ *           addition: a signer chooses Q, and where Q is a small multiple of +-G the two products coincide or cancel.
+ * q_xy:   n x 64 B: the device's public key.    sig: n x 64 B: r ‖ s.    digest: n x 32 B.    Byte forms as above.
+ * r_xy, t_xy, u_xy: n x 64 B.  Feeding r_xy and digest to cg_p256_tu_batch returns the same t_xy and u_xy.
+ * status: n x CG_SHOW_MADE / CG_SHOW_MALFORMED / CG_P256_BAD_SIGNATURE, that row only, with every output of a row that is not
+ *         MADE zero bytes.  MALFORMED: Q fails the checks of R above, or r or s is outside [1, n - 1].  BAD_SIGNATURE: R is
+ *         the identity or R.x mod n != r (the reference panics on its assertion).
+ * Errors and scheduling as for cg_p256_tu_batch. */
+int cg_p256_rtu_batch(cg_pvk* k, const uint8_t* q_xy, const uint8_t* sig, const uint8_t* digest, uint64_t n, uint8_t* r_xy, uint8_t* t_xy,
+                      uint8_t* u_xy, uint8_t* status);
+/* Diagnostic: what the three kernels of the handle's last cg_p256_tu_batch or cg_p256_rtu_batch took - the scalar stage, the
+ * terms, the finishing stage - by HIP events, summed over the chunks; *uploads: how often the table of G went up to this
+ * handle, 0 before the first call that needs it and 1 ever after.  (No counterpart in the reference.) */
+int cg_p256_last_kernel_ms(cg_pvk* k, float ms[3], uint32_t* uploads);
 /* Replaces: the digests of `revealed_preimages` that `verify_show` places among the public inputs (creds/src/lib.rs:590-603):
  *           per hashed attribute SHA-256 of the preimage string and its first 31 bytes through `bits_to_num`
  *           (creds/src/utils.rs:78-94), as the canonical Fr a host places into `revealed`.  Host only, on the library's worker

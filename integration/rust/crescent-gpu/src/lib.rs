@@ -1023,6 +1023,55 @@ impl GpuVerifyingKey {
         Ok((out, status))
     }
 
+    /// `ECDSACircuitPublicInputs::compute_TU` (ecdsa-pop/src/lib.rs:217-240) for n rows (`cg_p256_tu_batch`): `r_xy` n x 64 B
+    /// (R as x ‖ y) and `digest` n x 32 B, every P-256 quantity 32 bytes big-endian.  Returns (T n x 64 B, U n x 64 B, status
+    /// n x CG_SHOW_MADE / CG_SHOW_MALFORMED): the public inputs `ECDSAProof::verify` hands its circuit.  A malformed row - a
+    /// coordinate >= p, R off the curve, R.x = 0 mod n, where the reference panics - is zero bytes; so is the identity.
+    pub fn p256_tu_batch(&self, r_xy: &[u8], digest: &[u8]) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = r_xy.len() / 64;
+        if r_xy.len() != n * 64 || digest.len() != n * 32 {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (mut t, mut u, mut status) = (vec![0u8; n * 64], vec![0u8; n * 64], vec![0u8; n]);
+        let rc = unsafe { sys::cg_p256_tu_batch(self.h, r_xy.as_ptr(), digest.as_ptr(), n as u64, t.as_mut_ptr(), u.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((t, u, status))
+    }
+
+    /// `compute_RTU` (ecdsa-pop/src/lib.rs:180-215) for n rows (`cg_p256_rtu_batch`): `q_xy` n x 64 B (the device's public
+    /// key), `sig` n x 64 B (r ‖ s), `digest` n x 32 B.  Returns (R, T, U, each n x 64 B, status n): CG_SHOW_MADE,
+    /// CG_SHOW_MALFORMED or `sys::CG_P256_BAD_SIGNATURE`, where the reference panics on its assertion; every output of a row
+    /// that is not made is zero bytes.  This is the only place where the device's signature is checked.
+    pub fn p256_rtu_batch(&self, q_xy: &[u8], sig: &[u8], digest: &[u8]) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>, Vec<u8>), SynthesisError> {
+        let n = q_xy.len() / 64;
+        if q_xy.len() != n * 64 || sig.len() != n * 64 || digest.len() != n * 32 {
+            return Err(SynthesisError::MalformedVerifyingKey);
+        }
+        let (mut r, mut t, mut u, mut status) = (vec![0u8; n * 64], vec![0u8; n * 64], vec![0u8; n * 64], vec![0u8; n]);
+        let rc = unsafe {
+            sys::cg_p256_rtu_batch(self.h, q_xy.as_ptr(), sig.as_ptr(), digest.as_ptr(), n as u64, r.as_mut_ptr(), t.as_mut_ptr(), u.as_mut_ptr(),
+                                   status.as_mut_ptr())
+        };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((r, t, u, status))
+    }
+
+    /// (`cg_p256_last_kernel_ms`) HIP-event milliseconds of the three kernels of the last `p256_tu_batch` or `p256_rtu_batch`
+    /// on this key - the scalar stage, the terms, the finishing stage - and how often the table of P-256's generator was
+    /// uploaded to it (0 or 1).
+    pub fn p256_last_kernel_ms(&self) -> Result<([f32; 3], u32), SynthesisError> {
+        let (mut ms, mut uploads) = ([0f32; 3], 0u32);
+        let rc = unsafe { sys::cg_p256_last_kernel_ms(self.h, ms.as_mut_ptr(), &mut uploads) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((ms, uploads))
+    }
+
     /// (`cg_hq_last_kernel_ms`) HIP-event milliseconds of the kernel of the last `hq_batch` or `poseidon_p256_permute_batch`
     /// on this key and of the h_Q kernel of its last `device_link_prove_hq_batch`; and how often the Poseidon constants were
     /// uploaded to it (0 or 1).

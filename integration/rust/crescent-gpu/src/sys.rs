@@ -25,6 +25,7 @@ pub const CG_IO_HIDDEN: u8 = 1;
 pub const CG_IO_COMMITTED: u8 = 2;
 pub const CG_SHOW_MADE: u8 = 1;
 pub const CG_SHOW_MALFORMED: u8 = 2;
+pub const CG_P256_BAD_SIGNATURE: u8 = 3;
 pub const CG_RANGE_N_RAND: usize = 18;
 pub const CG_RANGE_N_RESP: usize = 6;
 
@@ -684,5 +685,18 @@ extern "C" {
         h_q_out: *mut u8,
     ) -> c_int;
     pub fn cg_hq_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32, uploads: *mut u32) -> c_int;
+    pub fn cg_p256_tu_batch(k: *mut cg_pvk, r_xy: *const u8, digest: *const u8, n: u64, t_xy: *mut u8, u_xy: *mut u8, status: *mut u8) -> c_int;
+    pub fn cg_p256_rtu_batch(
+        k: *mut cg_pvk,
+        q_xy: *const u8,
+        sig: *const u8,
+        digest: *const u8,
+        n: u64,
+        r_xy: *mut u8,
+        t_xy: *mut u8,
+        u_xy: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_p256_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32, uploads: *mut u32) -> c_int;
     pub fn cg_revealed_digest_batch(data: *const u8, offsets: *const u64, n_items: u64, out: *mut u8) -> c_int;
 }
