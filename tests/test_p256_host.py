@@ -2,7 +2,8 @@
 tests/cpp/test_p256.cpp) against Python integers and tests/p256_vectors.py: the scalar field at n's edges - (n - 1) + (n - 1)
 and (n - 1)^2 among them, where the sum and the Montgomery accumulator pass 2^256 -, the inversions, the complete addition on
 equal, opposite and identity operands, k G by the table walk and k P by the windowed chain, the table's first and last rows,
-and whole rows of compute_TU and compute_RTU with every status.  The same program, built with the address and
+whole rows of compute_TU and compute_RTU with every status, and the rows of tests/steer_vectors.py, which are steered to the
+rare branch of both fields' reductions and to the protocol's edges (R.x in [n, p), digests that are 0 mod n, structured scalars).  The same program, built with the address and
 undefined-behaviour sanitizers, answers the same requests on its own.  Then, without running anything: the kernels of csrc/p256tu.hip
 declare no private segment.  Pure CPU.
 
@@ -18,6 +19,7 @@ import pytest
 
 from conftest import ROOT
 import p256_vectors as V
+import steer_vectors as S
 
 P, N, G = V.P, V.N, V.G
 SRC = os.path.join(ROOT, "tests", "cpp", "test_p256.cpp")
@@ -152,13 +154,49 @@ def test_whole_rows_with_every_status(exe):
     compare(exe, lines, want)
 
 
+# ---- rows steered to the rare branches (tests/steer_vectors.py; tests/test_steer_vectors_cpu.py shows that each hits its case) --------
+def steered_lines(family, per_family=None):
+    """the family's vectors as `tu` and `rtu` requests with the oracle's answers; per_family: only every n-th"""
+    lines, want = [], []
+    for v in S.p256_families()[family][::per_family or 1]:
+        lines.append(v.kind + " " + " ".join(a.hex() for a in v.args))
+        w = S.expected(v)
+        want.append(str(w[0]) + "".join(b.hex() for b in w[1:]))
+    return lines, want
+
+
+@pytest.mark.parametrize("family", [name for name, _ in S.P256_FAMILIES])
+def test_steered_rows_byte_for_byte(exe, family):
+    lines, want = steered_lines(family)
+    assert len(lines) == S.P256_COUNTS[family]
+    compare(exe, lines, want)
+
+
+def test_steered_scalars_through_the_scalar_field_alone(exe):
+    """d, s and r whose q256_to_mont takes the rare branch, one operation each: x + 0, x * 1 and x^-1"""
+    xs = [S.facts(v)["scalar"] for v in S.p256_families()["entry_points"] if S.facts(v)["site"] in "dsr"]
+    assert len(xs) == 10 and all(S.from_words_hits(x, N) for x in xs)
+    lines, want = [], []
+    for x in xs:
+        lines += ["qadd %s %s" % (be(x), be(0)), "qmul %s %s" % (be(x), be(1)), "qinv " + be(x), "qadd %s %s" % (be(x), be(N - x))]
+        want += [be(x), be(x), be(pow(x, -1, N)), be(0)]
+    # sums of representations in [n, 2^256): a + b = delta 2^-256 with the representations adding up to n + delta
+    for delta in (0, 1, (1 << 256) - 1 - N):
+        a = 0x1234567 << 200
+        b = (S.unmont(delta, N) - a) % N
+        assert S.mont(a, N) + S.mont(b, N) == N + delta
+        lines.append("qadd %s %s" % (be(a), be(b)))
+        want.append(be((a + b) % N))
+    compare(exe, lines, want)
+
+
 def test_sanitized_build_answers_the_same(tmp_path):
     path = str(tmp_path / "test_p256_san")
     r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", path, SRC],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     lines, want = field_lines(300, 8)
-    for a, b in (group_lines(2), row_lines(2)):
+    for a, b in [group_lines(2), row_lines(2)] + [steered_lines(name, 7) for name, _ in S.P256_FAMILIES]:
         lines, want = lines + a, want + b
     assert ask_all(path, lines + ["tabrow 31"])[:-1] == want
 

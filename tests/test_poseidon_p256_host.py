@@ -1,7 +1,8 @@
 """csrc/fp256.hpp and csrc/poseidon_p256.hpp on the HOST (g++ build of tests/cpp/test_poseidon_p256.cpp): the field operations
 against Python integers at the prime's edges - (p - 1) + (p - 1) and (p - 1)^2 among them, where the sum and the Montgomery
 accumulator pass 2^256 and field.hpp's Fp<P> would drop a word -, the 199 elements a handle uploads, the permutation and h_Q
-against tests/poseidon_vectors.py.  The same program, built with the address and undefined-behaviour sanitizers, answers the
+against tests/poseidon_vectors.py, and the inputs of tests/steer_vectors.py, each of which takes one add or product site of the
+permutation's first round, or of h_Q's entry, into the rare branch of f256_reduce_once.  The same program, built with the address and undefined-behaviour sanitizers, answers the
 same requests on its own.  Then, without running anything: the new entries are declared, exported, bound and declared to
 Rust, a null handle is an argument error, and the three h_Q kernels declare no private segment.  Pure CPU."""
 import ctypes
@@ -16,6 +17,7 @@ import pytest
 
 from conftest import ROOT
 import poseidon_vectors as PV
+import steer_vectors as S
 
 P, R = PV.P256, PV.BN254_FR
 SRC = os.path.join(ROOT, "tests", "cpp", "test_poseidon_p256.cpp")
@@ -110,14 +112,82 @@ def test_permutation_and_hq_on_256_random_inputs(exe):
     assert want[lines.index("hq " + fe(1) + fe(2) + fe(3))] == "b4c83f5ebbc2a8a6c913d1361168ceee2d3796453258470cb7ac7c3abeb24ab5"
 
 
+# ---- inputs steered to the rare branch (tests/steer_vectors.py; tests/test_steer_vectors_cpu.py shows that each hits its site) --------
+def steered_lines(every=1):
+    """whole rows: `permute` on every steered state and `hq` on every steered triple"""
+    c = PV.p256()
+    lines, want = [], []
+    for name, _ in S.POSEIDON_FAMILIES:
+        for v in S.poseidon_families()[name][::every]:
+            lines.append("permute " + "".join(fe(x) for x in v.state))
+            want.append("".join(fe(x) for x in PV.permute(c, list(v.state))))
+    for v in S.hq_vectors()[::every]:
+        lines.append("hq " + "".join(fe(x) for x in v.q))
+        want.append(PV.hq(*v.q).hex())
+    return lines, want
+
+
+def site_lines(every=1):
+    """the steered site alone, as one `add`, `sqr` or `mul` on the values it meets"""
+    c = PV.p256()
+    lines, want = [], []
+    vecs = [v for name, _ in S.POSEIDON_FAMILIES for v in S.poseidon_families()[name]]
+    for v in vecs[::every]:
+        a = [(x + k) % P for x, k in zip(v.state, c.rc[:3])]
+        s = [pow(x, 5, P) for x in a]
+        kind, i = v.site[0], v.site[1]
+        if kind == "add_rc":
+            ops = [("add", v.state[i], c.rc[i])]
+        elif kind == "sqr":
+            ops = [("sqr", a[i]), ("pow5", a[i])]
+        elif kind == "sqr_sqr":
+            ops = [("sqr", a[i] * a[i] % P), ("pow5", a[i])]
+        elif kind == "mul_a4_a":
+            ops = [("mul", pow(a[i], 4, P), a[i]), ("pow5", a[i])]
+        elif kind == "mds_mul":
+            ops = [("mul", c.mds[i // 3][i % 3], s[i % 3])]
+        else:
+            t = [c.mds[i][j] * s[j] % P for j in range(3)]
+            ops = [("add", t[0], t[1])] if v.site[2] == 0 else [("add", (t[0] + t[1]) % P, t[2])]
+        for op in ops:
+            x = op[1:]
+            lines.append(op[0] + " " + " ".join(fe(y) for y in x))
+            want.append(fe({"add": lambda: x[0] + x[1], "mul": lambda: x[0] * x[1], "sqr": lambda: x[0] * x[0], "pow5": lambda: pow(x[0], 5, P)}[op[0]]() % P))
+    # P-256's coordinates at the entry of p256_read_point and p256_on_curve: from_words (inside `sqr`), x + x and 2x + x
+    for v in S.p256_families()["entry_points"][::every]:
+        f = S.facts(v)
+        if "point" in f and v.kind == "tu":
+            x, y = f["point"]
+            lines += ["sqr " + fe(x), "sqr " + fe(y), "add %s %s" % (fe(x), fe(x)), "add %s %s" % (fe(2 * x % P), fe(x))]
+            want += [fe(x * x % P), fe(y * y % P), fe(2 * x % P), fe(3 * x % P)]
+    return lines, want
+
+
+def test_steered_states_and_triples_byte_for_byte(exe):
+    lines, want = steered_lines()
+    assert len(lines) == sum(S.POSEIDON_COUNTS.values()) == 33
+    got = ask_all(exe, lines)
+    for line, g, w in zip(lines, got, want):
+        assert g == w, line[:80]
+
+
+def test_steered_sites_one_operation_each(exe):
+    lines, want = site_lines()
+    assert len(lines) == 9 + 9 * 2 + 3 + 6 + 10 * 4
+    got = ask_all(exe, lines)
+    for line, g, w in zip(lines, got, want):
+        assert g == w, line
+
+
 def test_sanitized_build_answers_the_same(tmp_path):
     path = str(tmp_path / "test_poseidon_p256_san")
     r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", path, SRC],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     lines, want = field_lines(500)
-    a, b = poseidon_lines(16)
-    lines, want = lines + a + ["consts"], want + b + ["".join(fe(x) for x in PV.table())]
+    for a, b in (poseidon_lines(16), steered_lines(3), site_lines(3)):
+        lines, want = lines + a, want + b
+    lines, want = lines + ["consts"], want + ["".join(fe(x) for x in PV.table())]
     assert ask_all(path, lines) == want
 
 
