@@ -316,6 +316,12 @@ _SIGNATURES = {
     "cg_p256_tu_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_p256_rtu_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cg_p256_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "cg_t256_gens_load": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cg_t256_gens_free": (None, [C.c_void_p]),
+    "cg_t256_gens_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cg_t256_commit_rows_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cg_hyrax_commit_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "cg_t256_commit_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "cg_revealed_digest_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p]),
     "cg_prepare_verifying_key": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
@@ -2257,6 +2263,65 @@ class RangeVerifyingKey(_LatencyMode, _RangeSlots, _Handle):
         _check(lib().cg_range_vk_load(C.byref(self._h), _ptr(b) if b.size else None, b.size, self.n_bits, device))
         if latency:
             self.set_latency(True)
+
+
+class T256Gens(_Handle):
+    """`MultiCommitGens { G, h }` of spartan_t256 (forks/Spartan-t256/src/commitments.rs) resident on the current GPU as
+    fixed-base tables (cg_t256_gens_load): g_xy n_gens x 64 B and h_xy 64 B, uncompressed T-256 points, x ‖ y big-endian.
+    The byte forms of T-256 are UNVERIFIED readings of halo2curves (include/crescent_gpu.h).  A coordinate >= p_T, a point
+    off the curve or the identity raises CrescentGpuError before the GPU is touched.  Use as a context manager or close()."""
+    _free = "cg_t256_gens_free"
+
+    def __init__(self, g_xy, h_xy):
+        g, h = _u8(g_xy), _u8(h_xy, 64)
+        if g.size % 64:
+            raise ValueError("g_xy is n_gens x 64 bytes")
+        self._h = C.c_void_p()
+        _check(lib().cg_t256_gens_load(_ptr(g) if g.size else None, g.size // 64, _ptr(h), C.byref(self._h)))
+        self.n_gens = g.size // 64
+
+    @property
+    def table_bytes(self) -> int:
+        """what the set's n_gens + 1 tables take on the device (cg_t256_gens_info)"""
+        n, b = C.c_uint64(), C.c_uint64()
+        _check(lib().cg_t256_gens_info(self._h, C.byref(n), C.byref(b)))
+        return int(b.value)
+
+    def commit_rows_batch(self, scalars, blinds):
+        """cg_t256_commit_rows_batch: `Vec<Scalar>::commit` (commitments.rs:88-99) for n rows - scalars n x n_gens x 32 B and
+        blinds n x 32 B, little-endian, below q.  Returns (out33 (n, 33) compressed points, status (n,)); a row with a scalar
+        or blind >= q is CG_SHOW_MALFORMED and zero bytes.  n_gens = 1 is `Scalar::commit`."""
+        s, b = _u8(scalars), _u8(blinds)
+        if b.size % 32 or s.size != b.size * self.n_gens:
+            raise ValueError("blinds are n x 32 bytes and scalars n x n_gens x 32 bytes")
+        n = b.size // 32
+        out, status = np.zeros((n, 33), np.uint8), np.zeros(n, np.uint8)
+        _check(lib().cg_t256_commit_rows_batch(self._h, _ptr(s) if n else None, _ptr(b) if n else None, n, _ptr(out), _ptr(status)))
+        return out, status
+
+    def hyrax_commit_batch(self, num_vars: int, vars_, blinds):
+        """cg_hyrax_commit_batch: `DensePolynomial::commit` (dense_mlpoly.rs:181-206) for n proofs of 2^num_vars evaluations
+        each, as L x R matrices with L = 2^(num_vars // 2) and R = n_gens: vars_ n x 2^num_vars x 32 B, blinds n x L x 32 B.
+        Returns (out33 (n, L, 33), status (n,)); a proof with a scalar or blind >= q is CG_SHOW_MALFORMED and all its rows
+        zero bytes."""
+        v, b = _u8(vars_), _u8(blinds)
+        num_vars = int(num_vars)
+        if not 0 <= num_vars < 63:
+            raise ValueError("num_vars")
+        L = 1 << (num_vars // 2)
+        if b.size % (32 * L) or v.size != (b.size // L) << num_vars:
+            raise ValueError("blinds are n x L x 32 bytes and vars_ n x 2^num_vars x 32 bytes")
+        n = b.size // (32 * L)
+        out, status = np.zeros((n, L, 33), np.uint8), np.zeros(n, np.uint8)
+        _check(lib().cg_hyrax_commit_batch(self._h, num_vars, _ptr(v) if n else None, _ptr(b) if n else None, n, _ptr(out), _ptr(status)))
+        return out, status
+
+    def commit_last_kernel_ms(self) -> Tuple[float, float, int]:
+        """cg_t256_commit_last_kernel_ms: HIP-event milliseconds of the last call on this set - the check of the scalars, the
+        group stage (the rows' sums and their normalisation) - and how many lanes shared a row in its last chunk"""
+        ms, w = (C.c_float * 2)(), C.c_uint32()
+        _check(lib().cg_t256_commit_last_kernel_ms(self._h, ms, C.byref(w)))
+        return float(ms[0]), float(ms[1]), int(w.value)
 
 
 @dataclass

@@ -28,7 +28,7 @@ CALLER_BIN = os.path.join(HERE, "..", "integration", "c", "crescent_prove")
 THROUGHPUT_SRC = os.path.join(HERE, "..", "integration", "c", "crescent_throughput.c")
 THROUGHPUT_BIN = os.path.join(HERE, "..", "integration", "c", "crescent_throughput")
 
-HIP_SOURCES = ["ntt.hip", "wmap29.hip", "msm.hip", "ecntt.hip", "prover.hip", "unit.hip", "setup.hip", "r1cs.hip", "serialize.hip", "verify.hip", "rangeproof.hip", "rangeverify.hip", "transcript.hip", "devicelink.hip", "devicelinkmake.hip", "p256tu.hip"]
+HIP_SOURCES = ["ntt.hip", "wmap29.hip", "msm.hip", "ecntt.hip", "prover.hip", "unit.hip", "setup.hip", "r1cs.hip", "serialize.hip", "verify.hip", "rangeproof.hip", "rangeverify.hip", "transcript.hip", "devicelink.hip", "devicelinkmake.hip", "p256tu.hip", "t256commit.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # A/B aid: extra compiler flags (e.g. CG_HIPCC_EXTRA="-DCG_MUL2_ONE_CHAIN"); a change of flags rebuilds every object
 EXTRA_FLAGS = os.environ.get("CG_HIPCC_EXTRA", "").split()

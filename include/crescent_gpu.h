@@ -1203,6 +1203,61 @@ int cg_p256_rtu_batch(cg_pvk* k, const uint8_t* q_xy, const uint8_t* sig, const 
  * terms, the finishing stage - by HIP events, summed over the chunks; *uploads: how often the table of G went up to this
  * handle, 0 before the first call that needs it and 1 ever after.  (No counterpart in the reference.) */
 int cg_p256_last_kernel_ms(cg_pvk* k, float ms[3], uint32_t* uploads);
+
+/* ---- pi2's witness commitment: the group T-256 and Hyrax rows ----------------------------------------------------------------
+ * T-256 (forks/halo2curves/src/t256/) is the group every commitment of `spartan_t256` lives in: y^2 = x^3 - 3x + b over the
+ * prime p_T of t256/fp.rs:10, of prime order q = P-256's base prime (csrc/t256.hpp over csrc/ft256.hpp).
+ * Byte forms, as halo2curves writes them (serde.rs:174-319, src/derive/curve.rs:69-73 and :139-181,
+ * derive/src/field/mod.rs:326-344 and :470-476).  UNVERIFIED: the reference pins no T-256 bytes (t256/curve.rs:129 says so
+ * itself), so these are readings of its code that no byte made by it has confirmed; each has one reader or writer in
+ * csrc/t256.hpp and one in tests/t256_vectors.py.
+ *   a coordinate       32 B big-endian
+ *   a scalar           32 B little-endian, below q: the form cg_poseidon_p256_permute_batch takes for the same field
+ *   uncompressed point x ‖ y, 64 B; the identity is 64 zero bytes
+ *   compressed point   33 B: byte 0 has bit 7 set when y is odd and bit 6 set for the identity (whose bit 7 is clear),
+ *                      bytes 1..33 are x big-endian; the identity is 0x40 and 32 zero bytes */
+typedef struct cg_t256_gens cg_t256_gens;
+/* Replaces: what `MultiCommitGens { G, h }` (forks/Spartan-t256/src/commitments.rs) is to the commitments below: a set of
+ *           n_gens generators and the blinding generator h, held as fixed-base tables (8-bit windows, 522 240 B a point) that
+ *           are built on the host and stay on the current device.
+ * NOT done here: `MultiCommitGens::new` (SHAKE-256 and hash-to-curve), which stays on the host; the host hands over the points.
+ * g_xy: n_gens x 64 B, h_xy: 64 B, uncompressed points (UNVERIFIED byte form, above).
+ * Errors, all reported before any HIP call: a null argument; n_gens < 1 or so large that the n_gens + 1 tables pass 1 GiB
+ * (n_gens > 2055; 257 tables are 134 MB); a coordinate >= p_T (the reference reduces it silently; this library fails closed on
+ * non-canonical input); a point off the curve; the identity - each CG_ERR_INVALID_ARGUMENT, naming the point. */
+int cg_t256_gens_load(const uint8_t* g_xy, uint64_t n_gens, const uint8_t* h_xy, cg_t256_gens** out);
+void cg_t256_gens_free(cg_t256_gens* g);
+/* *n_gens as loaded, *table_bytes what the set's tables take on the device.  (No counterpart in the reference.) */
+int cg_t256_gens_info(const cg_t256_gens* g, uint64_t* n_gens, uint64_t* table_bytes);
+/* Replaces: `Vec<Scalar>::commit` (forks/Spartan-t256/src/commitments.rs:88-99) for n_rows rows over one set of generators:
+ *           row i is sum_j scalars[i][j] · G[j] + blinds[i] · h, written compressed (UNVERIFIED byte form, above).  The row
+ *           length is the set's n_gens - the reference asserts equality -; with n_gens = 1 this is `Scalar::commit` (:81-86).
+ * scalars: n_rows x n_gens x 32 B.    blinds: n_rows x 32 B.    out33: n_rows x 33 B.
+ * status: n_rows x CG_SHOW_MADE / CG_SHOW_MALFORMED.  MALFORMED means that row only, its 33 bytes zero: a scalar of the row or
+ *         its blind is >= q.  A row whose sum is the identity is MADE, and 0x40 with 32 zero bytes.
+ * Errors, reported before any HIP call and with no output touched: a null argument.  n_rows = 0 is CG_OK.  The library draws
+ * no randomness: the blinds are the caller's, from its `RandomTape`.  Runs on the handle's stream under its lock, in chunks of
+ * at most 16384 rows and 64 MB of scalars; a chunk of cg_hyrax_commit_batch holds whole proofs and never less than one, so at
+ * num_vars = 22, the one shape whose proof is larger (2^22 scalars), it is that proof's 128 MB.  Measured on an MI355X: profiles/t256_commit.md. */
+int cg_t256_commit_rows_batch(cg_t256_gens* g, const uint8_t* scalars, const uint8_t* blinds, uint64_t n_rows, uint8_t* out33,
+                              uint8_t* status);
+/* Replaces: `DensePolynomial::commit` (forks/Spartan-t256/src/dense_mlpoly.rs:181-206, `commit_inner` :151-163), the first
+ *           step of `R1CSProof::prove` (r1csproof.rs:163-173), for n proofs: the 2^num_vars evaluations as an L x R matrix,
+ *           L = 2^(num_vars / 2) and R = 2^(num_vars - num_vars / 2) (`compute_factored_lens`, :88-90), and one commitment per
+ *           row - the kernels of cg_t256_commit_rows_batch on n · L rows, which writes the same bytes for the same data.
+ * NOT done here: the rest of pi2 - the sum-checks, the dot-product and evaluation proofs, the verifier.
+ * vars: n x 2^num_vars x 32 B.    blinds: n x L x 32 B.    out33: n x L x 33 B, in the order `PolyCommitment.C` has
+ * (UNVERIFIED byte form, above).
+ * status: n x CG_SHOW_MADE / CG_SHOW_MALFORMED, one per PROOF: a scalar or blind of the proof is >= q, and all its L rows are
+ *         zero bytes; no other proof is touched.
+ * Errors, reported before any HIP call and with no output touched: a null argument; R != the set's n_gens.  n = 0 is CG_OK.
+ * Scheduling as for cg_t256_commit_rows_batch; a chunk holds whole proofs. */
+int cg_hyrax_commit_batch(cg_t256_gens* g, uint32_t num_vars, const uint8_t* vars, const uint8_t* blinds, uint64_t n, uint8_t* out33,
+                          uint8_t* status);
+/* Diagnostic: what the kernels of the handle's last cg_t256_commit_rows_batch or cg_hyrax_commit_batch took - ms[0] the check
+ * of the scalars, ms[1] the group stage (the rows' sums and their normalisation) - by HIP events, summed over the chunks; *lanes_per_row: how many lanes shared a row in its
+ * last chunk (csrc/t256commit.hip has the rule), 0 before the first call.  (No counterpart in the reference.) */
+int cg_t256_commit_last_kernel_ms(cg_t256_gens* g, float ms[2], uint32_t* lanes_per_row);
 /* Replaces: the digests of `revealed_preimages` that `verify_show` places among the public inputs (creds/src/lib.rs:590-603):
  *           per hashed attribute SHA-256 of the preimage string and its first 31 bytes through `bits_to_num`
  *           (creds/src/utils.rs:78-94), as the canonical Fr a host places into `revealed`.  Host only, on the library's worker

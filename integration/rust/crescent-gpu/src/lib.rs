@@ -1650,3 +1650,92 @@ impl Drop for GpuRangeVerifyingKey {
         unsafe { sys::cg_range_vk_free(self.h) }
     }
 }
+
+/// `MultiCommitGens { G, h }` of spartan_t256 (forks/Spartan-t256/src/commitments.rs) resident on the GPU as fixed-base
+/// tables (`cg_t256_gens_load`), and on it the commitments of pi2's witness.  Points are uncompressed, x ‖ y big-endian;
+/// scalars 32 B little-endian; commitments come back compressed, 33 B.  These byte forms are UNVERIFIED readings of
+/// halo2curves (include/crescent_gpu.h): a caller converts with halo2curves' own `to_bytes` / `from_bytes` and compares once.
+pub struct GpuT256Gens {
+    h: *mut sys::cg_t256_gens,
+    n_gens: usize,
+}
+unsafe impl Send for GpuT256Gens {}
+unsafe impl Sync for GpuT256Gens {} // calls on one handle serialise inside the library
+
+impl GpuT256Gens {
+    /// `g_xy`: n_gens x 64 B, `h_xy`: 64 B.  `MultiCommitGens::new` itself stays on the host, which has the points.
+    pub fn load(g_xy: &[u8], h_xy: &[u8]) -> Result<Self, SynthesisError> {
+        if g_xy.len() % 64 != 0 || h_xy.len() != 64 {
+            return Err(SynthesisError::AssignmentMissing);
+        }
+        let mut h = std::ptr::null_mut();
+        let rc = unsafe { sys::cg_t256_gens_load(g_xy.as_ptr(), (g_xy.len() / 64) as u64, h_xy.as_ptr(), &mut h) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok(GpuT256Gens { h, n_gens: g_xy.len() / 64 })
+    }
+
+    /// (n_gens, bytes of the set's tables on the device) (`cg_t256_gens_info`)
+    pub fn info(&self) -> Result<(u64, u64), SynthesisError> {
+        let (mut n, mut b) = (0u64, 0u64);
+        let rc = unsafe { sys::cg_t256_gens_info(self.h, &mut n, &mut b) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((n, b))
+    }
+
+    /// `Vec<Scalar>::commit` (commitments.rs:88-99) for n rows (`cg_t256_commit_rows_batch`): `scalars` n x n_gens x 32 B,
+    /// `blinds` n x 32 B.  Returns (n x 33 B, n status bytes: CG_SHOW_MADE, or CG_SHOW_MALFORMED and zero bytes for a row with
+    /// a scalar or blind >= q).  With n_gens = 1 this is `Scalar::commit`.
+    pub fn commit_rows_batch(&self, scalars: &[u8], blinds: &[u8]) -> Result<(Vec<u8>, Vec<u8>), SynthesisError> {
+        if blinds.len() % 32 != 0 || scalars.len() != blinds.len() * self.n_gens {
+            return Err(SynthesisError::AssignmentMissing);
+        }
+        let n = blinds.len() / 32;
+        let (mut out, mut status) = (vec![0u8; 33 * n], vec![0u8; n]);
+        let rc = unsafe { sys::cg_t256_commit_rows_batch(self.h, scalars.as_ptr(), blinds.as_ptr(), n as u64, out.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((out, status))
+    }
+
+    /// `DensePolynomial::commit` (dense_mlpoly.rs:181-206) for n proofs (`cg_hyrax_commit_batch`): `vars` n x 2^num_vars x 32 B,
+    /// `blinds` n x L x 32 B with L = 2^(num_vars / 2).  Returns (n x L x 33 B in `PolyCommitment.C`'s order, n status bytes,
+    /// one per proof).
+    pub fn hyrax_commit_batch(&self, num_vars: u32, vars: &[u8], blinds: &[u8]) -> Result<(Vec<u8>, Vec<u8>), SynthesisError> {
+        if num_vars >= 63 {
+            return Err(SynthesisError::AssignmentMissing);
+        }
+        let l = 1usize << (num_vars / 2);
+        if blinds.len() % (32 * l) != 0 || vars.len() != (blinds.len() / l) << num_vars {
+            return Err(SynthesisError::AssignmentMissing);
+        }
+        let n = blinds.len() / (32 * l);
+        let (mut out, mut status) = (vec![0u8; 33 * l * n], vec![0u8; n]);
+        let rc = unsafe { sys::cg_hyrax_commit_batch(self.h, num_vars, vars.as_ptr(), blinds.as_ptr(), n as u64, out.as_mut_ptr(), status.as_mut_ptr()) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((out, status))
+    }
+
+    /// (`cg_t256_commit_last_kernel_ms`) HIP-event milliseconds of the last call - the check, the group stage (the rows' sums
+    /// and their normalisation) - and how many lanes shared a row in its last chunk
+    pub fn commit_last_kernel_ms(&self) -> Result<([f32; 2], u32), SynthesisError> {
+        let (mut ms, mut lanes) = ([0f32; 2], 0u32);
+        let rc = unsafe { sys::cg_t256_commit_last_kernel_ms(self.h, ms.as_mut_ptr(), &mut lanes) };
+        if rc != 0 {
+            return Err(map_err(rc));
+        }
+        Ok((ms, lanes))
+    }
+}
+
+impl Drop for GpuT256Gens {
+    fn drop(&mut self) {
+        unsafe { sys::cg_t256_gens_free(self.h) }
+    }
+}

@@ -231,6 +231,7 @@ pub enum cg_qap_ctx {}
 pub enum cg_pvk {}
 pub enum cg_range_pk {}
 pub enum cg_range_vk {}
+pub enum cg_t256_gens {}
 
 extern "C" {
     pub fn cg_init(n_devices: c_int, device_ids: *const c_int) -> c_int;
@@ -698,5 +699,19 @@ extern "C" {
         status: *mut u8,
     ) -> c_int;
     pub fn cg_p256_last_kernel_ms(k: *mut cg_pvk, ms: *mut f32, uploads: *mut u32) -> c_int;
+    pub fn cg_t256_gens_load(g_xy: *const u8, n_gens: u64, h_xy: *const u8, out: *mut *mut cg_t256_gens) -> c_int;
+    pub fn cg_t256_gens_free(g: *mut cg_t256_gens);
+    pub fn cg_t256_gens_info(g: *const cg_t256_gens, n_gens: *mut u64, table_bytes: *mut u64) -> c_int;
+    pub fn cg_t256_commit_rows_batch(g: *mut cg_t256_gens, scalars: *const u8, blinds: *const u8, n_rows: u64, out33: *mut u8, status: *mut u8) -> c_int;
+    pub fn cg_hyrax_commit_batch(
+        g: *mut cg_t256_gens,
+        num_vars: u32,
+        vars: *const u8,
+        blinds: *const u8,
+        n: u64,
+        out33: *mut u8,
+        status: *mut u8,
+    ) -> c_int;
+    pub fn cg_t256_commit_last_kernel_ms(g: *mut cg_t256_gens, ms: *mut f32, lanes_per_row: *mut u32) -> c_int;
     pub fn cg_revealed_digest_batch(data: *const u8, offsets: *const u64, n_items: u64, out: *mut u8) -> c_int;
 }
