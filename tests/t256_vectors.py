@@ -132,6 +132,21 @@ class Gens:
         return compressed(acc)
 
 
+class PointGens(Gens):
+    """generators given as points, with no known logarithm (tests/t256_steer_vectors.py chooses their coordinates): a row's
+    expected value is the sum term by term, a scalar multiplication per non-zero term"""
+
+    def __init__(self, points, h):
+        assert all(p is not None and on_curve(p) for p in list(points) + [h])
+        self.points, self.h, self.n = list(points), h, len(points)
+
+    def commit(self, z, blind):
+        assert len(z) == self.n
+        if any(not 0 <= v < Q for v in z) or not 0 <= blind < Q:
+            return MALFORMED, ZERO_ROW
+        return MADE, self.commit_term_by_term(z, blind)
+
+
 def make_gens(seed, n):
     rng = random.Random(seed)
     return Gens([rng.randrange(1, Q) for _ in range(n)], rng.randrange(1, Q))

@@ -25,6 +25,9 @@ FILL = 0xA5
 
 
 CHUNK_ROWS = 1 << 14        # csrc/t256commit.hip's T256_CHUNK_ROWS: the rows of one launch set
+CHUNK_SCALARS = 1 << 21     # its T256_CHUNK_SCALARS: the scalars of one launch set
+TARGET_WAVES = 2048         # its T256_TARGET_WAVES: the waves below which a row keeps its lanes
+COMMIT_SOURCE = os.path.join(ROOT, "crescent-credentials_amd", "csrc", "t256commit.hip")
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -104,6 +107,45 @@ def test_rows_call_byte_for_byte(cc, sets, n):
     assert all(st == MADE for st, _ in want)
     V.assert_both_parities([r for _, r in want])
     assert handle.commit_last_kernel_ms()[2] == min(64, 1 << n.bit_length())
+
+
+@pytest.mark.parametrize("n", [3, 5, 12, 31, 33, 63, 65])
+def test_rows_call_on_generator_counts_that_are_no_power_of_two(cc, sets, n):
+    """3 and 63 make the n + 1 terms exactly W; 12 is the first count at sixteen lanes a row (two windows of a term a lane), 31
+    has 32 lanes; 33 and 65 run a whole wave a row with the term index wrapping past W at an odd stride.  The blind sits on
+    lane n mod W, and the scan's four-at-a-time steps meet the end of (n + 1) 2^log_per digits off a multiple of four"""
+    gens, handle = sets(n)
+    rng = random.Random(0x5100 + n)
+    rows = [([rng.randrange(Q) for _ in range(n)], rng.randrange(Q)) for _ in range(3)]
+    rows += [(V.mixed_scalars(rng, n), rng.randrange(Q)) for _ in range(3)]
+    rows += [([0] * n, rng.randrange(1, Q)), ([0] * (n - 1) + [rng.randrange(1, Q)], 0), ([rng.randrange(1, Q)] + [0] * (n - 1), 0)]
+    want = check_rows(cc, gens, handle, rows)
+    assert all(st == MADE for st, _ in want)
+    V.assert_both_parities([r for _, r in want])
+    assert handle.commit_last_kernel_ms()[2] == min(64, 1 << n.bit_length())
+
+
+def test_one_hot_digits_at_sixteen_lanes_a_row(cc, sets):
+    """Twelve generators and the blind are 13 terms, W = 16: lane t has windows (t - j) mod 16 and that + 16 of term j.  One row
+    for every term j and window w, whose only non-zero byte is byte w of term j's scalar: a wrong map from lane to window, or
+    a wrong offset into the tables, fails at a named (j, w)"""
+    n = 12
+    gens, handle = sets(n)
+    rng = random.Random(0x0E07)
+    cells = [(j, w) for j in range(n + 1) for w in range(32)]
+    digits = [rng.randrange(1, 256) for _ in cells]
+    lo, hi = rng.sample(range(len(cells)), 2)
+    digits[lo], digits[hi] = 1, 255
+    assert len(cells) == 416 and 1 in digits and 255 in digits and all(1 <= d <= 255 for d in digits)
+    terms = [[d << (8 * w) if i == j else 0 for i in range(n + 1)] for (j, w), d in zip(cells, digits)]
+    ks = gens.ks + [gens.kh]
+    want = [V.compressed(V.mul(d * ks[j] << (8 * w), V.G)) for (j, w), d in zip(cells, digits)]
+    assert want[5] == gens.commit(terms[5][:n], terms[5][n])[1] and want[-1] == gens.commit(terms[-1][:n], terms[-1][n])[1]
+    out, status = call_rows(cc, handle, pack([v for t in terms for v in t[:n]]), pack([t[n] for t in terms]), len(cells))
+    assert handle.commit_last_kernel_ms()[2] == 16
+    for i, (j, w) in enumerate(cells):
+        assert status[i] == MADE and out[i].tobytes() == want[i], ("term %d window %d digit %d" % (j, w, digits[i]), out[i].tobytes().hex(), want[i].hex())
+    V.assert_both_parities(want)
 
 
 # ---- Hyrax ---------------------------------------------------------------------------------------------------------------------
@@ -199,6 +241,29 @@ def test_a_malformed_scalar_takes_its_whole_proof_and_no_neighbour(cc, sets):
     V.assert_both_parities([out[i, j].tobytes() for i in (0, 2) for j in range(L)])
 
 
+def test_the_check_kernel_past_its_first_sixty_four_elements(cc, sets):
+    """num_vars = 7 is 128 scalars and 8 blinds a proof, and k_t256_check's wave takes them 64 at a time: elements 64 and 127
+    (scalars) and 128 and 135 (blinds 0 and 7) are met on the second and third trip only.  Four proofs are bad in exactly one
+    of these places, two are good"""
+    num_vars = 7
+    L, R = V.factored_lens(num_vars)
+    assert (L, R) == (8, 16)
+    gens, handle = sets(R)
+    rng = random.Random(0xBAD3)
+    proofs = [(V.mixed_scalars(rng, L * R) if i % 2 else [rng.randrange(Q) for _ in range(L * R)], [rng.randrange(Q) for _ in range(L)]) for i in range(6)]
+    proofs[0][0][64] = Q
+    proofs[2][0][127] = (1 << 256) - 1
+    proofs[3][1][0] = (1 << 256) - 1
+    proofs[5][1][7] = Q
+    want = [V.hyrax(gens, num_vars, v, b) for v, b in proofs]
+    assert [st for st, _ in want] == [MALFORMED, MADE, MALFORMED, MALFORMED, MADE, MALFORMED]
+    assert all(rows == V.ZERO_ROW * L for st, rows in want if st == MALFORMED)
+    out, status = call_hyrax(cc, handle, num_vars, pack([x for v, _ in proofs for x in v]), pack([x for _, b in proofs for x in b]), 6)
+    for i, (st, rows) in enumerate(want):
+        assert status[i] == st and out[i].tobytes() == rows, i
+    V.assert_both_parities([out[i, j].tobytes() for i in (1, 4) for j in range(L)])
+
+
 # ---- chunks and the choice of lanes per row -----------------------------------------------------------------------------------------
 def cycled(gens, rows, count):
     """`count` rows that cycle through the distinct `rows`: the arrays, and what the oracle makes of the distinct ones"""
@@ -215,7 +280,7 @@ def test_a_call_that_crosses_a_chunk(cc, sets):
     """n_gens = 1 and chunk + 3 rows that cycle through eight distinct inputs, one of them malformed: the oracle computes eight"""
     gens, handle = sets(1)
     chunk = CHUNK_ROWS
-    assert "constexpr uint64_t T256_CHUNK_ROWS = 1u << 14;" in open(os.path.join(ROOT, "crescent-credentials_amd", "csrc", "t256commit.hip")).read()
+    assert "constexpr uint64_t T256_CHUNK_ROWS = 1u << 14;" in open(COMMIT_SOURCE).read()
     rng = random.Random(0xC4)
     rows = [([rng.randrange(Q)], rng.randrange(Q)) for _ in range(5)] + [([0], 0), ([Q], 1), ([1], 0)]
     n = chunk + 3
@@ -242,6 +307,113 @@ def test_a_large_batch_shares_a_row_among_fewer_lanes(cc, sets):
     small, _ = call_rows(cc, handle, scal[:8 * 128 * 32], blind[:8 * 32], 8)
     assert handle.commit_last_kernel_ms()[2] == 64 and small.tobytes() == out[:8].tobytes()
     V.assert_both_parities([r for _, r in want])
+
+
+def lanes_of(rows, n_terms):
+    """csrc/t256commit.hip's pick_log_w, restated: the least power of two >= n_terms, at most 64, halved while the rows still
+    make TARGET_WAVES waves of 64 lanes at half the width"""
+    log_w = 0
+    while log_w < 6 and (1 << log_w) < n_terms:
+        log_w += 1
+    while log_w > 0 and (rows << (log_w - 1)) >> 6 >= TARGET_WAVES:
+        log_w -= 1
+    return 1 << log_w
+
+
+def test_the_halved_widths_on_many_terms(cc, sets):
+    """33 generators are 34 terms, 64 lanes a row for a small call.  A call halves W while rows · W / 2 / 64 >= 2048 waves:
+    4096 rows · 32 / 64 = 2048, so 4096 rows run at W = 32 (and 4096 · 16 / 64 = 1024 stops there); 8192 rows go on to W = 16
+    (8192 · 16 / 64 = 2048, 8192 · 8 / 64 = 1024); 16384 rows to W = 8 (16384 · 8 / 64 = 2048, 16384 · 4 / 64 = 1024).
+    W = 32 with 34 terms is the lane-to-window map with log_per = 0 and a term index that wraps past W; W = 16 has two windows
+    of a term a lane, W = 8 four.  All three are one chunk.  The same bytes as at 64 lanes a row"""
+    n_gens = 33
+    gens, handle = sets(n_gens)
+    assert "constexpr uint64_t T256_TARGET_WAVES = 2048;" in open(COMMIT_SOURCE).read()
+    assert [lanes_of(r, n_gens + 1) for r in (8, 4095, 4096, 8191, 8192, 16383, 16384)] == [64, 64, 32, 32, 16, 16, 8]
+    rng = random.Random(0x1A8)
+    rows = [([rng.randrange(Q) for _ in range(n_gens)], rng.randrange(Q)) for _ in range(2)]
+    rows += [(V.mixed_scalars(rng, n_gens), rng.randrange(Q)) for _ in range(5)] + [([0] * n_gens, 0)]
+    scal, blind, want_out, want_status, want = cycled(gens, rows, 16384)
+    assert (want_status == MADE).all() and want[7][1] == V.IDENTITY_COMPRESSED
+    V.assert_both_parities([r for _, r in want])
+    small, small_status = call_rows(cc, handle, scal[:8 * n_gens * 32], blind[:8 * 32], 8)
+    assert handle.commit_last_kernel_ms()[2] == 64
+    assert (small_status == MADE).all() and (small.reshape(-1) == want_out[:8 * 33]).all()
+    for n, lanes in ((4096, 32), (8192, 16), (16384, 8)):
+        out, status = call_rows(cc, handle, scal[:n * n_gens * 32], blind[:n * 32], n)
+        assert handle.commit_last_kernel_ms()[2] == lanes, n
+        assert (status == MADE).all() and (out.reshape(-1) == want_out[:n * 33]).all(), n
+        assert out[:8].tobytes() == small.tobytes(), n
+
+
+def cycled_proofs(gens, num_vars, proofs, order):
+    """the proofs `proofs[i] for i in order` as one call's arrays, and what the oracle makes of the distinct ones:
+    (vars, blinds, expected bytes, expected statuses, want)"""
+    want = [V.hyrax(gens, num_vars, v, b) for v, b in proofs]
+    vars_ = [pack(v) for v, _ in proofs]
+    blinds = [pack(b) for _, b in proofs]
+    outs = [np.frombuffer(rows, np.uint8) for _, rows in want]
+    return (np.concatenate([vars_[i] for i in order]), np.concatenate([blinds[i] for i in order]), np.concatenate([outs[i] for i in order]),
+            np.array([want[i][0] for i in order], np.uint8), want)
+
+
+def test_a_hyrax_call_that_crosses_a_row_bound_chunk(cc, sets):
+    """num_vars = 3 is two rows of four scalars a proof: a chunk is min(16384 / 2, 2^21 / 8) = 8192 proofs, bound by its rows.
+    8192 + 5 proofs cycle through seven distinct ones; 7 does not divide 8192, so the second chunk starts at another place of
+    the cycle than the first: proof 8192 is the cycle's place 2.  Place 2 is malformed by a scalar, place 3 all zero with
+    zero blinds (the identity's bytes), place 5 malformed by a blind: the second chunk, places 2 to 6, holds all three.  What
+    the second chunk reads (scalars and blinds from proof 8192 on) and writes (rows from 2 · 8192 on, statuses from 8192 on)
+    is offset by whole proofs, and its flags are indexed from the chunk's first proof"""
+    num_vars = 3
+    L, R = V.factored_lens(num_vars)
+    gens, handle = sets(R)
+    per_chunk = min(CHUNK_ROWS // L, CHUNK_SCALARS // (L * R))
+    assert (L, R, per_chunk) == (2, 4, 8192) and CHUNK_ROWS // L < CHUNK_SCALARS // (L * R)
+    rng = random.Random(0xC5)
+    proofs = [([rng.randrange(Q) for _ in range(L * R)], [rng.randrange(Q) for _ in range(L)]) for _ in range(7)]
+    proofs[1] = (V.mixed_scalars(rng, L * R), proofs[1][1])
+    proofs[2][0][5] = Q
+    proofs[3] = ([0] * (L * R), [0] * L)
+    proofs[5][1][1] = (1 << 256) - 1
+    n = per_chunk + 5
+    order = [i % 7 for i in range(n)]
+    vars_, blinds, want_out, want_status, want = cycled_proofs(gens, num_vars, proofs, order)
+    assert [st for st, _ in want] == [MADE, MADE, MALFORMED, MADE, MADE, MALFORMED, MADE] and want[3][1] == V.IDENTITY_COMPRESSED * L
+    assert order[per_chunk] == 2 and order[per_chunk:] == [2, 3, 4, 5, 6] and order[:5] != order[per_chunk:]
+    assert {MADE, MALFORMED} == set(want_status[per_chunk:].tolist())
+    out, status = call_hyrax(cc, handle, num_vars, vars_, blinds, n)
+    assert (status == want_status).all()
+    assert out.size == n * L * 33 and (out.reshape(-1) == want_out).all()
+    V.assert_both_parities([rows[33 * j:33 * j + 33] for _, rows in want for j in range(L)])
+
+
+def test_a_hyrax_call_that_crosses_a_scalar_bound_chunk(cc, sets):
+    """num_vars = 16 is 256 rows of 256 scalars a proof: a chunk is min(16384 / 256, 2^21 / 65536) = min(64, 32) = 32 proofs,
+    bound by its scalars, so the 33rd proof is a chunk of its own.  The proofs cycle through three distinct ones of a circuit's
+    mix of wires, the second of them malformed (the oracle's 2 · 256 rows take three seconds; a fourth proof would add half as
+    much again): the 33rd is the third distinct proof, so its rows are neither those of proof 0 nor those of proof 1, which
+    a chunk-relative offset would read or write"""
+    num_vars = 16
+    L, R = V.factored_lens(num_vars)
+    gens, handle = sets(R)
+    source = open(COMMIT_SOURCE).read()
+    assert "constexpr uint64_t T256_CHUNK_SCALARS = 1u << 21;" in source and "constexpr uint64_t T256_CHUNK_ROWS = 1u << 14;" in source
+    per_chunk = min(CHUNK_ROWS // L, CHUNK_SCALARS // (L * R))
+    assert (L, R, per_chunk) == (256, 256, 32) and CHUNK_SCALARS // (L * R) < CHUNK_ROWS // L
+    rng = random.Random(0xC6)
+    proofs = [(V.mixed_scalars(rng, L * R), [rng.randrange(Q) for _ in range(L)]) for _ in range(3)]
+    proofs[1][0][L * R - R - 1] = Q                                             # the last scalar of the last row but one
+    n = per_chunk + 1
+    order = [i % 3 for i in range(n)]
+    vars_, blinds, want_out, want_status, want = cycled_proofs(gens, num_vars, proofs, order)
+    assert vars_.size == n << (num_vars + 5) and [st for st, _ in want] == [MADE, MALFORMED, MADE]
+    assert want[2][1] != want[0][1] and want[2][1] != want[1][1] and order[per_chunk] == 2 and (order[0], order[1]) == (0, 1)
+    out, status = call_hyrax(cc, handle, num_vars, vars_, blinds, n)
+    assert status[per_chunk] == MADE and out[per_chunk].tobytes() == want[2][1]
+    assert out[per_chunk].tobytes() != out[0].tobytes() and out[per_chunk].tobytes() != out[1].tobytes()
+    assert (status == want_status).all()
+    assert (out.reshape(-1) == want_out).all()
+    V.assert_both_parities([rows[33 * j:33 * j + 33] for _, rows in want for j in range(L)])
 
 
 def test_empty_calls(cc, sets):
